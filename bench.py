@@ -2,6 +2,12 @@
 """bench.py -- inversion-steps/sec of the MI355X-native EG3D inversion inner loop (BASELINE.json metric).
 
   python bench.py --gpus N --steps K --warmup W          (N > 1: launched by torch.distributed.run, one rank per GPU)
+  python bench.py --gpus 1 --steps K --warmup W --full   (also every side measurement listed below)
+  python bench.py ... --dump-outputs DIR                 (also write what the last timed step computed as DIR/<name>.npy)
+
+A plain run sets up, warms up, times exactly K steps (one region), and prints the result line; `--repeats R` times R regions of K
+steps and reports the median one.  With --dump-outputs the last timed step starts from the state the projector was built with
+(InitialState, restored in an untimed pause), so the dumped outputs are the same in every run up to rounding.
 
 One "step" = one Phase-A latent-inversion step of config C2 (BASELINE.json configs[1], "FFHQ 512^2
 single-image w+ inversion, 1 x MI355X"): G.synthesis forward with grad on the full-size ffhqrebalanced512-128-shaped generator
@@ -10,7 +16,7 @@ into the latent and the 13+4 noise buffers, Adam step, noise renormalisation.  W
 (deterministic per-tensor generator); the perceptual net is the stub feature pyramid of inv3d_amd.inversion.
 N GPUs = N independent images (weak scaling), one packed stat all-reduce per step over RCCL.
 
-The JSON line also carries
+With --full (default repeats 5) the JSON line also carries
   roofline      : the dominant kernel = the conv kernel family (tile configuration x arithmetic) with the largest share of the step's
                   time: conv_v2_kernel<9,true> (csrc/conv_v2.hip, pre-split fp16 pieces, LDS-DMA staged halo) on the default settings.
                   achieved = algorithmic FLOPs of its launches (2 x MACs of the convolution) / their HIP-event
@@ -474,12 +480,79 @@ def run_child(kind, args, timeout=600):
     return dict(error=f'child process ({kind}) ended with code {r.returncode} and no result', stderr_tail=r.stderr.strip()[-300:])
 
 
+DUMP_BUDGET_BYTES = 60 << 20       # float32 payload of --dump-outputs (the .npy headers stay well inside 64 MB)
+
+
+class InitialState:
+    """The optimisation state a LatentProjector was built with: latent, noise maps, step index and random stream (its optimiser's
+    moments and step count start at zero).  Float atomics make every step differ from run to run in the last bits, and a few hundred
+    optimisation steps amplify that far beyond rounding, so with --dump-outputs the LAST timed step starts from this state again:
+    its inputs are then the same in every run and two builds compare output for output.  Restored in place (the captured step
+    reads these very tensors), outside the timed span."""
+
+    def __init__(self, proj):
+        self.proj = proj
+        self.step_idx = proj.step_idx
+        self.gen = proj.gen.get_state()
+        self.tensors = [(p, p.detach().clone()) for p in proj.optimizer.param_groups[0]['params']]
+
+    def restore(self):
+        proj = self.proj
+        with torch.no_grad():
+            for p, v in self.tensors:
+                p.copy_(v)
+            seen = set()
+            for st in proj.optimizer.state.values():       # exp_avg, exp_avg_sq, step: zero, as before the first step
+                for v in st.values():
+                    if torch.is_tensor(v) and id(v) not in seen:
+                        seen.add(id(v))
+                        v.zero_()
+        proj.gen.set_state(self.gen)
+        proj.step_idx = self.step_idx
+
+
+def dump_outputs(out_dir, proj):
+    """What the timed path computed in its last step, as float32 DIR/<name>.npy: the step's result dictionary (loss, dist, image, ...)
+    plus the optimised state it updated (the latent `w_opt`, every noise map) and the optimiser's moments (`adam.exp_avg.*`,
+    `adam.exp_avg_sq.*`: the step's full gradients, regulariser included).  Over the budget (many images per GPU) every array
+    is reduced to the same fixed, seeded sample of its flattened elements, so two builds still compare element for element."""
+    import numpy as np
+    arrays = {k: v for k, v in proj.last.items() if torch.is_tensor(v)}
+    arrays['w_opt'] = proj.w_opt
+    if proj.noise_maps:                 # several images per GPU: per-image maps owned by the projector
+        maps = list(proj.noise_maps.items())
+    else:
+        maps = [('backbone.synthesis.' + n, b) for n, b in proj.noise_bufs.items()] + [('superresolution.' + n, b) for n, b in proj.noise_bufs2.items()]
+    for n, b in maps:
+        arrays['noise.' + n] = b
+    names = {id(proj.w_opt): 'w_opt', **{id(b): 'noise.' + n for n, b in maps}}
+    for p in proj.optimizer.param_groups[0]['params']:
+        for k in ('exp_avg', 'exp_avg_sq'):
+            v = proj.optimizer.state.get(p, {}).get(k)
+            if torch.is_tensor(v):
+                arrays['adam.%s.%s' % (k, names[id(p)])] = v
+    arrays = {k: v.detach().float().contiguous().cpu().numpy() for k, v in arrays.items()}
+    total = sum(a.size for a in arrays.values()) * 4
+    keep = min(1.0, DUMP_BUDGET_BYTES / total)
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in arrays.items():
+        if keep < 1.0 and a.size > 1:
+            idx = np.sort(np.random.RandomState(0).choice(a.size, max(1, int(a.size * keep)), replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(out_dir, k + '.npy'), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
     ap.add_argument('--steps', type=int, default=200)
     ap.add_argument('--warmup', type=int, default=10)
-    ap.add_argument('--repeats', type=int, default=5, help='timed regions of --steps steps each; the line reports the median region and the spread')
+    ap.add_argument('--repeats', type=int, default=None,
+                    help='timed regions of --steps steps each (default 1; 5 with --full); the line reports the median region and the spread')
+    ap.add_argument('--full', action='store_true',
+                    help='also measure everything beside the headline: roofline passes, CPU baselines, side configurations, the final-PSNR run')
+    ap.add_argument('--dump-outputs', default=None, metavar='DIR',
+                    help='after the timed steps, write what the last timed step computed as DIR/<name>.npy (float32)')
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--no-roofline', action='store_true')
     ap.add_argument('--no-graph', action='store_true', help='launch every kernel from the host instead of replaying the captured step')
@@ -495,6 +568,10 @@ def main():
                          "section 8d); 'vgg16' = the full VGG16-LPIPS architecture (random weights) on the same kernels")
     ap.add_argument('--child', default=None, choices=['side', 'final'], help=argparse.SUPPRESS)      # internal: the side figures / the final-PSNR run in a process of their own
     args = ap.parse_args()
+    if args.repeats is None:
+        args.repeats = 5 if args.full else 1
+    if not args.full:                   # a plain run measures the headline only
+        args.no_roofline = args.no_cpu_baseline = args.no_side_configs = args.no_final_psnr = True
 
     if args.gpus > 1 and 'RANK' not in os.environ:
         # not under torch.distributed.run: launch the ranks ourselves (one process per GPU, RCCL rendezvous on the loopback address)
@@ -541,6 +618,7 @@ def main():
         return
     proj = LatentProjector(G, target, num_steps=400, cam=cam, wplus=args.wplus, seed=100 + rank, use_graph=use_graph, feature_net=feature_net)
     proj.preheat = 0
+    initial = InitialState(proj) if args.dump_outputs else None
 
     ones = torch.ones(1, device=dev)
     reducer = D.StepStatReducer(4, dev)      # the path's only collective: packed per-step stats, reduced asynchronously (no rank lockstep)
@@ -570,11 +648,22 @@ def main():
     # over ranks; the line reports the MEDIAN region (a single 0.08 .. 0.8 s sample on one box cannot tell a +3 % change from a lucky lease) and the
     # min / max beside it.  With the launch profiler on (eager --no-graph runs) one region only: the profiler brackets every launch of it.
     regions = []
-    for _ in range(1 if prof is not None else max(1, args.repeats)):
+    n_regions = 1 if prof is not None else max(1, args.repeats)
+    psnr_now = None
+    for r in range(n_regions):
         torch.cuda.synchronize()
         D.barrier()
         t0 = time.perf_counter()
-        for _ in range(args.steps):
+        for i in range(args.steps):
+            if initial is not None and r == n_regions - 1 and i == args.steps - 1:
+                # --dump-outputs: the last timed step starts from the state the projector was built with (InitialState), so that what it
+                # computes is the same in every run; the pause for the restore is not timed
+                torch.cuda.synchronize()
+                t_pause = time.perf_counter()
+                psnr_now = float(psnr_01(proj.last['image'], target))
+                initial.restore()
+                torch.cuda.synchronize()
+                t0 += time.perf_counter() - t_pause
             one_step()
         torch.cuda.synchronize()
         D.barrier()
@@ -582,7 +671,10 @@ def main():
     elapsed = sorted(regions)[len(regions) // 2]
     H.PROFILER = None
     step_stats = reducer.finish()              # [sum loss, sum dist, steps x ranks, .] over everything pushed (warm-up included)
-    psnr_now = float(psnr_01(proj.last['image'], target))
+    if psnr_now is None:
+        psnr_now = float(psnr_01(proj.last['image'], target))
+    if args.dump_outputs and rank == 0:       # before anything else runs on the generator (its noise buffers are the projector's state)
+        dump_outputs(args.dump_outputs, proj)
     roofline_pass = 'HIP events around every launch of the kernel inside the timed region'
     if not args.no_roofline and use_graph:
         # HIP events cannot bracket a kernel inside a captured graph: the per-launch durations of the dominant kernel come from an

@@ -46,7 +46,7 @@ def test_pti_10_steps_cpu():
 def test_config_c1_at_full_size_cpu():
     """BASELINE.json configs[0] as worded: the ffhqrebalanced512-128-shaped generator, one image, 10 PTI steps on CPU through the pure-PyTorch
     path (the oracle = the pinned port of the reference's `_ref` ops) -- preceded by 2 latent steps so both phases of PTI run at full size.
-    ~1 minute on 8 cores; bench.py times the same steps on the GPU box's host as `cpu_baseline` / `cpu_baseline_c1`."""
+    ~1 minute on 8 cores; `bench.py --full` times the same steps on the GPU box's host as `cpu_baseline` / `cpu_baseline_c1`."""
     cfg = O.full_config()
     P = O.synth_params(cfg, 0)
     cam = O.synth_cameras(1, seed=2)

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Executes INTEGRATION.md section 1 against the real checkout.  BUILD CONTAINER ONLY (needs /root/reference; CPU is enough: nothing
-here launches a kernel).  `tests/test_host.py::test_reference_binding_against_checkout` runs it in a subprocess when the checkout exists.
+here launches a kernel).  Run it by hand; the suite checks the mechanism on stand-in checkouts (tests/test_host.py, tests/test_weights_cpu.py).
 
     python tools/check_reference_binding.py [/path/to/3DGAN-Inversion]
 

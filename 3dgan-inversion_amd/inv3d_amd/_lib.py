@@ -218,6 +218,14 @@ class StyleBank(C.Structure):
                 ('layers', StyleLayer * STYLE_BANK_MAX)]
 
 
+class McParams(C.Structure):
+    """eg3d_mc_params: marching cubes (eg3d_mc_query_workspace / eg3d_mc_count / eg3d_mc_emit)."""
+    _fields_ = [('vol', C.c_void_p), ('D0', C.c_int32), ('D1', C.c_int32), ('D2', C.c_int32), ('level', C.c_float),
+                ('origin', C.c_float * 3), ('spacing', C.c_float * 3), ('workspace', C.c_void_p), ('workspace_bytes', C.c_int64),
+                ('totals', C.c_void_p), ('emit_workspace', C.c_void_p), ('emit_workspace_bytes', C.c_int64),
+                ('verts', C.c_void_p), ('vert_capacity', C.c_int64), ('faces', C.c_void_p), ('face_capacity', C.c_int64)]
+
+
 _SIGS = {
     'eg3d_abi_version': (C.c_int, []),
     'eg3d_status_string': (C.c_char_p, [C.c_int]),
@@ -339,6 +347,9 @@ _SIGS = {
     'eg3d_triplane_scatter_workspace_ints': (C.c_int64, [C.c_int64, C.c_int, C.c_int, C.c_int]),
     'eg3d_triplane_scatter': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float,
                                         C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    'eg3d_mc_query_workspace': (C.c_int, [C.POINTER(McParams), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    'eg3d_mc_count': (C.c_int, [C.POINTER(McParams), C.c_void_p]),
+    'eg3d_mc_emit': (C.c_int, [C.POINTER(McParams), C.c_void_p]),
     'eg3d_sample_decode': (C.c_int, [C.POINTER(RenderParams), C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
 }
 

@@ -11,8 +11,11 @@ training/projectors/w_projector.py:55-283), reduced to what touches the generato
         metrics: MSE / PSNR of the pivot and of the tuned reconstruction
     one packed-stat all-reduce over the ranks at the end     (inv3d_amd.dist)
 
-Images are independent optimisations, so N GPUs = N shards with no data-path communication (weak scaling).  File I/O, logging,
-video / mesh export and the third-party encoders (e4e, ResNet pose head, ArcFace) of the reference loop are outside this package.
+Images are independent optimisations, so N GPUs = N shards with no data-path communication (weak scaling).  Shape export is here:
+with `gen_mesh` every image's tuned generator writes {mesh_dir}/{name}_pti.mrc (or .ply) at the pivot latent after Phase B, as
+global_config.gen_mesh -> create_geometry does (single_id_coach.py:109-110,120-163; inference.density_grid / extract_mesh / write_mrc /
+write_ply).  Image / video file I/O, logging and the third-party encoders (e4e, ResNet pose head, ArcFace) of the reference loop are
+outside this package.
 """
 from dataclasses import dataclass, field
 from typing import Callable, Dict, List, Optional, Sequence, Tuple
@@ -22,7 +25,7 @@ import os
 import torch
 
 from . import dist as D
-from .inference import estimate_w_stats
+from .inference import density_grid, estimate_w_stats, extract_mesh, write_mrc, write_ply
 from .inversion import LatentProjector, PivotalTuner, psnr_01
 
 
@@ -37,6 +40,7 @@ class InversionResult:
     steps_a: int
     steps_b: int
     tuned_state: Optional[Dict[str, torch.Tensor]] = field(default=None, repr=False)    # generator weights after Phase B (opt-in)
+    mesh_path: Optional[str] = None                                                       # the shape written with gen_mesh
 
 
 class InversionCoach:
@@ -45,13 +49,22 @@ class InversionCoach:
                  feature_net: Optional[Callable] = None, early_stop_interval: int = 1, use_graph: bool = False, keep_tuned_state: bool = False,
                  synth_kwargs: Optional[dict] = None, seed: int = 0, pose_net_factory: Optional[Callable] = None, pose_mode: str = 'quat',
                  w_avg_samples: int = 10000, w_stats: Optional[Tuple[torch.Tensor, float]] = None,
-                 start_w_fn: Optional[Callable[[torch.Tensor], torch.Tensor]] = None, sr_fp16: bool = True):
+                 start_w_fn: Optional[Callable[[torch.Tensor], torch.Tensor]] = None, sr_fp16: bool = True, gen_mesh: bool = False,
+                 mesh_dir: Optional[str] = None, mesh_res: int = 512, mesh_level: float = 10.0, mesh_format: str = '.mrc'):
         """Hyper-parameter names and defaults follow configs/hyperparameters.py.  `early_stop_interval` = how often Phase B reads the
         early-stop state back to the host (1 = every step like the reference).  With the library's Adam the TEST itself runs on the device
         in every step whatever the interval (PivotalTuner.device_stop): the interval then only bounds how many masked no-op steps are
         issued after the stop, not when tuning stops.  Phase A starts where the reference starts (w_projector.py:88-97,100,118): at the mean latent
         of `w_avg_samples` mapped z (plus `start_w_fn(target_255_256)`, the e4e encoder's offset, when given) with the latent-noise scale
-        tied to their standard deviation; `w_stats=(w_avg, w_std)` overrides the estimate, `w_avg_samples=0` starts at w = 0, std 1."""
+        tied to their standard deviation; `w_stats=(w_avg, w_std)` overrides the estimate, `w_avg_samples=0` starts at w = 0, std 1.
+        `gen_mesh` (global_config.gen_mesh): after Phase B write the tuned generator's shape at the pivot latent to
+        {mesh_dir}/{name}_pti{mesh_format} like create_geometry(shape_res=mesh_res, shape_format=mesh_format): '.mrc' = the raw density grid,
+        '.ply' = its marching-cubes mesh at `mesh_level` (the reference's level 10)."""
+        if mesh_format not in ('.mrc', '.ply'):
+            raise ValueError(f"mesh_format must be '.mrc' or '.ply', got {mesh_format!r}")
+        if gen_mesh and not mesh_dir:
+            raise ValueError('gen_mesh needs a mesh_dir')
+        self.gen_mesh, self.mesh_dir, self.mesh_res, self.mesh_level, self.mesh_format = gen_mesh, mesh_dir, int(mesh_res), float(mesh_level), mesh_format
         self.G = G
         self.first_inv_steps, self.max_pti_steps, self.thr = first_inv_steps, max_pti_steps, lpips_threshold
         self.first_inv_lr, self.pti_lr = first_inv_lr, pti_lr
@@ -138,7 +151,19 @@ class InversionCoach:
             mse = float(((img.clamp(-1, 1) - target) ** 2).mean() / 4.0)
         state = {k: v.detach().clone() for k, v in G.state_dict().items()} if self.keep else None
         G.requires_grad_(False)
-        return InversionResult(name, w_pivot, cam_pivot, psnr_pivot, psnr_tuned, mse, self.first_inv_steps, steps_b, state)
+        mesh_path = self.write_mesh(name, w_pivot) if self.gen_mesh else None
+        return InversionResult(name, w_pivot, cam_pivot, psnr_pivot, psnr_tuned, mse, self.first_inv_steps, steps_b, state, mesh_path)
+
+    def write_mesh(self, name: str, w_pivot: torch.Tensor) -> str:
+        """create_geometry(G, w_pivot, outdir=mesh_dir, fname=name + '_pti') with the generator as it is now (the tuned one)."""
+        os.makedirs(self.mesh_dir, exist_ok=True)
+        path = os.path.join(self.mesh_dir, f'{name}_pti{self.mesh_format}')
+        if self.mesh_format == '.ply':
+            verts, faces = extract_mesh(self.G, w_pivot, res=self.mesh_res, level=self.mesh_level)
+            write_ply(path, verts, faces)
+        else:
+            write_mrc(path, density_grid(self.G, w_pivot, res=self.mesh_res))
+        return path
 
     def run(self, images: Sequence[Tuple[str, torch.Tensor, Optional[torch.Tensor]]]) -> Tuple[List[InversionResult], Dict[str, float]]:
         """Invert this rank's shard of `images` = [(name, target [1,3,H,W] in [-1,1], cam [1,25] | None), ...] (every rank passes the

@@ -1837,3 +1837,40 @@ def noise_normalize_(bufs):
         n, xs, res = _buf_arrays(bufs[lo:lo + NOISE_BANK_MAX])
         ws = zeros((2 * n,), bufs[0].device)          # per-buffer (sum, sum of squares): multi-block path
         L.check(L.lib().eg3d_noise_normalize(xs, res, n, L.ptr(ws), L.stream_ptr()), 'noise_normalize')
+
+
+_INT32_MAX = 2 ** 31 - 1
+
+
+def marching_cubes(vol: torch.Tensor, level: float, origin=None, spacing=None):
+    """(verts fp32 [V,3], faces int32 [F,3]) of the level-`level` surface of the fp32 grid vol [D0,D1,D2] (eg3d_mc_*; include/eg3d_hip.h):
+    the frame of skimage's marching_cubes(vol.transpose(2,1,0), level) (grid point (i0,i1,i2) -> (i2,i1,i0)), then * spacing + origin per
+    output axis.  Inside = v > level; the faces' right-hand normals point toward lower values.  Finite values assumed.  Workspace from
+    the caching allocator; one host synchronise (the totals)."""
+    L.require_cuda(vol)
+    if vol.dim() != 3 or vol.dtype != torch.float32:
+        raise L.Eg3dHipError(f'marching_cubes: a 3-D fp32 grid, got {tuple(vol.shape)} {vol.dtype}')
+    vol = vol.contiguous()
+    dev = vol.device
+    p = L.McParams(vol=vol.data_ptr(), D0=vol.shape[0], D1=vol.shape[1], D2=vol.shape[2], level=float(level))
+    p.origin[:] = [float(v) for v in (origin if origin is not None else (0.0, 0.0, 0.0))]
+    p.spacing[:] = [float(v) for v in (spacing if spacing is not None else (1.0, 1.0, 1.0))]
+    lib = L.lib()
+    count_bytes, per_active = C.c_int64(0), C.c_int64(0)
+    L.check(lib.eg3d_mc_query_workspace(C.byref(p), C.byref(count_bytes), C.byref(per_active)), 'mc_query_workspace')
+    ws = torch.empty(count_bytes.value, dtype=torch.uint8, device=dev)
+    totals = torch.empty(4, dtype=torch.int64, device=dev)
+    p.workspace, p.workspace_bytes, p.totals = ws.data_ptr(), count_bytes.value, totals.data_ptr()
+    L.check(lib.eg3d_mc_count(C.byref(p), L.stream_ptr()), 'mc_count')
+    A, V, F, _ = totals.tolist()
+    if max(A, V, F) > _INT32_MAX:
+        L.check(-3, f'marching_cubes ({A} active points, {V} vertices, {F} faces)')
+    verts = torch.empty((V, 3), dtype=torch.float32, device=dev)
+    faces = torch.empty((F, 3), dtype=torch.int32, device=dev)
+    if A == 0:
+        return verts, faces
+    emit = torch.empty(A * per_active.value, dtype=torch.uint8, device=dev)
+    p.emit_workspace, p.emit_workspace_bytes = emit.data_ptr(), emit.numel()
+    p.verts, p.vert_capacity, p.faces, p.face_capacity = verts.data_ptr(), V, faces.data_ptr(), F
+    L.check(lib.eg3d_mc_emit(C.byref(p), L.stream_ptr()), 'mc_emit')
+    return verts, faces

@@ -6,11 +6,15 @@ G.mapping / ImportanceRenderer.run_model on the gfx950 kernels.
                                   returned as tensors)
   estimate_w_stats             <- mean latent / spread of the projector, training/projectors/w_projector.py:88-97
   density_grid                 <- create_geometry + create_samples, training/coaches/single_id_coach.py:120-186 (sigma on a res^3 grid)
+  extract_mesh, write_ply      <- create_geometry's '.ply' branch (single_id_coach.py:155-157) and convert_sdf_samples_to_ply /
+                                  convert_mrc, shape_utils.py:40-100: marching cubes on the device (hipops.marching_cubes), no skimage / plyfile
+  write_mrc                    <- create_geometry's '.mrc' branch (single_id_coach.py:158-160, mrcfile.new_mmap mode 2), no mrcfile
 
 Differences from the reference that do not change results: the tri-planes of a fixed latent are synthesised once per orbit / per grid
 instead of once per frame / per chunk (the reference re-runs the backbone every time), and grid coordinates are generated per chunk on
 the device instead of materialising res^3 x 3 floats on the host."""
 import math
+import struct
 from typing import Iterator, Optional, Tuple
 
 import numpy as np
@@ -120,3 +124,67 @@ def density_grid(G, ws: torch.Tensor, res: int = 512, max_batch: int = 1 << 22, 
         g[:, :, :pad] = pad_value
         g[:, :, -pad:] = pad_value
     return g
+
+
+@torch.no_grad()
+def extract_mesh(G, ws: torch.Tensor, res: int = 512, level: float = 10.0, max_batch: int = 1 << 22, **synthesis_kwargs):
+    """(verts fp32 [V,3], faces int32 [F,3]) on the device: density_grid, then marching cubes at `level` in the coordinates of the reference's
+    PLY (marching_cubes(np.transpose(grid, (2,1,0)), level, spacing=[1]*3), origin [0,0,0]: voxel units).  Faces are wound so that their
+    right-hand normals point out of the dense region.  Triangles may differ from skimage's Lewiner method in ambiguous cubes; vertices do not."""
+    from .hipops import marching_cubes
+    grid = density_grid(G, ws, res=res, max_batch=max_batch, **synthesis_kwargs)
+    return marching_cubes(grid, level)
+
+
+def _host(a, dtype):
+    if isinstance(a, torch.Tensor):
+        a = a.detach().cpu().numpy()
+    return np.ascontiguousarray(a, dtype=dtype)
+
+
+def write_ply(path: str, verts, faces) -> None:
+    """Binary little-endian PLY with the header plyfile writes for the reference's dtypes (shape_utils.py:84-97: vertex x, y, z 'f4'; face
+    vertex_indices 'i4' x 3 as a list with a uchar count)."""
+    v = _host(verts, np.float32).reshape(-1, 3)
+    f = _host(faces, np.int32).reshape(-1, 3)
+    header = '\n'.join(['ply', 'format binary_little_endian 1.0', f'element vertex {len(v)}', 'property float x', 'property float y',
+                        'property float z', f'element face {len(f)}', 'property list uchar int vertex_indices', 'end_header']) + '\n'
+    rec = np.empty(len(f), dtype=np.dtype([('n', 'u1'), ('i', '<i4', (3,))]))
+    rec['n'] = 3
+    rec['i'] = f
+    with open(path, 'wb') as fh:
+        fh.write(header.encode('ascii'))
+        fh.write(np.ascontiguousarray(v, dtype='<f4').data)
+        fh.write(rec.tobytes())
+
+
+def write_mrc(path: str, grid) -> None:
+    """MRC2014 mode 2 (fp32) file of the [nz, ny, nx] grid as the reference writes it un-transposed (mrcfile.new_mmap(shape=grid.shape,
+    mrc_mode=2)): 1024-byte header (nx = shape[2], ny = shape[1], nz = shape[0]; mx/my/mz = the same; cell 0, angles 90; mapc/r/s = 1,2,3;
+    dmin/dmax/dmean/rms of the data; ispg 1; nversion 20140; 'MAP '; little-endian stamp 44 44 00 00), then the data, x fastest."""
+    if isinstance(grid, torch.Tensor):
+        g = grid.detach()
+        if g.dim() != 3:
+            raise ValueError(f'write_mrc: a 3-D grid, got {tuple(g.shape)}')
+        g64 = g.double()
+        stats = (float(g.min()), float(g.max()), float(g64.mean()), float(g64.std(unbiased=False)))
+        data = _host(g, np.float32)
+    else:
+        data = _host(grid, np.float32)
+        if data.ndim != 3:
+            raise ValueError(f'write_mrc: a 3-D grid, got {data.shape}')
+        stats = (float(data.min()), float(data.max()), float(data.mean(dtype=np.float64)), float(data.std(dtype=np.float64)))
+    nz, ny, nx = data.shape
+    h = bytearray(1024)
+    struct.pack_into('<10i', h, 0, nx, ny, nz, 2, 0, 0, 0, nx, ny, nz)
+    struct.pack_into('<6f', h, 40, 0.0, 0.0, 0.0, 90.0, 90.0, 90.0)
+    struct.pack_into('<3i', h, 64, 1, 2, 3)
+    struct.pack_into('<3f', h, 76, stats[0], stats[1], stats[2])
+    struct.pack_into('<2i', h, 88, 1, 0)
+    struct.pack_into('<i', h, 108, 20140)
+    h[208:212] = b'MAP '
+    h[212:216] = bytes([0x44, 0x44, 0x00, 0x00])
+    struct.pack_into('<f', h, 216, stats[3])
+    with open(path, 'wb') as fh:
+        fh.write(bytes(h))
+        fh.write(np.ascontiguousarray(data, dtype='<f4').data)

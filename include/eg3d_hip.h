@@ -967,6 +967,43 @@ int eg3d_grid_sample_nhwc_fwd(const float* input, const float* grid, float* out,
 int eg3d_grid_sample_nhwc_bwd(const float* input, const float* grid, const float* dout, float* dgrid, float* dinput, int N, int H, int W, int C, int Ho,
                               int Wo, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Marching cubes (shape export) -- replaces skimage.measure.marching_cubes(np.transpose(sigmas, (2,1,0)), level, spacing=[1]*3) in
+ *   create_geometry, training/coaches/single_id_coach.py:120-163, and convert_mrc, shape_utils.py:40-100 (csrc/marching_cubes.hip).
+ *   vol: contiguous fp32 [D0][D1][D2] (i2 fastest), D0, D1, D2 >= 2, D0*D1*D2 < 2^31, finite values.  A corner is inside iff v > level.
+ *   One vertex per grid edge whose ends differ in inside-ness: p = a + t (b - a), t = (level - v_a) / (v_b - v_a) in fp32 (a = the end of
+ *   lower linear index); grid point (i0, i1, i2) is the vertex coordinate (i2, i1, i0); written as p * spacing[k] + origin[k].
+ *   Faces: int32 triples, right-hand normal toward lower values (a closed surface around a dense blob has positive signed volume).
+ *   Order: vertices by (owning grid point = the edge's lower end, axis x, y, z); faces by (cube's min-corner linear index, table order of
+ *   csrc/mc_tables.h).  Bit-identical from run to run and between the two builds (no atomics).
+ *   Protocol:
+ *     eg3d_mc_query_workspace  host only: count workspace bytes, and emit workspace bytes per active point (16-byte aligned buffers)
+ *     eg3d_mc_count            fills `workspace` and writes totals[0..3] = (active points A, vertices V, faces F, 0) on the device
+ *     (host reads totals: one synchronise; allocates verts [V,3], faces [F,3], emit workspace A * emit_bytes_per_active)
+ *     eg3d_mc_emit             writes verts / faces, never beyond vert_capacity / face_capacity rows or the emit workspace
+ *   V = F = 0 is a normal result.  A grid of 2^31 points or more, or capacities of 2^31 rows or more: EG3D_ERR_TOO_LARGE (the caller checks
+ *   the totals the same way before it allocates).
+ */
+typedef struct eg3d_mc_params {
+    const float* vol;
+    int32_t D0, D1, D2;
+    float level;
+    float origin[3];                   /* per output axis x, y, z; 0 / 1 = the reference's frame */
+    float spacing[3];
+    void* workspace;                   /* eg3d_mc_query_workspace's count_bytes */
+    int64_t workspace_bytes;
+    int64_t* totals;                   /* device int64[4] */
+    void* emit_workspace;              /* A x emit_bytes_per_active */
+    int64_t emit_workspace_bytes;
+    float* verts;                      /* [vert_capacity, 3] */
+    int64_t vert_capacity;
+    int32_t* faces;                    /* [face_capacity, 3] */
+    int64_t face_capacity;
+} eg3d_mc_params;
+int eg3d_mc_query_workspace(const eg3d_mc_params* p, int64_t* count_bytes, int64_t* emit_bytes_per_active);
+int eg3d_mc_count(const eg3d_mc_params* p, void* stream);
+int eg3d_mc_emit(const eg3d_mc_params* p, void* stream);
+
 /* Measurement aid (bench.py): a register-only v_mfma_f32_32x32x16_f16 loop on caller-supplied fp16 data -- what the matrix pipe sustains on
  * this chip at its current power / clock state, timed inside the benchmark run.  in: 4096 x 8 fp16 (64 KiB); out: blocks x 256 floats;
  * executes blocks x 4 waves x iters x 24 MFMAs of 32 x 32 x 16.  No reference counterpart. */

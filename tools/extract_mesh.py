@@ -1,0 +1,56 @@
+"""Shape export from the command line: a latent in, a mesh out (create_geometry's '.ply' branch, training/coaches/single_id_coach.py:120-163;
+convert_sdf_samples_to_ply, shape_utils.py:40-100), on the GPU kernels of this package.
+
+  python tools/extract_mesh.py --ws pivot_ws.npy --out face.ply [--weights G.safetensors] [--res 512] [--level 10] [--mrc face.mrc]
+
+--weights: a generator archive (inv3d_amd.weights, tools/convert_eg3d_pickle.py); without it, the full-size synthetic generator
+(inv3d_amd.synthetic, seed --seed).  --ws: a [1, num_ws, w_dim] (or [num_ws, w_dim]) .npy latent, e.g. the reference's {image}_ws.npy.
+--mrc additionally writes the density grid as create_geometry's '.mrc' branch does."""
+import argparse
+import os
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, '3dgan-inversion_amd'))
+
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__.splitlines()[0])
+    ap.add_argument('--ws', required=True, help='latent .npy, [1, num_ws, w_dim] or [num_ws, w_dim]')
+    ap.add_argument('--out', required=True, help='output .ply')
+    ap.add_argument('--weights', default=None, help='generator archive; default: the synthetic full-size generator')
+    ap.add_argument('--seed', type=int, default=0, help='synthetic generator weights seed')
+    ap.add_argument('--res', type=int, default=512)
+    ap.add_argument('--level', type=float, default=10.0)
+    ap.add_argument('--mrc', default=None, help='also write the density grid to this .mrc')
+    a = ap.parse_args()
+    from inv3d_amd import inference as INF
+    dev = torch.device('cuda')
+    if a.weights:
+        from inv3d_amd.weights import load_generator
+        G = load_generator(a.weights, device=dev)
+    else:
+        from inv3d_amd import synthetic as S
+        G = S.make_generator(device=dev)
+        S.load_synthetic_weights(G, seed=a.seed)
+    ws = torch.from_numpy(np.load(a.ws)).float().to(dev)
+    if ws.dim() == 2:
+        ws = ws.unsqueeze(0)
+    t0 = time.perf_counter()
+    grid = INF.density_grid(G, ws, res=a.res)
+    from inv3d_amd.hipops import marching_cubes
+    verts, faces = marching_cubes(grid, a.level)
+    torch.cuda.synchronize()
+    dt = time.perf_counter() - t0
+    INF.write_ply(a.out, verts, faces)
+    if a.mrc:
+        INF.write_mrc(a.mrc, grid)
+    print(f'{a.out}: {verts.shape[0]} vertices, {faces.shape[0]} faces ({a.res}^3 grid, level {a.level}; grid + march {dt * 1e3:.1f} ms)')
+
+
+if __name__ == '__main__':
+    main()

@@ -29,3 +29,11 @@ for res in (256, 512):
     print(f'density grid {res}^3: {dt * 1e3:.1f} ms = {res ** 3 / dt / 1e9:.2f} G points/s', flush=True)
 dt, (w_avg, w_std) = timed(lambda: INF.estimate_w_stats(G, num_samples=10000))
 print(f'w_avg over 10000 mapped latents: {dt * 1e3:.1f} ms (w_std {w_std:.4f})', flush=True)
+# marching cubes alone on the full-size grid (g: the 512^3 grid of the loop above): count + scan + emit + faces, one host synchronise inside
+from inv3d_amd import hipops as H
+for level in (10.0, float(torch.quantile(g[60:-60:4, 60:-60:4, 60:-60:4].reshape(-1), 0.7))):
+    H.marching_cubes(g, level)
+    dt, (v, f) = timed(lambda: H.marching_cubes(g, level), reps=10)
+    floor = 2 * g.numel() * 4            # two passes read the grid: >= 1 GB at 512^3 (~0.13 ms at 8 TB/s)
+    print(f'marching cubes 512^3 level {level:.3f}: {dt * 1e3:.2f} ms, V {v.shape[0]} F {f.shape[0]}, '
+          f'{floor / dt / 1e12:.2f} TB/s against the {floor / 1e9:.2f} GB byte floor', flush=True)

@@ -226,6 +226,18 @@ class McParams(C.Structure):
                 ('verts', C.c_void_p), ('vert_capacity', C.c_int64), ('faces', C.c_void_p), ('face_capacity', C.c_int64)]
 
 
+SSIM_MAX_LEVELS = 8
+
+
+class SsimParams(C.Structure):
+    """eg3d_ssim_params: SSIM / MS-SSIM (eg3d_ssim_query_workspace / eg3d_ssim_forward / eg3d_ssim_backward)."""
+    _fields_ = [('x', C.c_void_p), ('y', C.c_void_p), ('N', C.c_int32), ('C', C.c_int32), ('H', C.c_int32), ('W', C.c_int32),
+                ('mode', C.c_int32), ('levels', C.c_int32), ('nonnegative', C.c_int32), ('size_average', C.c_int32), ('win_size', C.c_int32),
+                ('win_sigma', C.c_float), ('C1', C.c_float), ('C2', C.c_float), ('weights', C.c_float * SSIM_MAX_LEVELS),
+                ('pyramid', C.c_void_p), ('stats', C.c_void_p), ('out', C.c_void_p), ('workspace', C.c_void_p), ('workspace_bytes', C.c_int64),
+                ('grad_out', C.c_void_p), ('grad_x', C.c_void_p), ('grad_y', C.c_void_p)]
+
+
 _SIGS = {
     'eg3d_abi_version': (C.c_int, []),
     'eg3d_status_string': (C.c_char_p, [C.c_int]),
@@ -350,6 +362,11 @@ _SIGS = {
     'eg3d_mc_query_workspace': (C.c_int, [C.POINTER(McParams), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     'eg3d_mc_count': (C.c_int, [C.POINTER(McParams), C.c_void_p]),
     'eg3d_mc_emit': (C.c_int, [C.POINTER(McParams), C.c_void_p]),
+    'eg3d_ssim_query_workspace': (C.c_int, [C.POINTER(SsimParams), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64),
+                                            C.POINTER(C.c_int64)]),
+    'eg3d_ssim_forward': (C.c_int, [C.POINTER(SsimParams), C.c_void_p]),
+    'eg3d_ssim_backward': (C.c_int, [C.POINTER(SsimParams), C.c_void_p]),
+    'eg3d_face_pool': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     'eg3d_sample_decode': (C.c_int, [C.POINTER(RenderParams), C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
 }
 

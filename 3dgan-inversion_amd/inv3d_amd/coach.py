@@ -14,19 +14,23 @@ training/projectors/w_projector.py:55-283), reduced to what touches the generato
 Images are independent optimisations, so N GPUs = N shards with no data-path communication (weak scaling).  Shape export is here:
 with `gen_mesh` every image's tuned generator writes {mesh_dir}/{name}_pti.mrc (or .ply) at the pivot latent after Phase B, as
 global_config.gen_mesh -> create_geometry does (single_id_coach.py:109-110,120-163; inference.density_grid / extract_mesh / write_mrc /
-write_ply).  Image / video file I/O, logging and the third-party encoders (e4e, ResNet pose head, ArcFace) of the reference loop are
-outside this package.
+write_ply).  Evaluation is here too: with `do_evaluation` the tuned reconstruction's mse / lpips / msssim / identity (metrics.py: GPU
+MS-SSIM, the ArcFace IR-SE-50 identity distance) go to {eval_dir}/{name}metrics.txt, and `save_pivot` writes {name}_ws.npy /
+{name}_cam.npy (single_id_coach.py:87-117).  Image / video file I/O and logging of the reference loop are outside this package; the
+e4e encoder, the pose head and ArcFace are in e4e.py, pose_net.py and metrics.py.
 """
 from dataclasses import dataclass, field
 from typing import Callable, Dict, List, Optional, Sequence, Tuple
 
 import os
 
+import numpy as np
 import torch
 
 from . import dist as D
 from .inference import density_grid, estimate_w_stats, extract_mesh, write_mrc, write_ply
 from .inversion import LatentProjector, PivotalTuner, psnr_01
+from .metrics import IDLoss, format_metrics_txt, reconstruction_metrics
 
 
 @dataclass
@@ -41,6 +45,7 @@ class InversionResult:
     steps_b: int
     tuned_state: Optional[Dict[str, torch.Tensor]] = field(default=None, repr=False)    # generator weights after Phase B (opt-in)
     mesh_path: Optional[str] = None                                                       # the shape written with gen_mesh
+    metrics: Optional[Dict[str, float]] = None                                            # mse / lpips / msssim / identity with do_evaluation
 
 
 class InversionCoach:
@@ -50,7 +55,9 @@ class InversionCoach:
                  synth_kwargs: Optional[dict] = None, seed: int = 0, pose_net_factory: Optional[Callable] = None, pose_mode: str = 'quat',
                  w_avg_samples: int = 10000, w_stats: Optional[Tuple[torch.Tensor, float]] = None,
                  start_w_fn: Optional[Callable[[torch.Tensor], torch.Tensor]] = None, sr_fp16: bool = True, gen_mesh: bool = False,
-                 mesh_dir: Optional[str] = None, mesh_res: int = 512, mesh_level: float = 10.0, mesh_format: str = '.mrc'):
+                 mesh_dir: Optional[str] = None, mesh_res: int = 512, mesh_level: float = 10.0, mesh_format: str = '.mrc',
+                 do_evaluation: bool = False, eval_dir: Optional[str] = None, lpips_eval_net: Optional[Callable] = None,
+                 id_net: Optional[Callable] = None, save_pivot: bool = False, pivot_dir: Optional[str] = None):
         """Hyper-parameter names and defaults follow configs/hyperparameters.py.  `early_stop_interval` = how often Phase B reads the
         early-stop state back to the host (1 = every step like the reference).  With the library's Adam the TEST itself runs on the device
         in every step whatever the interval (PivotalTuner.device_stop): the interval then only bounds how many masked no-op steps are
@@ -59,12 +66,29 @@ class InversionCoach:
         tied to their standard deviation; `w_stats=(w_avg, w_std)` overrides the estimate, `w_avg_samples=0` starts at w = 0, std 1.
         `gen_mesh` (global_config.gen_mesh): after Phase B write the tuned generator's shape at the pivot latent to
         {mesh_dir}/{name}_pti{mesh_format} like create_geometry(shape_res=mesh_res, shape_format=mesh_format): '.mrc' = the raw density grid,
-        '.ply' = its marching-cubes mesh at `mesh_level` (the reference's level 10)."""
+        '.ply' = its marching-cubes mesh at `mesh_level` (the reference's level 10).
+        `do_evaluation` (global_config.do_evaluation): after Phase B render G.synthesis(w_pivot[:, :14], cam[:, :25]) with the tuned generator and
+        write metrics.reconstruction_metrics to {eval_dir}/{name}metrics.txt; `lpips_eval_net` (LPIPSAlex) and `id_net` (IDLoss) are built
+        once per coach when None.  `save_pivot` writes {pivot_dir}/{name}_ws.npy and {name}_cam.npy; in the reference it only takes effect
+        under do_evaluation, here it is independent of it (like gen_mesh)."""
+        if do_evaluation and not eval_dir:
+            raise ValueError('do_evaluation needs an eval_dir')
+        if save_pivot and not pivot_dir:
+            raise ValueError('save_pivot needs a pivot_dir')
         if mesh_format not in ('.mrc', '.ply'):
             raise ValueError(f"mesh_format must be '.mrc' or '.ply', got {mesh_format!r}")
         if gen_mesh and not mesh_dir:
             raise ValueError('gen_mesh needs a mesh_dir')
         self.gen_mesh, self.mesh_dir, self.mesh_res, self.mesh_level, self.mesh_format = gen_mesh, mesh_dir, int(mesh_res), float(mesh_level), mesh_format
+        self.do_evaluation, self.eval_dir, self.save_pivot, self.pivot_dir = do_evaluation, eval_dir, save_pivot, pivot_dir
+        self.lpips_eval_net, self.id_net = lpips_eval_net, id_net
+        if do_evaluation:
+            dev = next(G.parameters()).device
+            if self.lpips_eval_net is None:
+                from .loss_nets import LPIPSAlex
+                self.lpips_eval_net = LPIPSAlex('pm1').to(dev)           # lpips.LPIPS(net='alex') (base_coach.py:48)
+            if self.id_net is None:
+                self.id_net = IDLoss().to(dev)
         self.G = G
         self.first_inv_steps, self.max_pti_steps, self.thr = first_inv_steps, max_pti_steps, lpips_threshold
         self.first_inv_lr, self.pti_lr = first_inv_lr, pti_lr
@@ -152,7 +176,22 @@ class InversionCoach:
         state = {k: v.detach().clone() for k, v in G.state_dict().items()} if self.keep else None
         G.requires_grad_(False)
         mesh_path = self.write_mesh(name, w_pivot) if self.gen_mesh else None
-        return InversionResult(name, w_pivot, cam_pivot, psnr_pivot, psnr_tuned, mse, self.first_inv_steps, steps_b, state, mesh_path)
+        metrics = self.evaluate(name, w_pivot, cam_pivot, target) if self.do_evaluation else None
+        if self.save_pivot:
+            os.makedirs(self.pivot_dir, exist_ok=True)
+            np.save(os.path.join(self.pivot_dir, f'{name}_cam.npy'), cam_pivot.detach().cpu().numpy())
+            np.save(os.path.join(self.pivot_dir, f'{name}_ws.npy'), w_pivot.detach().cpu().numpy())
+        return InversionResult(name, w_pivot, cam_pivot, psnr_pivot, psnr_tuned, mse, self.first_inv_steps, steps_b, state, mesh_path, metrics)
+
+    def evaluate(self, name: str, w_pivot: torch.Tensor, cam: torch.Tensor, target: torch.Tensor) -> Dict[str, float]:
+        """single_id_coach.py:87-106 with the generator as it is now (the tuned one): the metrics, written to {eval_dir}/{name}metrics.txt."""
+        with torch.no_grad():
+            img = self.G.synthesis(w_pivot[:, :14], cam[:, :25], noise_mode='const', force_fp32=True, **self.synth_kwargs)['image']
+        m = reconstruction_metrics(img, target, self.lpips_eval_net, self.id_net)
+        os.makedirs(self.eval_dir, exist_ok=True)
+        with open(os.path.join(self.eval_dir, f'{name}metrics.txt'), 'w') as f:
+            f.write(format_metrics_txt(m))
+        return m
 
     def write_mesh(self, name: str, w_pivot: torch.Tensor) -> str:
         """create_geometry(G, w_pivot, outdir=mesh_dir, fname=name + '_pti') with the generator as it is now (the tuned one)."""
@@ -181,5 +220,12 @@ class InversionCoach:
                                        n_done=float(len(results)), steps=float(sum(r.steps_a + r.steps_b for r in results))), dev)
         if stats['n_done'] > 0:
             stats['mean_psnr'] = stats['psnr'] / stats['n_done']
+        if self.do_evaluation:
+            keys = ('mse', 'lpips', 'msssim', 'identity')
+            sums = torch.tensor([sum(r.metrics[k] for r in results) for k in keys], dtype=torch.float64, device=dev)
+            for k, v in zip(keys, D.allreduce_stats_device(sums).tolist()):
+                stats[f'eval_{k}'] = v
+                if stats['n_done'] > 0:
+                    stats[f'mean_eval_{k}'] = v / stats['n_done']
         self.restore_generator()
         return results, stats

@@ -86,6 +86,22 @@ class bottleneck_IR_SE(torch.nn.Module):
         return H.to_cl(y + sc)
 
 
+def ir_se50_layers():
+    """(input_layer, body) of the IR-SE-50 trunk (helpers.py get_blocks(50) with bottleneck_IR_SE): the module trees and keys that both
+    Encoder4Editing and the ArcFace Backbone (models/encoders/model_irse.py, metrics.IDLoss) start with."""
+    input_layer = torch.nn.Sequential(torch.nn.Conv2d(3, 64, 3, 1, 1, bias=False), torch.nn.BatchNorm2d(64), torch.nn.PReLU(64))
+    units = []
+    for cin, depth, n in IRSE50:
+        units += [bottleneck_IR_SE(cin, depth, 2)] + [bottleneck_IR_SE(depth, depth, 1) for _ in range(n - 1)]
+    return input_layer, torch.nn.Sequential(*units)
+
+
+def run_input_layer(layer, x):
+    """input_layer (conv 3x3 + folded BatchNorm, PReLU) on a channels-last [N,4,H,W] image whose fourth channel is zero."""
+    x = _conv(x, layer[0], bn=layer[1])
+    return H.to_cl(F.prelu(x, layer[2].weight))
+
+
 class EqualLinear(torch.nn.Module):
     """models/e4e/stylegan2/model.py:129-158 without activation: y = x (W / sqrt(in) lr_mul)^T + b lr_mul."""
 
@@ -123,11 +139,7 @@ class Encoder4Editing(torch.nn.Module):
         super().__init__()
         if num_layers != 50 or mode != 'ir_se':
             raise NotImplementedError('the inversion pipeline uses Encoder4Editing(50, "ir_se") (models/e4e/psp.py:27)')
-        self.input_layer = torch.nn.Sequential(torch.nn.Conv2d(3, 64, 3, 1, 1, bias=False), torch.nn.BatchNorm2d(64), torch.nn.PReLU(64))
-        units = []
-        for cin, depth, n in IRSE50:
-            units += [bottleneck_IR_SE(cin, depth, 2)] + [bottleneck_IR_SE(depth, depth, 1) for _ in range(n - 1)]
-        self.body = torch.nn.Sequential(*units)
+        self.input_layer, self.body = ir_se50_layers()
         self.style_count, self.coarse_ind, self.middle_ind = 18, 3, 7
         self.styles = torch.nn.ModuleList(GradualStyleBlock(512, 512, 16 if i < 3 else (32 if i < 7 else 64)) for i in range(18))
         self.latlayer1 = torch.nn.Conv2d(256, 512, 1)
@@ -142,8 +154,7 @@ class Encoder4Editing(torch.nn.Module):
     def trunk(self, x):
         n, c, h, w = x.shape
         x = torch.cat([x.float(), x.new_zeros(n, 1, h, w, dtype=torch.float32)], 1).contiguous(memory_format=torch.channels_last)
-        x = _conv(x, self.input_layer[0], bn=self.input_layer[1])
-        x = H.to_cl(F.prelu(x, self.input_layer[2].weight))
+        x = run_input_layer(self.input_layer, x)
         feats = {}
         for i, unit in enumerate(self.body):
             x = unit(x)

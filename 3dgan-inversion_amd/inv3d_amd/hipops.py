@@ -1874,3 +1874,58 @@ def marching_cubes(vol: torch.Tensor, level: float, origin=None, spacing=None):
     p.verts, p.vert_capacity, p.faces, p.face_capacity = verts.data_ptr(), V, faces.data_ptr(), F
     L.check(lib.eg3d_mc_emit(C.byref(p), L.stream_ptr()), 'mc_emit')
     return verts, faces
+
+
+def _ssim_params(x, y, mode, weights, nonnegative, size_average, win_size, win_sigma, C1, C2):
+    N, Ch, Hh, Ww = x.shape
+    p = L.SsimParams(x=x.data_ptr(), y=y.data_ptr(), N=N, C=Ch, H=Hh, W=Ww, mode=mode, levels=len(weights), nonnegative=int(bool(nonnegative)),
+                     size_average=int(bool(size_average)), win_size=int(win_size), win_sigma=float(win_sigma), C1=float(C1), C2=float(C2))
+    p.weights[:len(weights)] = [float(w) for w in weights]
+    pyr, st, fwd, bwd = C.c_int64(0), C.c_int64(0), C.c_int64(0), C.c_int64(0)
+    L.check(L.lib().eg3d_ssim_query_workspace(C.byref(p), C.byref(pyr), C.byref(st), C.byref(fwd), C.byref(bwd)), 'ssim_query_workspace')
+    return p, pyr.value, st.value, fwd.value, bwd.value
+
+
+def ssim_forward(x, y, mode, weights, nonnegative=False, size_average=True, win_size=11, win_sigma=1.5, C1=1e-4, C2=9e-4):
+    """SSIM (mode 0, one level) / MS-SSIM (mode 1, len(weights) levels) of fp32 [N,C,H,W] images (eg3d_ssim_*; include/eg3d_hip.h):
+    (out [N] or [] with size_average, pooled pyramid, per-channel stats) -- the last two are what ssim_backward reads.  levels + 1 launches,
+    workspace from the caching allocator, no host synchronise."""
+    L.require_cuda(x, y)
+    x, y = x.contiguous(), y.contiguous()
+    p, npyr, nst, fwd, _ = _ssim_params(x, y, mode, weights, nonnegative, size_average, win_size, win_sigma, C1, C2)
+    dev = x.device
+    pyr = torch.empty(max(npyr, 1), dtype=torch.float32, device=dev)
+    stats = torch.empty(nst, dtype=torch.float64, device=dev)
+    out = torch.empty(1 if size_average else x.shape[0], dtype=torch.float32, device=dev)
+    ws = torch.empty(fwd, dtype=torch.uint8, device=dev)
+    p.pyramid, p.stats, p.out, p.workspace, p.workspace_bytes = pyr.data_ptr(), stats.data_ptr(), out.data_ptr(), ws.data_ptr(), fwd
+    L.check(L.lib().eg3d_ssim_forward(C.byref(p), L.stream_ptr()), 'ssim_forward')
+    return (out.view(()) if size_average else out), pyr, stats
+
+
+def ssim_backward(x, y, pyr, stats, grad_out, need_x, need_y, mode, weights, nonnegative=False, size_average=True, win_size=11, win_sigma=1.5,
+                  C1=1e-4, C2=9e-4):
+    """(grad_x, grad_y) of ssim_forward's output weighted by grad_out (either None when not needed): 2 launches per level, coarsest first."""
+    x, y = x.contiguous(), y.contiguous()
+    p, _, _, _, bwd = _ssim_params(x, y, mode, weights, nonnegative, size_average, win_size, win_sigma, C1, C2)
+    g = grad_out.detach().float().contiguous().reshape(-1)
+    gx = torch.empty_like(x) if need_x else None
+    gy = torch.empty_like(y) if need_y else None
+    ws = torch.empty(bwd, dtype=torch.uint8, device=x.device)
+    p.pyramid, p.stats, p.workspace, p.workspace_bytes = pyr.data_ptr(), stats.data_ptr(), ws.data_ptr(), bwd
+    p.grad_out, p.grad_x, p.grad_y = g.data_ptr(), (gx.data_ptr() if need_x else None), (gy.data_ptr() if need_y else None)
+    L.check(L.lib().eg3d_ssim_backward(C.byref(p), L.stream_ptr()), 'ssim_backward')
+    return gx, gy
+
+
+def face_pool(x: torch.Tensor, r0: int, r1: int, c0: int, c1: int, size: int) -> torch.Tensor:
+    """AdaptiveAvgPool2d(size)(x[:, :, r0:r1, c0:c1]) (bounds within the image) of fp32 [N,3,H,W], written as the channels-last [N,4,size,size]
+    image with a zero fourth channel that the IR-SE trunk takes (eg3d_face_pool): one launch."""
+    L.require_cuda(x)
+    if x.dim() != 4 or x.shape[1] != 3 or x.dtype != torch.float32:
+        raise L.Eg3dHipError(f'face_pool: fp32 [N,3,H,W], got {tuple(x.shape)} {x.dtype}')
+    x = x.contiguous()
+    N, _, Hh, Ww = x.shape
+    out = empty_cl(N, 4, size, size, x.device)
+    L.check(L.lib().eg3d_face_pool(x.data_ptr(), N, Hh, Ww, r0, r1, c0, c1, size, out.data_ptr(), L.stream_ptr()), 'face_pool')
+    return out

@@ -1004,6 +1004,58 @@ int eg3d_mc_query_workspace(const eg3d_mc_params* p, int64_t* count_bytes, int64
 int eg3d_mc_count(const eg3d_mc_params* p, void* stream);
 int eg3d_mc_emit(const eg3d_mc_params* p, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * SSIM / MS-SSIM (reconstruction metrics) -- pytorch_msssim 1.0's ssim / ms_ssim with win=None, as the reference's evaluation calls it
+ *   (training/coaches/single_id_coach.py:87-99; csrc/ssim.hip).  x, y: contiguous fp32 [N,C,H,W], any value range.
+ *   Gaussian window win[k] = exp(-(k - win_size/2)^2 / (2 sigma^2)) / sum, applied separably (H then W) per channel, valid (no padding).
+ *   Per level: cs = (2 s_xy + C2) / (s_xx + s_yy + C2), ssim = (2 mu_x mu_y + C1) / (mu_x^2 + mu_y^2 + C1) * cs, averaged per (image, channel).
+ *   ms_ssim (mode 1): `levels` levels, between them avg_pool2d(2, 2, padding = side % 2, count_include_pad) of both images; the value per
+ *   channel is prod_l relu(m_l)^weights[l], m_l = mean cs for l < levels-1, mean ssim for the last.  ssim (mode 0): levels = 1, the
+ *   mean ssim (relu'd when `nonnegative`).  out: [N] means over channels, or [1] the mean over everything with size_average.
+ *   No floating-point atomics: partial sums per workgroup, reduced in a fixed order (bit-identical run to run and between the two builds);
+ *   no host synchronise.  Every level's sides must be >= win_size (EG3D_ERR_INVALID otherwise).
+ *   Protocol:
+ *     eg3d_ssim_query_workspace  host only: floats of the pooled-image pyramid, doubles of the per-channel statistics, workspace bytes of
+ *                                the forward and of the backward
+ *     eg3d_ssim_forward          levels + 1 launches: writes pyramid (levels 1.., x then y), stats ([N*C][levels+1]: the means m_l, then the
+ *                                value) and out
+ *     eg3d_ssim_backward         2 launches per level, coarsest first: grad_x / grad_y (either may be NULL) = d(sum_n grad_out[n] out[n]) /
+ *                                d(x, y), from the forward's pyramid and stats (moments recomputed).  A term at or below 0 (relu) passes no
+ *                                gradient, so a clamped level, or a value that is 0, gives zeros, never NaN.
+ */
+#define EG3D_SSIM_MAX_LEVELS 8
+#define EG3D_SSIM_MAX_WIN 15
+typedef struct eg3d_ssim_params {
+    const float* x;
+    const float* y;
+    int32_t N, C, H, W;
+    int32_t mode;                      /* 0 = ssim, 1 = ms_ssim */
+    int32_t levels;                    /* 1 .. EG3D_SSIM_MAX_LEVELS (1 for ssim) */
+    int32_t nonnegative;               /* ssim: relu the per-channel value */
+    int32_t size_average;              /* out has 1 value instead of N */
+    int32_t win_size;                  /* odd, 1 .. EG3D_SSIM_MAX_WIN */
+    float win_sigma;
+    float C1, C2;                      /* (K1 data_range)^2, (K2 data_range)^2 */
+    float weights[EG3D_SSIM_MAX_LEVELS];
+    float* pyramid;                    /* eg3d_ssim_query_workspace's pyramid_floats (may be NULL when levels = 1) */
+    double* stats;                     /* N*C*(levels+1) */
+    float* out;                        /* N, or 1 with size_average */
+    void* workspace;
+    int64_t workspace_bytes;
+    const float* grad_out;             /* backward: N, or 1 with size_average */
+    float* grad_x;                     /* backward: [N,C,H,W] or NULL */
+    float* grad_y;
+} eg3d_ssim_params;
+int eg3d_ssim_query_workspace(const eg3d_ssim_params* p, int64_t* pyramid_floats, int64_t* stats_doubles, int64_t* forward_bytes,
+                              int64_t* backward_bytes);
+int eg3d_ssim_forward(const eg3d_ssim_params* p, void* stream);
+int eg3d_ssim_backward(const eg3d_ssim_params* p, void* stream);
+
+/* Face crop + pool of the identity metric (criteria/id_loss.py IDLoss.extract_feats): x[:, :, r0:r1, c0:c1] (bounds already clamped to the
+ * image, non-empty) -> AdaptiveAvgPool2d(S): output i averages rows [floor(i*Hc/S), ceil((i+1)*Hc/S)) of the crop.  x: contiguous fp32 [N,3,H,W];
+ * out: [N,S,S,4] (the channels-last [N,4,S,S] image of the IR-SE trunk, fourth channel 0).  One launch. */
+int eg3d_face_pool(const float* x, int N, int H, int W, int r0, int r1, int c0, int c1, int S, float* out, void* stream);
+
 /* Measurement aid (bench.py): a register-only v_mfma_f32_32x32x16_f16 loop on caller-supplied fp16 data -- what the matrix pipe sustains on
  * this chip at its current power / clock state, timed inside the benchmark run.  in: 4096 x 8 fp16 (64 KiB); out: blocks x 256 floats;
  * executes blocks x 4 waves x iters x 24 MFMAs of 32 x 32 x 16.  No reference counterpart. */

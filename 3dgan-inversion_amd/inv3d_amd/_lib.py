@@ -238,6 +238,15 @@ class SsimParams(C.Structure):
                 ('grad_out', C.c_void_p), ('grad_x', C.c_void_p), ('grad_y', C.c_void_p)]
 
 
+class BatchNormParams(C.Structure):
+    """eg3d_batchnorm_params: training-mode BatchNorm (eg3d_batchnorm_query_workspace / eg3d_batchnorm_forward / eg3d_batchnorm_backward)."""
+    _fields_ = [('x', C.c_void_p), ('gamma', C.c_void_p), ('beta', C.c_void_p), ('residual', C.c_void_p), ('y', C.c_void_p), ('M', C.c_int64),
+                ('C', C.c_int32), ('act', C.c_int32), ('eps', C.c_float), ('momentum', C.c_float), ('running_mean', C.c_void_p),
+                ('running_var', C.c_void_p), ('num_batches_tracked', C.c_void_p), ('save_mean', C.c_void_p), ('save_invstd', C.c_void_p),
+                ('stats', C.c_void_p), ('workspace', C.c_void_p), ('workspace_bytes', C.c_int64), ('dy', C.c_void_p), ('dx', C.c_void_p),
+                ('dresidual', C.c_void_p), ('dgamma', C.c_void_p), ('dbeta', C.c_void_p)]
+
+
 _SIGS = {
     'eg3d_abi_version': (C.c_int, []),
     'eg3d_status_string': (C.c_char_p, [C.c_int]),
@@ -366,6 +375,9 @@ _SIGS = {
                                             C.POINTER(C.c_int64)]),
     'eg3d_ssim_forward': (C.c_int, [C.POINTER(SsimParams), C.c_void_p]),
     'eg3d_ssim_backward': (C.c_int, [C.POINTER(SsimParams), C.c_void_p]),
+    'eg3d_batchnorm_query_workspace': (C.c_int, [C.c_int64, C.c_int32, C.POINTER(C.c_int64)]),
+    'eg3d_batchnorm_forward': (C.c_int, [C.POINTER(BatchNormParams), C.c_void_p]),
+    'eg3d_batchnorm_backward': (C.c_int, [C.POINTER(BatchNormParams), C.c_void_p]),
     'eg3d_face_pool': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     'eg3d_sample_decode': (C.c_int, [C.POINTER(RenderParams), C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
 }

@@ -1929,3 +1929,88 @@ def face_pool(x: torch.Tensor, r0: int, r1: int, c0: int, c1: int, size: int) ->
     out = empty_cl(N, 4, size, size, x.device)
     L.check(L.lib().eg3d_face_pool(x.data_ptr(), N, Hh, Ww, r0, r1, c0, c1, size, out.data_ptr(), L.stream_ptr()), 'face_pool')
     return out
+
+
+# ------------------------------------------------------------------------------------------------- BatchNorm on batch statistics
+def _bn_params(x, gamma, act):
+    N, Cc, Hh, Ww = x.shape
+    M = N * Hh * Ww
+    nbytes = C.c_int64(0)
+    L.check(L.lib().eg3d_batchnorm_query_workspace(M, Cc, C.byref(nbytes)), 'batchnorm_query_workspace')
+    ws = torch.empty(nbytes.value, dtype=torch.uint8, device=x.device)
+    p = L.BatchNormParams(x=x.data_ptr(), gamma=gamma.data_ptr(), M=M, C=Cc, act=L.ACT_IDS[act], workspace=ws.data_ptr(), workspace_bytes=nbytes.value)
+    return p, ws
+
+
+class _BatchNormTrainFn(torch.autograd.Function):
+    """eg3d_batchnorm_forward / eg3d_batchnorm_backward (csrc/batchnorm.hip): three launches each, running statistics updated on the device."""
+
+    @staticmethod
+    def forward(ctx, x, gamma, beta, residual, running_mean, running_var, num_batches_tracked, momentum, eps, act):
+        L.require_cuda(x, gamma, beta, residual, running_mean, running_var, num_batches_tracked)
+        if not is_cl(x) or (residual is not None and not (is_cl(residual) and residual.shape == x.shape)):
+            raise L.Eg3dHipError(f'batch_norm_train: fp32 channels-last [N,C,H,W] operands, got {tuple(x.shape)} {x.dtype} strides {x.stride()}')
+        for t in (running_mean, running_var):
+            if t is not None and not (t.dtype == torch.float32 and t.is_contiguous()):
+                raise L.Eg3dHipError('batch_norm_train: running statistics must be contiguous fp32')
+        if num_batches_tracked is not None and num_batches_tracked.dtype != torch.int64:
+            raise L.Eg3dHipError('batch_norm_train: num_batches_tracked must be int64')
+        g, b = gamma.detach().contiguous().float(), beta.detach().contiguous().float()
+        N, Cc, Hh, Ww = x.shape
+        y = empty_cl(N, Cc, Hh, Ww, x.device)
+        stats = torch.empty(2 * Cc, dtype=torch.float64, device=x.device)
+        save = torch.empty((2, Cc), dtype=torch.float32, device=x.device)
+        p, ws = _bn_params(x, g, act)
+        p.beta, p.residual, p.y = b.data_ptr(), L.ptr(residual), y.data_ptr()
+        p.eps, p.momentum = float(eps), float(momentum)
+        p.running_mean, p.running_var, p.num_batches_tracked = L.ptr(running_mean), L.ptr(running_var), L.ptr(num_batches_tracked)
+        p.save_mean, p.save_invstd, p.stats = save[0].data_ptr(), save[1].data_ptr(), stats.data_ptr()
+        L.check(L.lib().eg3d_batchnorm_forward(C.byref(p), L.stream_ptr()), 'batchnorm_forward')
+        ctx.save_for_backward(x, g, y if act == 'relu' else None, stats)
+        ctx.act, ctx.has_res = act, residual is not None
+        ctx.mark_non_differentiable(save)
+        return y, save
+
+    @staticmethod
+    def backward(ctx, dy, _dsave):
+        x, g, y, stats = ctx.saved_tensors
+        need_x, need_g, need_b, need_r = ctx.needs_input_grad[:4]
+        dy = to_cl(dy.float())
+        N, Cc, Hh, Ww = x.shape
+        dx = empty_cl(N, Cc, Hh, Ww, x.device) if need_x else None
+        dres = None
+        if need_r and ctx.has_res:
+            dres = empty_cl(N, Cc, Hh, Ww, x.device) if ctx.act == 'relu' else dy          # linear: dy' is dy itself
+        dgb = torch.empty((2, Cc), dtype=torch.float32, device=x.device)
+        p, ws = _bn_params(x, g, ctx.act)
+        p.y, p.stats, p.dy = L.ptr(y), stats.data_ptr(), dy.data_ptr()
+        p.dx, p.dresidual = L.ptr(dx), (dres.data_ptr() if (dres is not None and dres is not dy) else None)
+        p.dgamma, p.dbeta = dgb[0].data_ptr(), dgb[1].data_ptr()
+        L.check(L.lib().eg3d_batchnorm_backward(C.byref(p), L.stream_ptr()), 'batchnorm_backward')
+        return dx, (dgb[0] if need_g else None), (dgb[1] if need_b else None), dres, None, None, None, None, None, None
+
+
+def batch_norm_train(x, gamma, beta, running_mean=None, running_var=None, num_batches_tracked=None, momentum=0.1, eps=1e-5, residual=None, act='linear',
+                     return_stats=False):
+    """act(batch_norm(x; batch statistics) * gamma + beta [+ residual]) -- torch.nn.BatchNorm2d in training mode, with the residual add and the
+    ReLU of a ResNet block folded into the same pass.  The running buffers (and the batch counter) are updated in place as PyTorch does
+    (through raw pointers: their tensor version counters do not move, so a cache keyed on them must be dropped by the caller):
+    momentum-weighted, the unbiased variance into running_var.  Gradients flow into x, gamma, beta and residual.  GPU: fp32 channels-last
+    tensors on the HIP kernels (csrc/batchnorm.hip; capturable, no host read); a missing kernel is an error.  CPU tensors: the same function
+    composed from torch.nn.functional.batch_norm(training=True) + add + relu, so that callers can be exercised without a GPU.
+    return_stats: also return the saved [2,C] fp32 (batch mean, 1 / sqrt(var + eps)) (GPU only)."""
+    if act not in ('linear', 'relu'):
+        raise ValueError(f"batch_norm_train: act must be 'linear' or 'relu', got {act!r}")
+    if momentum is None:
+        raise ValueError('batch_norm_train: a cumulative moving average (momentum=None) is not supported')
+    if not x.is_cuda:
+        y = torch.nn.functional.batch_norm(x, running_mean, running_var, gamma, beta, True, float(momentum), float(eps))
+        if num_batches_tracked is not None:
+            num_batches_tracked.add_(1)
+        if residual is not None:
+            y = y + residual
+        y = torch.relu(y) if act == 'relu' else y
+        assert not return_stats, 'the saved statistics are those of the HIP kernel'
+        return y
+    y, save = _BatchNormTrainFn.apply(x, gamma, beta, residual, running_mean, running_var, num_batches_tracked, float(momentum), float(eps), act)
+    return (y, save) if return_stats else y

@@ -1056,6 +1056,50 @@ int eg3d_ssim_backward(const eg3d_ssim_params* p, void* stream);
  * out: [N,S,S,4] (the channels-last [N,4,S,S] image of the IR-SE trunk, fourth channel 0).  One launch. */
 int eg3d_face_pool(const float* x, int N, int H, int W, int r0, int r1, int c0, int c1, int S, float* out, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * BatchNorm on batch statistics (training mode) -- torch.nn.BatchNorm2d.train() on channels-last fp32 [M = N*H*W, C] (csrc/batchnorm.hip; the
+ *   pose estimator's training path).  C a multiple of 4, M >= 2; x, y, residual, dy, dx, dresidual 16-byte aligned.
+ *   forward:  mean[c], var[c] (biased) over the M rows; y = act(gamma (x - mean) / sqrt(var + eps) + beta [+ residual]), act linear | relu;
+ *             running_mean = (1 - momentum) running_mean + momentum mean, running_var likewise with the UNBIASED variance var M / (M - 1),
+ *             num_batches_tracked += 1 (each of the three may be NULL); stats [2C] doubles = mean, 1 / sqrt(var + eps), which the backward
+ *             reads; save_mean / save_invstd (may be NULL) the same as fp32.  Three launches (chunk sums, per-channel finish, apply).
+ *   backward: dy' = dy where the saved output y > 0 (relu; y unused and may be NULL when linear); dbeta = sum dy', dgamma = sum dy' xhat,
+ *             dx = gamma invstd (dy' - dbeta / M - xhat dgamma / M), dresidual = dy' (dx, dresidual, dgamma, dbeta may each be NULL).
+ *             Three launches (chunk sums, finish, apply); x and dy are read twice.
+ *   The moments are double-precision sums of differences from a per-channel shift, per workgroup, combined in a fixed order: no atomics,
+ *   bit-identical between runs and between the two builds; no host synchronise.
+ *   workspace: eg3d_batchnorm_query_workspace bytes, 16-byte aligned, scratch (need not survive from forward to backward; stats must).
+ *   Errors: EG3D_ERR_INVALID (null / misaligned pointer, C % 4 != 0, M < 2, short workspace, momentum outside [0,1]), EG3D_ERR_UNSUPPORTED
+ *   (another activation), before anything is launched.
+ */
+typedef struct eg3d_batchnorm_params {
+    const float* x;                    /* [M,C] */
+    const float* gamma;                /* [C] */
+    const float* beta;                 /* [C] (forward) */
+    const float* residual;             /* [M,C] or NULL (forward) */
+    float* y;                          /* [M,C]: forward output; backward: the saved output (relu) */
+    int64_t M;
+    int32_t C;
+    int32_t act;                       /* EG3D_ACT_LINEAR | EG3D_ACT_RELU */
+    float eps, momentum;
+    float* running_mean;               /* [C] or NULL, updated in place (forward) */
+    float* running_var;
+    int64_t* num_batches_tracked;      /* one counter or NULL */
+    float* save_mean;                  /* [C] or NULL (forward) */
+    float* save_invstd;
+    double* stats;                     /* [2C]: written by forward, read by backward */
+    void* workspace;
+    int64_t workspace_bytes;
+    const float* dy;                   /* backward: [M,C] */
+    float* dx;                         /* [M,C] or NULL */
+    float* dresidual;                  /* [M,C] or NULL */
+    float* dgamma;                     /* [C] or NULL */
+    float* dbeta;
+} eg3d_batchnorm_params;
+int eg3d_batchnorm_query_workspace(int64_t M, int32_t C, int64_t* workspace_bytes);
+int eg3d_batchnorm_forward(const eg3d_batchnorm_params* p, void* stream);
+int eg3d_batchnorm_backward(const eg3d_batchnorm_params* p, void* stream);
+
 /* Measurement aid (bench.py): a register-only v_mfma_f32_32x32x16_f16 loop on caller-supplied fp16 data -- what the matrix pipe sustains on
  * this chip at its current power / clock state, timed inside the benchmark run.  in: 4096 x 8 fp16 (64 KiB); out: blocks x 256 floats;
  * executes blocks x 4 waves x iters x 24 MFMAs of 32 x 32 x 16.  No reference counterpart. */

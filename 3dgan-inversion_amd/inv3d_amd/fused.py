@@ -18,6 +18,7 @@ import os
 import torch
 
 from . import _lib as L
+from . import conv_plan as P
 from . import hipops as H
 
 _F44 = {}
@@ -185,20 +186,6 @@ GRAM_FUSED = os.environ.get('EG3D_GRAM_FUSED', '1') != '0'        # decoder-weig
 RENDER_PIPELINE_NOGRAD = os.environ.get('EG3D_RENDER_PIPELINE_NOGRAD', '1') != '0'   # ... also for no-grad rendering (scratch rows)
 RENDER_FEAT_ROWS = os.environ.get('EG3D_RENDER_FEAT_ROWS', '1') != '0'   # gather pass + feature rows (eg3d_render_params.feat_rows) in the pipelined renderer
 RENDER_PIPELINE = os.environ.get('EG3D_RENDER_PIPELINE', '1') != '0'     # forward renderer as positions -> MFMA decode -> importance -> decode -> composite
-KS_TARGET = 256       # blocks a split launch aims for (one per CU; 512 measured 0.7 % slower per step)
-
-
-def _auto_ksplit(classes, N, Nc, Ck):
-    """Split-K factor of an implicit GEMM whose output grid is too small to keep 256 CUs busy (the 4^2..64^2 layers): with few
-    128x128 tiles each workgroup walks a long K = taps x channels chain on its own and the launch is latency-bound (64^2 x 512
-    channels: 91 TF unsplit, 148 TF split 4 ways).  Slices accumulate with fp32 atomics into a zeroed buffer."""
-    blocks = sum((N * c.Ha * c.Wa + 127) // 128 for c in classes) * ((Nc + 127) // 128)
-    if blocks >= 200:           # measured: splitting layers with 256 tiles (128^2 x 256 ch) costs more in zero-fill + finish passes than it gains
-        return 1
-    steps = ((Ck + 15) // 16) * min(c.ntaps for c in classes)
-    # 64^2 x 512 (128 tiles, one tap class): 4 slices beat 2 (198 vs 164 TFLOP/s stand-alone, +0.2 % per step); smaller grids keep the target
-    target = KS_TARGET * 2 if (len(classes) == 1 and blocks >= 64) else KS_TARGET
-    return max(1, min(-(-target // blocks), steps // 8))
 
 
 # ---- cross-layer backward fusion (EG3D_EPI_BWD_ACT) ------------------------------------------------------------------------------------
@@ -322,35 +309,19 @@ class ModConvLayerFn(torch.autograd.Function):
         clampv = -1.0 if clamp is None else float(clamp)
         out = H.empty_cl(N, Co, Ho, Wo, x.device)
         b = bias.contiguous().float() if bias is not None else None
-        aflops = 2.0 * N * Hi * Wi * (1 if up == 2 else 1) * kh * kw * Ci * Co     # MACs of the (transposed) conv
+        aflops = 2.0 * N * Hi * Wi * kh * kw * Ci * Co     # MACs of the (transposed) conv
         pending = None
         prec = precision or H.modconv_precision()
-        ig_prec = 'f16x3' if prec == 'f16x1' else prec      # the loader-split kernel has no single-product form: it keeps the three products
+        nprod, ig_prec = P.products(prec), P.loader_precision(prec)
         # pre-split weight image for the loader-split kernel; frozen weights only (a trained weight would need the pass every step: +34 launches for ~1 %)
         wfp = cache.get_pieces(weight)[0] if (ig_prec == 'f16x3' and USE_PIECES and not weight.requires_grad) else None
         amax_out = H.zeros((1,), x.device)            # max|out|, reported by whichever kernel writes `out`: the next layer's operand range
         cls, Hz, Wz = (H.classes_corr(Ho, Wo, kh, kw, kh // 2), Ho, Wo) if up == 1 else H.classes_convT(Hi, Wi, kh, kw, up)
-        ks = _auto_ksplit(cls, N, Co, Ci)
-        # (transposed-conv classes run on it too, but measured slower than the loader-split kernel: three launches of 4 / 2 / 1-tap
-        #  classes on ragged 257-wide grids -- 196 vs 174 us on 256^2 x 256 -> 513^2 x 128, 116 vs 67 us on 128^2 x 256; opt-in)
-        # (a grid the pre-split kernel fills with its 2-row patches -- 64^2 x 512 -- goes there un-split rather than to a split-K launch)
-        v2 = H.USE_V2 and prec in ('f16x3', 'f16x1') and (up == 1 or (H.V2_CONVT and prec == 'f16x3')) and H.conv_v2_supported(Ci, Co, cls, N)
-        v2 = v2 and (ks == 1 or (up == 1 and H.conv_v2_rows(Ci, Co, cls, N) == 2))
-        if v2:
-            ks = 1
-        nprod = 1 if prec == 'f16x1' else 3
-        # 3x3 layers whose grids cannot fill the chip with 256 x 128 tiles (64^2 x 512, 32^2 x 512 at one image): the wave-split kernel
-        # (csrc/conv_v3.hip) -- 128 / 64-cell x 64-channel tiles, the contraction split over the waves of a workgroup, fused epilogue, no zero
-        # fill / atomics / finishing pass
-        v3p = H.conv_v3_plan(Ci, Co, cls, N) if (up == 1 and prec in ('f16x3', 'f16x1')) else None
-        if v3p:
-            v2, ks = False, 1
-        # ... or (opt-in) the pre-split kernel with the contraction split over workgroups (atomic partial tiles) + the finishing epilogue pass
-        ks2 = H.conv_v2_ksplit(Ci, Co, cls, N) if (up == 1 and not v2 and not v3p and prec in ('f16x3', 'f16x1')) else 0
-        # up-sampling layers: the four output parities of the transposed conv from one workgroup per input patch (csrc/conv_v2_up.hip)
-        ksu = H.conv_up2_plan(Ci, Co, Hi, Wi, N) if (up == 2 and not v2 and kh == 3 and kw == 3 and prec in ('f16x3', 'f16x1')) else None
+        assert kh == kw
+        plan = P.plan_forward(N, Ci, Co, Hi, Wi, kh, up, prec, not weight.requires_grad)        # which kernel, and why: conv_plan.py
         epi_kw = dict(noise=nz, noise_nstride=nstride or 0, noise_strength=noise_strength, bias=b, act='lrelu', alpha=0.2, gain=act_gain, clamp=clampv)
-        if v2 or v3p or ks2 or ksu:   # pre-split operands: modulation, range normalisation and the fp16 split happen once, not per tile and tap
+        aimg = None
+        if plan.presplit:             # pre-split operands: modulation, range normalisation and the fp16 split happen once, not per tile and tap
             pre_img = getattr(x, '_eg3d_split', None)           # (SplitImage, styles ptr, styles version) left by the producing layer's epilogue
             if pre_img is not None and pre_img[1] == styles.data_ptr() and pre_img[2] == styles._version and pre_img[0].shape == tuple(x.shape):
                 aimg = pre_img[0]
@@ -358,78 +329,64 @@ class ModConvLayerFn(torch.autograd.Function):
                 aimg = H.split_activation(x, H.amax_of(x), in_scale=styles)
             wimg = cache.get_split(weight)[0]
         rgb_y = None
-        if up == 1:
-            if v2:
-                rkw = {}
-                if rgb_head is not None and H.RGB_HEAD and Co == 128 and len(cls) == 1 and H.conv_v2_rows(Ci, Co, cls, N) == 8:
-                    tw, ts, tb, tclamp, tcache = rgb_head
-                    if tw.shape[0] <= 4 and tw.shape[1] == Co and tuple(ts.shape) == (N, Co):
-                        tw4, _, tb4 = tcache.get_padded(tw, 4, tb) if tw.shape[0] != 4 else (tcache.get(tw)[0], None, tb.contiguous().float() if tb is not None else None)
-                        y4 = H.empty_cl(N, 4, Ho, Wo, x.device)
-                        ts_c = ts.contiguous().float()
-                        rkw = dict(rgb_head=(tw4, ts_c, tb4, y4, -1.0 if tclamp is None else float(tclamp), 3 if tw.shape[0] == 3 else 4))
-                        rgb_y = (y4, tw.data_ptr(), tw._version, ts.data_ptr(), ts._version, None if tb is None else (tb.data_ptr(), tb._version),
-                                 -1.0 if tclamp is None else float(tclamp))
-                ran = []
-                H.conv_v2(aimg, wimg, out, cls, epi=L.EPI_FWD, out_scale=d, out_amax=amax_out, algo_flops=aflops, products=nprod, rgb_head_ran=ran, **epi_kw, **rkw)
-                if rgb_y is not None and ran != [True]:
-                    rgb_y = None                # the library refused the head's operands: ToRGBFn launches the 1x1 layer
-            elif v3p:
-                H.conv_v3(aimg, wimg, out, cls, plan=v3p, epi=L.EPI_FWD, out_scale=d, out_amax=amax_out, algo_flops=aflops, products=nprod, **epi_kw)
-            elif ks2:
-                z = H.zeros_cl(N, Co, Ho, Wo, x.device)
-                H.conv_v2(aimg, wimg, z, cls, epi=L.EPI_ATOMIC, ksplit=ks2, algo_flops=aflops, products=nprod)
-                if defer_epilogue and H.DEFER_EPILOGUE:
-                    pending = H.PendingEpilogue(z, out, d, amax_out, **epi_kw)
-                else:
-                    H.epilogue_fwd(z, out, d=d, out_amax=amax_out, **epi_kw)
-            elif ks == 1:
-                H.conv_igemm(x, wf, Ci, Co, out, cls, in_scale=styles, epi=L.EPI_FWD, out_scale=d, algo_flops=aflops, precision=ig_prec, out_amax=amax_out, w_pieces=wfp,
-                             **epi_kw)
+        z = None                      # raw sums of a launch without the layer's epilogue (plan.finish)
+        if plan.form == 'v2':
+            rkw = {}
+            if rgb_head is not None and plan.rgb_head:
+                tw, ts, tb, tclamp, tcache = rgb_head
+                if tw.shape[0] <= 4 and tw.shape[1] == Co and tuple(ts.shape) == (N, Co):
+                    tw4, _, tb4 = tcache.get_padded(tw, 4, tb) if tw.shape[0] != 4 else (tcache.get(tw)[0], None, tb.contiguous().float() if tb is not None else None)
+                    y4 = H.empty_cl(N, 4, Ho, Wo, x.device)
+                    ts_c = ts.contiguous().float()
+                    rkw = dict(rgb_head=(tw4, ts_c, tb4, y4, -1.0 if tclamp is None else float(tclamp), 3 if tw.shape[0] == 3 else 4))
+                    rgb_y = (y4, tw.data_ptr(), tw._version, ts.data_ptr(), ts._version, None if tb is None else (tb.data_ptr(), tb._version),
+                             -1.0 if tclamp is None else float(tclamp))
+            ran = []
+            H.conv_v2(aimg, wimg, out, cls, epi=L.EPI_FWD, out_scale=d, out_amax=amax_out, algo_flops=aflops, products=nprod, patch_rows=plan.rows,
+                      rgb_head_ran=ran, **epi_kw, **rkw)
+            if rgb_y is not None and ran != [True]:
+                rgb_y = None                # the library refused the head's operands: ToRGBFn launches the 1x1 layer
+        elif plan.form == 'v3':
+            H.conv_v3(aimg, wimg, out, cls, plan=plan.v3, epi=L.EPI_FWD, out_scale=d, out_amax=amax_out, algo_flops=aflops, products=nprod, **epi_kw)
+        elif plan.form == 'up2':
+            z = H.zeros_cl(N, Co, Hz, Wz, x.device) if plan.ksplit > 1 else H.empty_cl(N, Co, Hz, Wz, x.device)
+            up_kw = dict(epi=L.EPI_ATOMIC if plan.ksplit > 1 else L.EPI_STORE, ksplit=plan.ksplit, products=nprod, algo_flops=aflops, patch_rows=plan.rows)
+            if plan.ragged:      # the full (Hi + 1) x (Wi + 1) cell grid still fits one round of workgroups
+                H.conv_up2(aimg, wimg, z, **up_kw)
             else:
-                z = H.zeros_cl(N, Co, Ho, Wo, x.device)
-                if prec in ('f16x3', 'f16x1') and (H.CONV_WS_TRAINABLE or not weight.requires_grad) and H.conv_ws_ok(Ci, Co, cls, N, Hi, Wi):
-                    # 4^2 .. 16^2: one workgroup per (channel tile, 16-channel chunk), every weight byte fetched once, operand split inside (csrc/conv_ws.hip)
-                    H.conv_ws(x, cache.get_split(weight)[0], z, cls, in_scale=styles, x_amax=H.amax_of(x), products=nprod, algo_flops=aflops)
-                else:
-                    H.conv_atomic(x, wf, Ci, Co, z, cls, in_scale=styles, ksplit=ks, algo_flops=aflops, precision=ig_prec, w_pieces=wfp)
-                if defer_epilogue and H.DEFER_EPILOGUE:
-                    pending = H.PendingEpilogue(z, out, d, amax_out, **epi_kw)
-                else:
-                    H.epilogue_fwd(z, out, d=d, out_amax=amax_out, **epi_kw)
-        else:
-            if ksu:
-                ksplit, ragged, urows = ksu
-                z = H.zeros_cl(N, Co, Hz, Wz, x.device) if ksplit > 1 else H.empty_cl(N, Co, Hz, Wz, x.device)
-                if ragged:      # the full (Hi + 1) x (Wi + 1) cell grid still fits one round of workgroups
-                    H.conv_up2(aimg, wimg, z, epi=L.EPI_ATOMIC if ksplit > 1 else L.EPI_STORE, ksplit=ksplit, products=nprod, algo_flops=aflops, patch_rows=urows)
-                else:
-                    # main grid (Hi x Wi cells, perfectly tiled) on the fused-parity kernel; the last output row / column (1-D problems, ~20 us
-                    # of latency for 0.1 GFLOP) as four small tap classes of the loader-split kernel.  (Forking that launch onto a second
-                    # stream hides it at N = 1 -- but two processes sharing one device then replayed the two-branch graph at 1.2 s per step:
-                    # not worth the risk on an 8-rank node.)
-                    H.conv_up2(aimg, wimg, z, Hc=Hi, Wc=Wi, epi=L.EPI_ATOMIC if ksplit > 1 else L.EPI_STORE, ksplit=ksplit, products=nprod, algo_flops=aflops, patch_rows=urows)
-                    H.conv_igemm(x, wf, Ci, Co, z, H.up2_border_classes(Hi, Wi), out_stride=up, in_scale=styles, epi=L.EPI_STORE, algo_flops=0.0,
-                                 precision=ig_prec, w_pieces=wfp)
-            elif v2:
-                z = H.empty_cl(N, Co, Hz, Wz, x.device)
-                H.conv_v2(aimg, wimg, z, cls, out_stride=up, epi=L.EPI_STORE, algo_flops=aflops)
-            elif ks == 1:
-                z = H.empty_cl(N, Co, Hz, Wz, x.device)
-                H.conv_igemm(x, wf, Ci, Co, z, cls, out_stride=up, in_scale=styles, epi=L.EPI_STORE, algo_flops=aflops, precision=ig_prec, w_pieces=wfp)
+                # main grid (Hi x Wi cells, perfectly tiled) on the fused-parity kernel; the last output row / column (1-D problems, ~20 us
+                # of latency for 0.1 GFLOP) as four small tap classes of the loader-split kernel.  (Forking that launch onto a second
+                # stream hides it at N = 1 -- but two processes sharing one device then replayed the two-branch graph at 1.2 s per step:
+                # not worth the risk on an 8-rank node.)
+                H.conv_up2(aimg, wimg, z, Hc=Hi, Wc=Wi, **up_kw)
+                H.conv_igemm(x, wf, Ci, Co, z, H.up2_border_classes(Hi, Wi), out_stride=up, in_scale=styles, epi=L.EPI_STORE, algo_flops=0.0,
+                             precision=ig_prec, w_pieces=wfp)
+        elif plan.form == 'igemm':
+            H.conv_igemm(x, wf, Ci, Co, out, cls, in_scale=styles, epi=L.EPI_FWD, out_scale=d, algo_flops=aflops, precision=ig_prec, out_amax=amax_out, w_pieces=wfp,
+                         **epi_kw)
+        elif plan.form == 'igemm_up':
+            z = H.empty_cl(N, Co, Hz, Wz, x.device)
+            H.conv_igemm(x, wf, Ci, Co, z, cls, out_stride=up, in_scale=styles, epi=L.EPI_STORE, algo_flops=aflops, precision=ig_prec, w_pieces=wfp)
+        else:                         # split-K: partial sums accumulate into a zeroed buffer
+            z = H.zeros_cl(N, Co, Hz, Wz, x.device)
+            if plan.form == 'ws':
+                H.conv_ws(x, cache.get_split(weight)[0], z, cls, in_scale=styles, x_amax=H.amax_of(x), products=nprod, algo_flops=aflops)
+            elif plan.form == 'ws_up':
+                H.conv_ws_up(x, cache.get_split(weight)[0], z, in_scale=styles, x_amax=H.amax_of(x), products=nprod, algo_flops=aflops)
             else:
-                z = H.zeros_cl(N, Co, Hz, Wz, x.device)
-                if up == 2 and kh == 3 and kw == 3 and prec in ('f16x3', 'f16x1') and (H.CONV_WS_TRAINABLE or not weight.requires_grad) and H.conv_ws_up_ok(Ci, Co, N, Hi, Wi):
-                    # 4^2 / 8^2 input cells: the weight-streaming kernel's transposed form (four parity accumulator sets per wave, csrc/conv_ws.hip)
-                    H.conv_ws_up(x, cache.get_split(weight)[0], z, in_scale=styles, x_amax=H.amax_of(x), products=nprod, algo_flops=aflops)
-                else:
-                    H.conv_atomic(x, wf, Ci, Co, z, cls, out_stride=up, in_scale=styles, ksplit=ks, algo_flops=aflops, precision=ig_prec, w_pieces=wfp)
+                H.conv_atomic(x, wf, Ci, Co, z, cls, out_stride=up, in_scale=styles, ksplit=plan.ksplit, algo_flops=aflops, precision=ig_prec, w_pieces=wfp)
+        if up == 1 and plan.finish:
+            if defer_epilogue and H.DEFER_EPILOGUE:
+                pending = H.PendingEpilogue(z, out, d, amax_out, **epi_kw)
+            else:
+                H.epilogue_fwd(z, out, d=d, out_amax=amax_out, **epi_kw)
+        elif up != 1:
             simg = None
             if H.UPCONV_EPI and Co % 64 == 0 and up == 2:
                 # consumer = a 3x3 layer on the pre-split kernel (same channel count, output resolution): its operand image comes out of this
                 # epilogue when the range is known beforehand (conv_clamp: the super-resolution head)
-                want_split = (H.UPCONV_EPI_SPLIT and next_styles is not None and clampv >= 0 and prec in ('f16x3', 'f16x1') and H.USE_V2
-                              and tuple(next_styles.shape) == (N, Co) and H.conv_v2_supported(Co, Co, H.classes_corr(Ho, Wo, 3, 3, 1), N))
+                want_split = (H.UPCONV_EPI_SPLIT and next_styles is not None and clampv >= 0 and tuple(next_styles.shape) == (N, Co)
+                              and P.consumer_reads_split(N, Co, Ho, Wo, prec))
                 ns = next_styles.contiguous().float() if want_split else None
                 simg = H.upconv_epilogue_fwd(z, out, pad0=1, fir_gain=float(up * up), d=d, out_amax=amax_out, split_in_scale=ns, **epi_kw)
                 if simg is not None:
@@ -450,14 +407,13 @@ class ModConvLayerFn(torch.autograd.Function):
             rec.need = (bool(ng[5]), bool(ng[2] or (ng[1] and want_wgrad)), bool(ng[3]), bool(ng[4]))
             # this layer's backward will feed dz to the pre-split data-gradient kernel and to nothing else (frozen weights): a consumer that
             # runs the activation backward may then hand dz over as that kernel's operand image instead of an fp32 tensor (SPLIT_DZ)
-            rec.split_ok = False
-            if SPLIT_DZ and up == 1 and not (ng[1] and want_wgrad) and prec in ('f16x3', 'f16x1') and H.USE_V2 and Co % 8 == 0 and (ng[0] or ng[2]):
-                cls_adj0 = H.classes_corr_adjoint(Hi, Wi, kh, kw, kh // 2)
-                rec.split_ok = bool((_auto_ksplit(cls_adj0, N, Ci, Co) == 1 or H.conv_v2_rows(Co, Ci, cls_adj0, N) == 2) and H.conv_v2_supported(Co, Ci, cls_adj0, N))
+            rec.split_ok = bool(SPLIT_DZ and not (ng[1] and want_wgrad) and Co % 8 == 0 and (ng[0] or ng[2])
+                                and P.plan_dgrad(N, Ci, Co, Hi, Wi, kh, up, prec, not weight.requires_grad).form == 'v2')
         if rec is not None:             # (a no-grad forward of the same layer -- the canonical view of the warping loss -- leaves a pending record alone)
             _set_producer(cache, rec)
         # pivotal tuning: the weight gradient reads the forward's operand image again (csrc/conv_wgrad_v2.hip) instead of the fp32 activation
-        ctx.aimg = aimg if ((((v2 or v3p) and up == 1) or (ksu and up == 2)) and want_wgrad and ctx.needs_input_grad[1] and H.WGRAD_V2 and Ci % 64 == 0 and Co % 64 == 0) else None
+        ctx.aimg = aimg if (want_wgrad and ctx.needs_input_grad[1] and P.plan_wgrad(N, Ci, Co, Hi, Wi, kh, up, prec, fwd=plan).keep_ximg) else None
+        ctx.plan = plan
         ctx.rec = rec                   # THIS forward's record: the backward below trusts only it (two live graphs of one layer cannot mix)
         ctx.save_for_backward(x, weight, styles, d, out, nz, noise_strength, b)
         ctx.cfg = (up, act_gain, clampv, nstride, cache, want_wgrad, noise is not None and noise.dim() == 4, d_in is not None)
@@ -495,30 +451,30 @@ class ModConvLayerFn(torch.autograd.Function):
         if rec is not None:
             rec.fused = None    # the accumulators become parameter gradients: AccumulateGrad adopts a gradient nobody else references, copies it otherwise
         dz = pre[0] if pre is not None else H.empty_cl(N, Co, Ho, Wo, dev)
-        ks_adj = rep = None
-        if need_x or need_s:
-            cls_probe = H.classes_corr_adjoint(Hi, Wi, kh, kw, kh // 2) if up == 1 else H.classes_convT_adjoint(Hi, Wi, kh, kw, up)
-            ks_adj = _auto_ksplit(cls_probe, N, Ci, Co)
-            # thousands of tiles reduce into the same N*Ci style-gradient addresses: spread them over replicas, sum afterwards
-            rep = 1          # replicas of the style-gradient accumulator (eg3d_conv_params::ds_replicas) measured no gain on MI355X
+        need_dx = need_x or need_s
         # all small atomically-accumulated outputs of this backward from one zero fill
         prec = ctx.prec
-        ig_prec = 'f16x3' if prec == 'f16x1' else prec
-        wap = cache.get_pieces(weight)[1] if (ig_prec == 'f16x3' and USE_PIECES and not weight.requires_grad) else None
+        nprod, ig_prec, fp16 = P.products(prec), P.loader_precision(prec), P.presplit_arith(prec)
+        frozen = not weight.requires_grad
+        wap = cache.get_pieces(weight)[1] if (ig_prec == 'f16x3' and USE_PIECES and frozen) else None
         dz_img = None
         if pre is not None:
             _, dbias, dd, dnoise, dstrength, amax = pre[:6]
             dz_img = pre[6] if len(pre) > 6 else None
-            ds = None if ks_adj is None else H.zeros((N, Ci), dev)
+            ds = H.zeros((N, Ci), dev) if need_dx else None
         else:
             dbias, dd, dnoise, dstrength, ds, amax = _zeros_views(
                 dev, (Co,) if need_b else None, (N, Co) if (need_s or need_w) else None,
                 tuple(nz.shape) if (need_nz and nz is not None) else None, () if (need_ns and nz is not None) else None,
-                None if ks_adj is None else ((rep, N, Ci) if rep > 1 else (N, Ci)),
-                (1,) if (prec in ('f16x3', 'f16x1') and ks_adj is not None) else None)          # max|dz|: operand range of the two-piece fp16 data gradient
+                (N, Ci) if need_dx else None,
+                (1,) if (fp16 and need_dx) else None)          # max|dz|: operand range of the two-piece fp16 data gradient
             H.epilogue_bwd(dout, out, dz, d=d, noise=nz, noise_nstride=nstride or 0, noise_strength=noise_strength if nz is not None else None,
                            bias=b, act='lrelu', alpha=0.2, gain=act_gain, clamp=clampv, dbias=dbias, dd=dd, dnoise=dnoise,
                            dnoise_nstride=nstride or 0, dstrength=dstrength, dz_amax=amax)
+        assert kh == kw
+        geom = (N, Ci, Co, Hi, Wi, kh, up, prec)
+        dplan = P.plan_dgrad(*geom, frozen, amax_known=amax is not None, need_dx=need_dx, need_w=need_w)      # which kernels, and why: conv_plan.py
+        wplan = P.plan_wgrad(*geom, amax_known=amax is not None, need_dx=need_dx, fwd=ctx.plan) if need_w else None
         amul = 1.0 if up == 1 else float(up * up)       # g = FIR(dz) * up^2 with a non-negative unit-sum filter: |g| <= up^2 max|dz|
         gimg = None
         if up == 1:
@@ -526,19 +482,14 @@ class ModConvLayerFn(torch.autograd.Function):
             cls_adj = H.classes_corr_adjoint(Hi, Wi, kh, kw, kh // 2)
             in_stride = 1
             cls_w, out_stride_w = H.classes_corr(Ho, Wo, kh, kw, kh // 2), 1
-        elif ((need_x or need_s or need_w) and up == 2 and kh == 3 and kw == 3 and prec in ('f16x3', 'f16x1') and amax is not None
-              and (not (need_x or need_s) or H.conv_s2adj_ok(Co, Ci, Hi, Wi, N) or H.conv_v3_s2adj_ok(Co, Ci, Hi, Wi, N))
-              and (not need_w or H.conv_wgrad_v2_up_ok(Ci, Co, Hi, Wi, N))):
-            # the FIR adjoint writes the gradient operand directly as parity-split fp16 images (range bound up^2 max|dz|) -- no fp32 g, no strided
-            # gathers in a conv loader: the data gradient (conv_v2_s2adj / conv_v3_s2adj) and, when the weights train, the weight gradient
-            # (conv_wgrad_v2_up) both read them
-            g = None
-            gimg = H.fir44_adjoint_split(dz, amax, gain=float(up * up))
-            cls_adj = H.classes_convT_adjoint(Hi, Wi, kh, kw, up)
-            in_stride = up
-            cls_w, out_stride_w = H.classes_convT(Hi, Wi, kh, kw, up)[0], up
         else:
-            if FIR_ADJ_LDS and Co % 64 == 0 and dz.shape[2] * dz.shape[3] >= FIR_ADJ_LDS:
+            if dplan.fir_split:
+                # the FIR adjoint writes the gradient operand directly as parity-split fp16 images (range bound up^2 max|dz|) -- no fp32 g, no strided
+                # gathers in a conv loader: the data gradient (conv_v2_s2adj / conv_v3_s2adj) and, when the weights train, the weight gradient
+                # (conv_wgrad_v2_up) both read them
+                g = None
+                gimg = H.fir44_adjoint_split(dz, amax, gain=float(up * up))
+            elif FIR_ADJ_LDS and Co % 64 == 0 and dz.shape[2] * dz.shape[3] >= FIR_ADJ_LDS:
                 # the separable, LDS-tiled FIR pass of the forward (1.6 loads per output instead of 6.25): the [1,3,3,1] filter is its own flip
                 g = H.empty_cl(N, Co, dz.shape[2] + 1, dz.shape[3] + 1, dev)
                 H.upconv_epilogue_fwd(dz, g, pad0=2, fir_gain=float(up * up))
@@ -548,66 +499,43 @@ class ModConvLayerFn(torch.autograd.Function):
             in_stride = up
             cls_w, out_stride_w = H.classes_convT(Hi, Wi, kh, kw, up)[0], up
         dx = None
-        if need_x or need_s:
+        if need_dx:
             dx = H.empty_cl(N, Ci, Hi, Wi, dev)
             aflops = 2.0 * N * Hi * Wi * kh * kw * Ci * Co
-            ks = ks_adj
             # x is some layer's output: if that layer left a record, this launch also runs ITS activation backward (dx then holds its dz)
             prod, spec, pacc = _act_bwd_for(x, dev) if (need_x and ctx.fuse_input) else (None, None, None)
             fkw = dict(act_bwd=spec, out_amax=pacc[4]) if prod is not None else {}
-            ks2 = H.conv_v2_ksplit(Co, Ci, cls_adj, N) if (up == 1 and prec in ('f16x3', 'f16x1') and amax is not None) else 0
-            if gimg is not None:
+            bwd_kw = dict(epi=L.EPI_BWD, out_scale=styles, xin=x, ds=ds, algo_flops=aflops)
+            if dplan.fir_split:
                 if not fkw and SPLIT_DZ:          # dx goes on to a toRGB node as its pass-through gradient: that pass wants max|dx| (torgb_dgrad_act_split)
                     dx_amax = H.zeros((1,), dev)
                     fkw = dict(out_amax=dx_amax)
                     _DX_AMAX[dx.data_ptr()] = (dx_amax, weakref.ref(dx))
-                did = H.conv_v2_s2adj(gimg, cache.get_split(weight)[1], dx, cls_adj, epi=L.EPI_BWD, out_scale=styles, xin=x, ds=ds, algo_flops=aflops,
-                                      products=1 if prec == 'f16x1' else 3, v3=not H.conv_s2adj_ok(Co, Ci, Hi, Wi, N), **fkw)
-            elif H.USE_V2 and up == 1 and (ks == 1 or H.conv_v2_rows(Co, Ci, cls_adj, N) == 2) and prec in ('f16x3', 'f16x1') and H.conv_v2_supported(Co, Ci, cls_adj, N):
+                did = H.conv_v2_s2adj(gimg, cache.get_split(weight)[1], dx, cls_adj, products=nprod, v3=dplan.form == 'v3_s2adj', **bwd_kw, **fkw)
+            elif dplan.takes_image:
                 gimg = dz_img if dz_img is not None else H.split_activation(g, amax)           # (kept: the weight gradient below reads it too)
-                did = H.conv_v2(gimg, cache.get_split(weight)[1], dx, cls_adj, epi=L.EPI_BWD,
-                                out_scale=styles, xin=x, ds=ds, algo_flops=aflops, products=1 if prec == 'f16x1' else 3, **fkw)
                 dz_img = None
-            elif up == 1 and prec in ('f16x3', 'f16x1') and amax is not None and H.conv_v3_plan(Co, Ci, cls_adj, N):
-                # under-filled 3x3 grid: data gradient, style gradient and the producer's activation backward from one launch of the wave-split kernel
-                gimg = dz_img if dz_img is not None else H.split_activation(g, amax)
-                did = H.conv_v3(gimg, cache.get_split(weight)[1], dx, cls_adj, plan=H.conv_v3_plan(Co, Ci, cls_adj, N), epi=L.EPI_BWD, out_scale=styles,
-                                xin=x, ds=ds, algo_flops=aflops, products=1 if prec == 'f16x1' else 3, **fkw)
-                dz_img = None
-            elif ks2:                              # under-filled 3x3 grid: split-K launch of the pre-split kernel, then the finishing pass
+                if dplan.form == 'v2':
+                    did = H.conv_v2(gimg, cache.get_split(weight)[1], dx, cls_adj, products=nprod, patch_rows=dplan.rows, **bwd_kw, **fkw)
+                else:
+                    did = H.conv_v3(gimg, cache.get_split(weight)[1], dx, cls_adj, plan=dplan.v3, products=nprod, **bwd_kw, **fkw)
+            elif not dplan.finish:
+                did = H.conv_igemm(g, wa, Co, Ci, dx, cls_adj, in_stride=in_stride, w_pieces=wap, precision=ig_prec, a_amax=amax, a_amax_mul=amul, **bwd_kw, **fkw)
+            else:                                  # low resolution: split K over blocks, then scale / reduce in a finishing pass
                 z = H.zeros_cl(N, Ci, Hi, Wi, dev)
-                H.conv_v2(H.split_activation(g, amax), cache.get_split(weight)[1], z, cls_adj, epi=L.EPI_ATOMIC, ksplit=ks2, algo_flops=aflops,
-                          products=1 if prec == 'f16x1' else 3)
+                if dplan.form == 'ws':
+                    H.conv_ws(g, cache.get_split(weight)[1], z, cls_adj, x_amax=amax, products=nprod, algo_flops=aflops)
+                elif dplan.form == 'ws_s2':
+                    H.conv_ws(g, cache.get_split(weight)[1], z, cls_adj, x_amax=amax, x_amax_mul=amul, products=nprod, algo_flops=aflops, in_stride=2)
+                else:
+                    H.conv_atomic(g, wa, Co, Ci, z, cls_adj, in_stride=in_stride, ksplit=dplan.ksplit, algo_flops=aflops, precision=ig_prec, a_amax=amax, w_pieces=wap,
+                                  a_amax_mul=amul)
                 did = prod is not None and Ci % 4 == 0 and Ci <= 1024
                 if did:
                     H.dgrad_finish_act(z, x, styles, dx, spec, ds=ds, dz_amax=pacc[4])
                 elif ctx.from_torgb and H.DEFER_DGRAD_FINISH and need_x and prod is None and d_given:
                     _pend_dgrad(x, z, styles, ds)                          # the toRGB node that receives this gradient next finishes it in its launch (d_given: `ds` is read by
                                                                           # the style bank's node, which runs after every layer -- a per-layer affine would read it before the x.z term lands)
-                    dx = z
-                else:
-                    H.dgrad_finish(z, x, styles, dx, ds=ds)
-            elif ks == 1:
-                did = H.conv_igemm(g, wa, Co, Ci, dx, cls_adj, in_stride=in_stride, epi=L.EPI_BWD, out_scale=styles, xin=x, ds=ds, algo_flops=aflops, w_pieces=wap,
-                                   precision=ig_prec, a_amax=amax, a_amax_mul=amul, **fkw)
-                if rep > 1:
-                    ds = ds.sum(0)
-            else:                                  # low resolution: split K over blocks, then scale / reduce in a finishing pass
-                z = H.zeros_cl(N, Ci, Hi, Wi, dev)
-                if up == 1 and prec in ('f16x3', 'f16x1') and amax is not None and (H.CONV_WS_TRAINABLE or not weight.requires_grad) and H.conv_ws_ok(Co, Ci, cls_adj, N, Hi, Wi):
-                    H.conv_ws(g, cache.get_split(weight)[1], z, cls_adj, x_amax=amax, products=1 if prec == 'f16x1' else 3, algo_flops=aflops)
-                elif (up == 2 and g is not None and kh == 3 and kw == 3 and prec in ('f16x3', 'f16x1') and amax is not None and (H.CONV_WS_TRAINABLE or not weight.requires_grad)
-                      and H.conv_ws_ok(Co, Ci, cls_adj, N, Hi, Wi, in_stride=2)):
-                    H.conv_ws(g, cache.get_split(weight)[1], z, cls_adj, x_amax=amax, x_amax_mul=amul, products=1 if prec == 'f16x1' else 3, algo_flops=aflops,
-                              in_stride=2)
-                else:
-                    H.conv_atomic(g, wa, Co, Ci, z, cls_adj, in_stride=in_stride, ksplit=ks, algo_flops=aflops, precision=ig_prec, a_amax=amax, w_pieces=wap,
-                                  a_amax_mul=amul)
-                did = prod is not None and Ci % 4 == 0 and Ci <= 1024
-                if did:
-                    H.dgrad_finish_act(z, x, styles, dx, spec, ds=ds, dz_amax=pacc[4])
-                elif ctx.from_torgb and H.DEFER_DGRAD_FINISH and need_x and prod is None and d_given:
-                    _pend_dgrad(x, z, styles, ds)                          # the toRGB node that receives this gradient next finishes it in its launch
                     dx = z
                 else:
                     H.dgrad_finish(z, x, styles, dx, ds=ds)
@@ -623,33 +551,27 @@ class ModConvLayerFn(torch.autograd.Function):
             H.demod_bwd(styles, wsq, d, dd, ds=ds)
         dweight = None
         if need_w:
-            dwp = None
             # same arithmetic as the data gradient: two-piece fp16 split with the gradient operand range-normalised by max|dz|
-            wprec = prec if (prec in ('f16x3', 'f16x1') and amax is not None) else 'f32'
-            ximg = getattr(ctx, 'aimg', None)
-            if up == 1 and ximg is not None and wprec != 'f32' and amax is not None:
-                if gimg is None:
-                    gimg = H.split_activation(g, amax)
-                use_v2w = H.conv_wgrad_v2_ok(gimg, ximg, cls_w)
-            else:
-                use_v2w = False
-            if up == 2 and g is None:       # up layer on the parity-split path: G as the four parity images, X as the forward's (or a fresh) operand image
-                if ximg is None:
-                    ximg = H.split_activation(x, H.amax_of(x), in_scale=styles)
+            wprod = P.products(wplan.precision)
+            if wplan.form == 'v2_up':       # up layer on the parity-split path: G as the four parity images, X as the forward's (or a fresh) operand image
+                ximg = ctx.aimg if ctx.aimg is not None else H.split_activation(x, H.amax_of(x), in_scale=styles)
                 wtaps = [0] * 9
                 for c_ in cls_w:
                     for t_ in range(c_.ntaps):
                         wtaps[3 * (c_.out_py - 2 * c_.dy[t_]) + (c_.out_px - 2 * c_.dx[t_])] = c_.wtap[t_]
-                dwp = H.conv_wgrad_v2_up(gimg, ximg, H.zeros(wf.shape, dev), wtaps, products=1 if wprec == 'f16x1' else 3)
-            elif use_v2w:       # both operands as the split images the forward / data gradient consumed: LDS-DMA + transposing LDS reads, no VALU loader
-                if H.WGRAD_SLABS:       # partial tiles stored, summed in slab order by weight_grad_finish: no atomics, no zero fill
-                    dwp = H.conv_wgrad_v2_slabs(gimg, ximg, cls_w, products=1 if wprec == 'f16x1' else 3)
+                dwp = H.conv_wgrad_v2_up(gimg, ximg, H.zeros(wf.shape, dev), wtaps, products=wprod)
+            elif wplan.form in ('v2', 'v2_slabs'):       # both operands as the split images the forward / data gradient consumed: LDS-DMA + transposing LDS reads, no VALU loader
+                assert ctx.aimg is not None, 'the weight-gradient plan reads the operand image the forward was to keep'
+                if gimg is None:
+                    gimg = H.split_activation(g, amax)
+                if wplan.form == 'v2_slabs':       # partial tiles stored, summed in slab order by weight_grad_finish: no atomics, no zero fill
+                    dwp = H.conv_wgrad_v2_slabs(gimg, ctx.aimg, cls_w, products=wprod)
                 else:
-                    dwp = H.conv_wgrad_v2(gimg, ximg, H.zeros(wf.shape, dev), cls_w, products=1 if wprec == 'f16x1' else 3)
+                    dwp = H.conv_wgrad_v2(gimg, ctx.aimg, H.zeros(wf.shape, dev), cls_w, products=wprod)
             else:
                 dwp = H.zeros(wf.shape, dev)
-                H.conv_wgrad(x, g, Ci, Co, dwp, cls_w, in_stride=1, out_stride=out_stride_w, in_scale=styles, precision=wprec,
-                             g_amax=amax if wprec != 'f32' else None, g_amax_mul=amul)
+                H.conv_wgrad(x, g, Ci, Co, dwp, cls_w, in_stride=1, out_stride=out_stride_w, in_scale=styles, precision=wplan.precision,
+                             g_amax=amax if wplan.precision != 'f32' else None, g_amax_mul=amul)
             # [O,taps,I] accumulator -> the parameter's own (contiguous [O,I,kh,kw]) layout, plus the demodulation path d wsq / d w = 2 w
             # (dwsq from dd on the fly), in one pass; the fused multi-tensor Adam walks parameter and gradient with the same linear index
             dweight = H.weight_grad_finish(dwp, weight, styles, d, dd)

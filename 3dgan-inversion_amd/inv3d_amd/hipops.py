@@ -435,6 +435,49 @@ class ActBwdSpec:
         ab.dbias, ab.dd, ab.dnoise, ab.dstrength = tp(self.dbias), tp(self.dd), tp(self.dnoise), tp(self.dstrength)
 
 
+def _try_act_bwd(p, act_bwd, supported, aligned16=True):
+    """Turn a prepared EPI_BWD launch into EPI_BWD_ACT when the library takes it (`supported`: its check for this kernel) and, for the kernels
+    that load them as 16-byte vectors, the producer's d / bias are so aligned; else leave a plain EPI_BWD.  Returns whether the fused epilogue runs."""
+    p.epi = L.EPI_BWD_ACT
+    act_bwd.fill(p.act_bwd)
+    ok = bool(supported(C.byref(p))) and (not aligned16 or all(t is None or t.data_ptr() % 16 == 0 for t in (act_bwd.d, act_bwd.bias)))
+    if not ok:
+        p.epi = L.EPI_BWD
+        p.act_bwd = L.ActBwd()
+    return ok
+
+
+def _recorded(launch, cfg_id, prec_id, algo_flops, default_flops, meta):
+    """Run the launch thunk; under an active LaunchProfiler that times this kernel id, between two events, and leave its record
+    ((kernel id, precision id), algorithmic FLOPs -- `default_flops()` when the caller gave none --, events) and, when kept, `meta()`."""
+    prof = PROFILER
+    if prof is None or (prof.only_config is not None and prof.only_config != cfg_id):
+        return launch()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    launch()
+    e1.record()
+    prof.records.append(((cfg_id, prec_id), float(default_flops() if algo_flops is None else algo_flops), e0, e1))
+    if prof.meta is not None:
+        prof.meta.append(meta())
+
+
+def _patches(N, H, W, rows):
+    """rows x 32-cell patches that cover an H x W grid of N images."""
+    return N * -(-H // rows) * -(-W // 32)
+
+
+def tiles(classes, N, rows, Nc, ctile):
+    """Workgroups of a launch that covers every tap class of N images with rows x 32-cell patches and ctile-channel tiles."""
+    return sum(_patches(N, c.Ha, c.Wa, rows) for c in classes) * (Nc // ctile)
+
+
+def _taps_in_3x3(c):
+    """All taps of a class within a 3 x 3 window (the halo the pre-split kernels stage)."""
+    dys, dxs = [c.dy[t] for t in range(c.ntaps)], [c.dx[t] for t in range(c.ntaps)]
+    return max(dys) - min(dys) <= 2 and max(dxs) - min(dxs) <= 2
+
+
 def conv_igemm(x, wp, Ck, Nc, out, classes, in_stride=1, out_stride=1, in_scale=None, epi=L.EPI_STORE, ksplit=1,
                out_scale=None, bias=None, noise=None, noise_nstride=0, noise_strength=None, act='linear', alpha=0.0, gain=1.0,
                clamp=-1.0, addend=None, xin=None, ds=None, algo_flops=None, precision=None, a_amax=None, a_amax_mul=1.0, out_amax=None,
@@ -483,31 +526,12 @@ def conv_igemm(x, wp, Ck, Nc, out, classes, in_stride=1, out_stride=1, in_scale=
     if w_pieces is not None and p.precision == PRECISIONS['f16x3']:      # the packed weights' pre-split image (split_weight_pieces): same indexing
         assert w_pieces.shape == wp.shape and w_pieces.stride() == wp.stride()
         p.w, p.w_presplit = w_pieces.data_ptr(), 1
-    fused_act = False
-    if act_bwd is not None and epi == L.EPI_BWD:
-        p.epi = L.EPI_BWD_ACT
-        act_bwd.fill(p.act_bwd)
-        fused_act = bool(L.lib().eg3d_conv2d_igemm_act_bwd_ok(C.byref(p)))
-        if not fused_act:
-            p.epi = L.EPI_BWD
-            p.act_bwd = L.ActBwd()
-    prof = PROFILER
-    if prof is not None:
-        cfg = L.lib().eg3d_conv2d_igemm_config(C.byref(p))
-        if prof.only_config is not None and cfg != prof.only_config:
-            prof = None
-    if prof is not None:
-        if algo_flops is None:
-            algo_flops = 2.0 * Ck * Nc * sum(n * c.Ha * c.Wa * c.ntaps for c in classes)
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-    L.check(L.lib().eg3d_conv2d_igemm_f32(C.byref(p), L.stream_ptr()), 'conv2d_igemm_f32')
-    if prof is not None:
-        e1.record()
-        prof.records.append(((cfg, int(p.precision)), float(algo_flops), e0, e1))
-        if prof.meta is not None:
-            prof.meta.append(dict(N=n, Hi=hi, Wi=wi, Ck=Ck, Nc=Nc, Ho=ho, Wo=wo, taps=[c.ntaps for c in classes], epi=epi, ksplit=ksplit,
-                                  in_stride=in_stride, out_stride=out_stride, prec=p.precision))
+    fused_act = act_bwd is not None and epi == L.EPI_BWD and _try_act_bwd(p, act_bwd, L.lib().eg3d_conv2d_igemm_act_bwd_ok, aligned16=False)
+    _recorded(lambda: L.check(L.lib().eg3d_conv2d_igemm_f32(C.byref(p), L.stream_ptr()), 'conv2d_igemm_f32'),
+              L.lib().eg3d_conv2d_igemm_config(C.byref(p)) if PROFILER is not None else None, int(p.precision), algo_flops,
+              lambda: 2.0 * Ck * Nc * sum(n * c.Ha * c.Wa * c.ntaps for c in classes),
+              lambda: dict(N=n, Hi=hi, Wi=wi, Ck=Ck, Nc=Nc, Ho=ho, Wo=wo, taps=[c.ntaps for c in classes], epi=epi, ksplit=ksplit,
+                           in_stride=in_stride, out_stride=out_stride, prec=p.precision))
     return fused_act if act_bwd is not None else out
 
 
@@ -611,37 +635,26 @@ def _conv_v2_params(a, w, out, classes, out_stride, epi, out_scale, bias, noise,
 
 def conv_v2_tiles(Nc, classes, N=1):
     """256-cell x 128-channel tiles of a launch of the pre-split kernel."""
-    return sum(N * -(-c.Ha // 8) * -(-c.Wa // 32) for c in classes) * (Nc // 128)
+    return tiles(classes, N, 8, Nc, 128)
 
 
 def conv_v2_geometry_ok(Ck, Nc, classes):
     if Ck % 16 or Nc % 128 or CONV_MODE != 'auto':
         return False
-    for c in classes:
-        if c.ntaps not in (9, 4, 2, 1):
-            return False
-        dys, dxs = [c.dy[t] for t in range(c.ntaps)], [c.dx[t] for t in range(c.ntaps)]
-        if max(dys) - min(dys) > 2 or max(dxs) - min(dxs) > 2:
-            return False
-    return True
+    return all(c.ntaps in (9, 4, 2, 1) and _taps_in_3x3(c) for c in classes)
 
 
 def conv_v2_rows(Ck, Nc, classes, N=1):
-    """Patch rows (8 | 4 | 2) the pre-split kernel should run this launch with, 0 = not a launch for it.  8 x 32-cell patches when they fill the
+    """Patch rows (8 | 4) the pre-split kernel should run this launch with, 0 = not a launch for it.  8 x 32-cell patches when they fill the
     chip (>= V2_MIN_TILES workgroups); nine-tap classes whose 8-row grid does not but whose 4-row grid does (128^2 x 256: 128 -> 256
     workgroups) take the half-height patch -- fused epilogues intact, no split-K."""
     if not conv_v2_geometry_ok(Ck, Nc, classes):
         return 0
     tiles8 = conv_v2_tiles(Nc, classes, N)
     half_ok = V2_HALF and all(c.ntaps == 9 for c in classes)
-    tiles4 = sum(N * -(-c.Ha // 4) * -(-c.Wa // 32) for c in classes) * (Nc // 128)
-    if half_ok and tiles8 < V2_HALF_BELOW and tiles4 >= V2_MIN_TILES:
+    if half_ok and tiles8 < V2_HALF_BELOW and tiles(classes, N, 4, Nc, 128) >= V2_MIN_TILES:
         return 4
-    if tiles8 >= V2_MIN_TILES:
-        return 8
-    # 64^2 x 512 (64 workgroups of 8 rows): 2 x 32-cell patches give 256 (opt-in: V2_QUARTER)
-    tiles2 = sum(N * -(-c.Ha // 2) * -(-c.Wa // 32) for c in classes) * (Nc // 128)
-    return 2 if (half_ok and V2_QUARTER and tiles2 >= V2_MIN_TILES) else 0
+    return 8 if tiles8 >= V2_MIN_TILES else 0
 
 
 def conv_v2_supported(Ck, Nc, classes, N=1):
@@ -649,21 +662,8 @@ def conv_v2_supported(Ck, Nc, classes, N=1):
     return conv_v2_rows(Ck, Nc, classes, N) != 0
 
 
-def conv_v2_ksplit(Ck, Nc, classes, N=1):
-    """Split-K factor for a 3x3 layer whose grid cannot fill the chip with 256 x 128 tiles (128^2 x 256: 128 tiles, 64^2 x 512: 64):
-    slices of >= V2_KS_MIN_CHUNKS 16-channel chunks, aiming at two workgroups per CU.  0 = leave the layer to the loader-split kernel."""
-    if not (USE_V2 and V2_SPLITK) or len(classes) != 1 or classes[0].ntaps != 9 or not conv_v2_geometry_ok(Ck, Nc, classes):
-        return 0
-    tiles = conv_v2_tiles(Nc, classes, N)
-    if tiles >= V2_MIN_TILES or tiles < V2_KS_MIN_TILES:
-        return 0
-    ks = min(-(-V2_KS_TARGET // tiles), (Ck // 16) // V2_KS_MIN_CHUNKS)
-    return ks if ks >= 2 else 0
-
-
 V2_MIN_TILES = 256
 USE_V2 = os.environ.get('EG3D_CONV_V2', '1') != '0'
-V2_CONVT = False          # (was EG3D_V2_CONVT: the up layers on tap classes of the pre-split kernel -- superseded by conv_up2; tests set the attribute)
 # 4 x 32-cell patches for under-filled 3x3 grids (conv_v2_rows): 128^2 x 256: 107 -> 91 us, 256^2 x 128: 84 -> 67 us per launch.  (Off in the
 # first half of round 3: with the fused epilogues a few hundred of 8 M output elements per launch came out wrong on full-size layers --
 # a miscompile of the scalar epilogue arithmetic by the SLP vectoriser, see the Makefile; tests/test_gpu_ops.py::test_conv_v2_half_patch_full_size.)
@@ -672,18 +672,7 @@ V2_CONVT = False          # (was EG3D_V2_CONVT: the up layers on tap classes of 
 V2_KHALVES = os.environ.get('EG3D_V2_KHALVES', '1') != '0'
 V2_KHALVES_MAX_TILES = 256
 V2_HALF = os.environ.get('EG3D_V2_HALF', '1') != '0'             # half-height (4 x 32) patches for nine-tap launches ...
-# quarter-height (2 x 32) patches where not even the 4-row grid fills the chip (64^2 x 512: 64 -> 256 workgroups): OFF by default.  Stand-alone
-# (weights warm in L2) 74 us against 99 + 23 (4-way split-K launch of the loader-split kernel + its finishing pass); inside the step, where every
-# workgroup streams its 2.4 MB weight slice from HBM / MALL, 109 us + the 12 us operand split: no gain (194.3 vs 194.3 steps/s, A/B in one session)
-V2_QUARTER = False        # (was EG3D_V2_QUARTER; lost its A/B twice -- tests set the attribute)
 V2_HALF_BELOW = 512      # ... when the 8-row grid has fewer workgroups than this (256^2 x 128: 84 -> 67 us, 128^2 x 256: 107 -> 91 us)
-# split-K launches of the pre-split kernel for under-filled 3x3 grids: OFF by default.  Measured at N = 1 (MI355X): 128^2 x 256 118 -> 81 us,
-# 64^2 x 512 103 -> 82 us per launch, but the operand split pass (7 us), the zero fill and the finishing pass (2 x 10 us; the loader-split
-# kernel's fused epilogue needs neither on the 128^2 layer) eat it: -1.2 % per step.  Batched runs do not need it (the grids fill).
-V2_SPLITK = False         # (was EG3D_V2_SPLITK; -1.2 % twice -- tests set the attribute)
-V2_KS_TARGET = 512        # workgroups a split launch aims for (2 per CU)
-V2_KS_MIN_TILES = 32      # 32^2 x 512 (16 tiles): no gain over the loader-split kernel (46.8 vs 46.4 us)
-V2_KS_MIN_CHUNKS = 2
 
 
 def conv_v2(a: SplitImage, w: SplitImage, out, classes, out_stride=1, epi=L.EPI_STORE, out_scale=None, bias=None, noise=None, noise_nstride=0,
@@ -705,7 +694,7 @@ def conv_v2(a: SplitImage, w: SplitImage, out, classes, out_stride=1, epi=L.EPI_
         patch_rows = conv_v2_rows(p.Ck, p.Nc, classes, p.N) if epi != L.EPI_ATOMIC else 8
     p.patch_rows = patch_rows if patch_rows in (4, 2) else 8
     if (V2_KHALVES and p.patch_rows == 4 and epi != L.EPI_ATOMIC and ksplit <= 1 and rgb_head is None and (p.Ck // 16) % 2 == 0 and p.Ck >= 64
-            and sum(p.N * -(-c.Ha // 4) * -(-c.Wa // 32) for c in classes) * (p.Nc // 128) <= V2_KHALVES_MAX_TILES):
+            and tiles(classes, p.N, 4, p.Nc, 128) <= V2_KHALVES_MAX_TILES):
         # one workgroup per CU: eight waves, the contraction split over the two four-wave halves inside the workgroup (KH = 2 of conv_v2_kernel)
         p.ksplit = 2
     if rgb_head is not None:
@@ -720,33 +709,14 @@ def conv_v2(a: SplitImage, w: SplitImage, out, classes, out_stride=1, epi=L.EPI_
             rgb_head = None
         if rgb_head_ran is not None:
             rgb_head_ran.append(rgb_head is not None)
-    fused_act = False
-    if act_bwd is not None and epi == L.EPI_BWD and xin is not None:
-        p.epi = L.EPI_BWD_ACT
-        act_bwd.fill(p.act_bwd)
-        fused_act = bool(L.lib().eg3d_conv2d_v2_supported(C.byref(p))) and all(
-            t is None or t.data_ptr() % 16 == 0 for t in (act_bwd.d, act_bwd.bias))
-        if not fused_act:
-            p.epi = L.EPI_BWD
-            p.act_bwd = L.ActBwd()
-    prof = PROFILER
+    fused_act = act_bwd is not None and epi == L.EPI_BWD and xin is not None and _try_act_bwd(p, act_bwd, L.lib().eg3d_conv2d_v2_supported)
     cfg_id = {8: V2_CONFIG, 4: V2H_CONFIG, 2: V2Q_CONFIG}[int(p.patch_rows)]   # the patch heights are different instantiations: separate profiler records
     if rgb_head is not None:
         cfg_id = V2RGB_CONFIG       # ... and so is the one with the 1x1 head (conv_v2_kernel<9,*,false,4,true>)
-    if prof is not None and prof.only_config is not None and prof.only_config != cfg_id:
-        prof = None
-    if prof is not None:
-        if algo_flops is None:
-            algo_flops = 2.0 * p.Ck * p.Nc * sum(p.N * c.Ha * c.Wa * c.ntaps for c in classes)
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-    L.check(L.lib().eg3d_conv2d_v2(C.byref(p), L.stream_ptr()), 'conv2d_v2')
-    if prof is not None:
-        e1.record()
-        prof.records.append(((cfg_id, PRECISIONS['f16x3']), float(algo_flops), e0, e1))
-        if prof.meta is not None:
-            prof.meta.append(dict(N=p.N, Hi=p.Hi, Wi=p.Wi, Ck=p.Ck, Nc=p.Nc, Ho=p.Ho, Wo=p.Wo, taps=[c.ntaps for c in classes], epi=epi, ksplit=int(ksplit),
-                                  in_stride=1, out_stride=out_stride, prec=3, v2=True, patch_rows=int(p.patch_rows)))
+    _recorded(lambda: L.check(L.lib().eg3d_conv2d_v2(C.byref(p), L.stream_ptr()), 'conv2d_v2'), cfg_id, PRECISIONS['f16x3'], algo_flops,
+              lambda: 2.0 * p.Ck * p.Nc * sum(p.N * c.Ha * c.Wa * c.ntaps for c in classes),
+              lambda: dict(N=p.N, Hi=p.Hi, Wi=p.Wi, Ck=p.Ck, Nc=p.Nc, Ho=p.Ho, Wo=p.Wo, taps=[c.ntaps for c in classes], epi=epi, ksplit=int(ksplit),
+                           in_stride=1, out_stride=out_stride, prec=3, v2=True, patch_rows=int(p.patch_rows)))
     return fused_act if act_bwd is not None else out
 
 
@@ -763,18 +733,18 @@ def conv_v3_plan(Ck, Nc, classes, N=1):
     over eight waves (twice the workgroups, half the steps per wave)."""
     if not USE_V3 or CONV_MODE != 'auto' or Ck % 16 or Nc % 64 or not (1 <= len(classes) <= 4):
         return None
-    for c in classes:
-        if c.ntaps != 9:
-            return None
-        dys, dxs = [c.dy[t] for t in range(9)], [c.dx[t] for t in range(9)]
-        if max(dys) - min(dys) > 2 or max(dxs) - min(dxs) > 2:
-            return None
+    if any(c.ntaps != 9 or not _taps_in_3x3(c) for c in classes):
+        return None
     cells = sum(N * c.Ha * c.Wa for c in classes)
-    tiles8 = sum(N * -(-c.Ha // 8) * -(-c.Wa // 32) for c in classes) * -(-Nc // 128)
+    tiles8 = sum(_patches(N, c.Ha, c.Wa, 8) for c in classes) * -(-Nc // 128)      # (a 64-channel remainder counts as a tile)
     if cells < V3_MIN_CELLS or tiles8 >= V3_MAX_TILES8:
         return None
-    wg4 = sum(N * -(-c.Ha // 4) * -(-c.Wa // 32) for c in classes) * (Nc // 64)
-    return (4, 4) if wg4 >= 192 else (2, 8)
+    return conv_v3_tiling(classes, N, Nc)
+
+
+def conv_v3_tiling(classes, N, Nc):
+    """(patch_rows, waves) of a launch the wave-split kernel takes: see conv_v3_plan."""
+    return (4, 4) if tiles(classes, N, 4, Nc, 64) >= 192 else (2, 8)
 
 
 def conv_v3(a: SplitImage, w: SplitImage, out, classes, plan=None, out_stride=1, epi=L.EPI_STORE, out_scale=None, bias=None, noise=None, noise_nstride=0,
@@ -787,39 +757,17 @@ def conv_v3(a: SplitImage, w: SplitImage, out, classes, plan=None, out_stride=1,
                         addend, xin, ds, out_amax)
     rows, waves = plan if plan is not None else (4, 4)
     p.products, p.patch_rows, p.ksplit = int(products), int(rows), int(waves)
-    fused_act = False
-    if act_bwd is not None and epi == L.EPI_BWD and xin is not None:
-        p.epi = L.EPI_BWD_ACT
-        act_bwd.fill(p.act_bwd)
-        fused_act = bool(L.lib().eg3d_conv2d_v3_supported(C.byref(p))) and all(
-            t is None or t.data_ptr() % 16 == 0 for t in (act_bwd.d, act_bwd.bias))
-        if not fused_act:
-            p.epi = L.EPI_BWD
-            p.act_bwd = L.ActBwd()
-    prof = PROFILER
-    if prof is not None and prof.only_config is not None and prof.only_config != V3_CONFIG:
-        prof = None
-    if prof is not None:
-        if algo_flops is None:
-            algo_flops = 2.0 * p.Ck * p.Nc * sum(p.N * c.Ha * c.Wa * c.ntaps for c in classes)
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-    L.check(L.lib().eg3d_conv2d_v3(C.byref(p), L.stream_ptr()), 'conv2d_v3')
-    if prof is not None:
-        e1.record()
-        prof.records.append(((V3_CONFIG, PRECISIONS['f16x3']), float(algo_flops), e0, e1))
-        if prof.meta is not None:
-            prof.meta.append(dict(N=p.N, Hi=p.Hi, Wi=p.Wi, Ck=p.Ck, Nc=p.Nc, Ho=p.Ho, Wo=p.Wo, taps=[c.ntaps for c in classes], epi=epi, ksplit=int(waves),
-                                  in_stride=1, out_stride=out_stride, prec=3, v3=True, patch_rows=int(rows)))
+    fused_act = act_bwd is not None and epi == L.EPI_BWD and xin is not None and _try_act_bwd(p, act_bwd, L.lib().eg3d_conv2d_v3_supported)
+    _recorded(lambda: L.check(L.lib().eg3d_conv2d_v3(C.byref(p), L.stream_ptr()), 'conv2d_v3'), V3_CONFIG, PRECISIONS['f16x3'], algo_flops,
+              lambda: 2.0 * p.Ck * p.Nc * sum(p.N * c.Ha * c.Wa * c.ntaps for c in classes),
+              lambda: dict(N=p.N, Hi=p.Hi, Wi=p.Wi, Ck=p.Ck, Nc=p.Nc, Ho=p.Ho, Wo=p.Wo, taps=[c.ntaps for c in classes], epi=epi, ksplit=int(waves),
+                           in_stride=1, out_stride=out_stride, prec=3, v3=True, patch_rows=int(rows)))
     return fused_act if act_bwd is not None else out
 
 
 RGB_HEAD = os.environ.get('EG3D_RGB_HEAD', '1') != '0'       # the SR head's last toRGB evaluated in conv1's forward epilogue (eg3d_conv_v2_params::rgb_out)
 CONV_WS = os.environ.get('EG3D_CONV_WS', '1') != '0'
 CONV_WS_MAX_CELLS = 256
-# ... NOT when the weights carry gradients (pivotal tuning): measured in round 6 (A/B twice in one session, graph-replayed C4 step) 6.22 / 6.21 ms without,
-# 6.29 / 6.26 ms with -- re-splitting six more 9.4 MB weight tensors per step (forward + adjoint images) costs more than the twelve 19.7 us launches save
-CONV_WS_TRAINABLE = False
 CONV_WS_S2 = os.environ.get('EG3D_CONV_WS_S2', '1') != '0'      # ... and its stride-2 adjoint form for the data gradients of the 8^2 .. 32^2 up layers
 WS_CONFIG = 12
 
@@ -875,21 +823,10 @@ def conv_ws(x, w: SplitImage, out, classes, in_scale=None, x_amax=None, x_amax_m
     in_stride 2: the stride-2 adjoint form (x: the FIR-adjointed gradient of an up layer, out: its data gradient before the style scale)."""
     assert is_cl(x) and is_cl(out) and x.dtype == torch.float32
     p = _conv_ws_params(x, w, out, classes[0], in_scale, x_amax if x_amax is not None else absmax(x), x_amax_mul, products, in_stride)
-    prof = PROFILER
-    if prof is not None and prof.only_config is not None and prof.only_config != WS_CONFIG:
-        prof = None
-    if prof is not None:
-        if algo_flops is None:
-            algo_flops = 2.0 * p.Ck * p.Nc * p.N * p.H * p.W * 9
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-    L.check(L.lib().eg3d_conv2d_ws(C.byref(p), L.stream_ptr()), 'conv2d_ws')
-    if prof is not None:
-        e1.record()
-        prof.records.append(((WS_CONFIG, PRECISIONS['f16x3']), float(algo_flops), e0, e1))
-        if prof.meta is not None:
-            prof.meta.append(dict(N=p.N, Hi=p.Hx, Wi=p.Wx, Ck=p.Ck, Nc=p.Nc, Ho=p.H, Wo=p.W, taps=[9], epi=L.EPI_ATOMIC, ksplit=p.Ck // 16,
-                                  in_stride=int(in_stride), out_stride=1, prec=3, ws=True))
+    _recorded(lambda: L.check(L.lib().eg3d_conv2d_ws(C.byref(p), L.stream_ptr()), 'conv2d_ws'), WS_CONFIG, PRECISIONS['f16x3'], algo_flops,
+              lambda: 2.0 * p.Ck * p.Nc * p.N * p.H * p.W * 9,
+              lambda: dict(N=p.N, Hi=p.Hx, Wi=p.Wx, Ck=p.Ck, Nc=p.Nc, Ho=p.H, Wo=p.W, taps=[9], epi=L.EPI_ATOMIC, ksplit=p.Ck // 16,
+                           in_stride=int(in_stride), out_stride=1, prec=3, ws=True))
     return out
 
 
@@ -921,21 +858,10 @@ def conv_ws_up(x, w: SplitImage, out, in_scale=None, x_amax=None, x_amax_mul=1.0
     for t in range(9):
         p.dy[t], p.dx[t], p.wtap[t] = 0, 0, t
     p.products, p.in_stride, p.out_stride = int(products), 1, 2
-    prof = PROFILER
-    if prof is not None and prof.only_config is not None and prof.only_config != WS_CONFIG:
-        prof = None
-    if prof is not None:
-        if algo_flops is None:
-            algo_flops = 2.0 * p.Ck * p.Nc * p.N * p.H * p.W * 9
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-    L.check(L.lib().eg3d_conv2d_ws(C.byref(p), L.stream_ptr()), 'conv2d_ws (transposed)')
-    if prof is not None:
-        e1.record()
-        prof.records.append(((WS_CONFIG, PRECISIONS['f16x3']), float(algo_flops), e0, e1))
-        if prof.meta is not None:
-            prof.meta.append(dict(N=p.N, Hi=p.H, Wi=p.W, Ck=p.Ck, Nc=p.Nc, Ho=ho, Wo=wo, taps=[4, 2, 2, 1], epi=L.EPI_ATOMIC, ksplit=p.Ck // 16,
-                                  in_stride=1, out_stride=2, prec=3, ws=True))
+    _recorded(lambda: L.check(L.lib().eg3d_conv2d_ws(C.byref(p), L.stream_ptr()), 'conv2d_ws (transposed)'), WS_CONFIG, PRECISIONS['f16x3'], algo_flops,
+              lambda: 2.0 * p.Ck * p.Nc * p.N * p.H * p.W * 9,
+              lambda: dict(N=p.N, Hi=p.H, Wi=p.W, Ck=p.Ck, Nc=p.Nc, Ho=ho, Wo=wo, taps=[4, 2, 2, 1], epi=L.EPI_ATOMIC, ksplit=p.Ck // 16,
+                           in_stride=1, out_stride=2, prec=3, ws=True))
     return out
 
 
@@ -961,7 +887,7 @@ def conv_s2adj_ok(Ck, Nc, Hi, Wi, N=1):
     """The up layers' data gradient on the parity-split kernel (csrc/conv_v2_s2adj.hip): geometry + enough 256 x 128 tiles."""
     if not (USE_V2 and V2_S2ADJ) or CONV_MODE != 'auto' or Ck % 64 or Nc % 128:
         return False
-    return N * -(-Hi // 8) * -(-Wi // 32) * (Nc // 128) >= S2ADJ_MIN_TILES
+    return _patches(N, Hi, Wi, 8) * (Nc // 128) >= S2ADJ_MIN_TILES
 
 
 V3_S2ADJ = os.environ.get('EG3D_V3_S2ADJ', '1') != '0'
@@ -986,29 +912,11 @@ def conv_v2_s2adj(a: SplitImage, w: SplitImage, out, classes, epi=L.EPI_STORE, o
     p = _conv_v2_params(a, w, out, classes, 1, epi, out_scale, None, None, 0, None, 'linear', 0.0, 1.0, -1.0, addend, xin, ds, out_amax)
     p.in_stride = 2
     p.products, p.ksplit = int(products), int(ksplit)
-    fused_act = False
-    if act_bwd is not None and epi == L.EPI_BWD and xin is not None:
-        p.epi = L.EPI_BWD_ACT
-        act_bwd.fill(p.act_bwd)
-        fused_act = bool(fn_ok(C.byref(p))) and all(t is None or t.data_ptr() % 16 == 0 for t in (act_bwd.d, act_bwd.bias))
-        if not fused_act:
-            p.epi = L.EPI_BWD
-            p.act_bwd = L.ActBwd()
-    prof = PROFILER
-    if prof is not None and prof.only_config is not None and prof.only_config != cfg_id:
-        prof = None
-    if prof is not None:
-        if algo_flops is None:
-            algo_flops = 2.0 * p.Ck * p.Nc * p.N * classes[0].Ha * classes[0].Wa * 9
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-    L.check(fn(C.byref(p), L.stream_ptr()), nm)
-    if prof is not None:
-        e1.record()
-        prof.records.append(((cfg_id, PRECISIONS['f16x3']), float(algo_flops), e0, e1))
-        if prof.meta is not None:
-            prof.meta.append(dict(N=p.N, Hi=2 * p.Hi - 1, Wi=2 * p.Wi - 1, Ck=p.Ck, Nc=p.Nc, Ho=p.Ho, Wo=p.Wo, taps=[9], epi=epi, ksplit=int(ksplit), in_stride=2,
-                                  out_stride=1, prec=3, v2=True))
+    fused_act = act_bwd is not None and epi == L.EPI_BWD and xin is not None and _try_act_bwd(p, act_bwd, fn_ok)
+    _recorded(lambda: L.check(fn(C.byref(p), L.stream_ptr()), nm), cfg_id, PRECISIONS['f16x3'], algo_flops,
+              lambda: 2.0 * p.Ck * p.Nc * p.N * classes[0].Ha * classes[0].Wa * 9,
+              lambda: dict(N=p.N, Hi=2 * p.Hi - 1, Wi=2 * p.Wi - 1, Ck=p.Ck, Nc=p.Nc, Ho=p.Ho, Wo=p.Wo, taps=[9], epi=epi, ksplit=int(ksplit), in_stride=2,
+                           out_stride=1, prec=3, v2=True))
     return fused_act if act_bwd is not None else out
 
 
@@ -1033,16 +941,14 @@ def conv_up2_plan(Ck, Nc, Hi, Wi, N=1):
         return None
     # 8 x 32-cell patches (eight waves, one workgroup per CU) when they fill the chip; else 4 x 32-cell patches (conv_v2_up2r_kernel: four waves, tap-row weight
     # ring, two workgroups per CU) when THOSE do -- the backbone's 128^2 -> 256^2 layer at one image (128 -> 256 workgroups)
-    tiles8 = N * -(-Hi // 8) * -(-Wi // 32) * (Nc // 64)
-    tiles4 = N * -(-Hi // 4) * -(-Wi // 32) * (Nc // 64)
-    if tiles8 >= UP2_MIN_TILES:
+    if _patches(N, Hi, Wi, 8) * (Nc // 64) >= UP2_MIN_TILES:
         rows = 8
-    elif UP2_ROWS4 and tiles4 >= UP2_MIN_TILES:
+    elif UP2_ROWS4 and _patches(N, Hi, Wi, 4) * (Nc // 64) >= UP2_MIN_TILES:
         rows = 4
     else:
         return None
     # ragged: the full (Hi + 1) x (Wi + 1) cell grid in one launch when it still fits one round of workgroups (8 rows: one per CU; 4 rows: two per CU)
-    ragged = N * -(-(Hi + 1) // rows) * -(-(Wi + 1) // 32) * (Nc // 64) <= (512 if rows == 4 else 256)
+    ragged = _patches(N, Hi + 1, Wi + 1, rows) * (Nc // 64) <= (512 if rows == 4 else 256)
     return 1, ragged, rows
 
 
@@ -1079,21 +985,10 @@ def conv_up2(a: SplitImage, w: SplitImage, out, Hc=None, Wc=None, epi=L.EPI_STOR
     for t in range(9):
         p.wtap[t] = t
     p.epi, p.products, p.ksplit, p.patch_rows = epi, int(products), int(ksplit), int(patch_rows)
-    prof = PROFILER
-    if prof is not None and prof.only_config is not None and prof.only_config != UP2_CONFIG:
-        prof = None
-    if prof is not None:
-        if algo_flops is None:
-            algo_flops = 2.0 * ck * nc * n * hi * wi * 9
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-    L.check(L.lib().eg3d_conv2d_up2(C.byref(p), L.stream_ptr()), 'conv2d_up2')
-    if prof is not None:
-        e1.record()
-        prof.records.append(((UP2_CONFIG, PRECISIONS['f16x3']), float(algo_flops), e0, e1))
-        if prof.meta is not None:
-            prof.meta.append(dict(N=n, Hi=hi, Wi=wi, Ck=ck, Nc=nc, Ho=ho, Wo=wo, taps=[4, 2, 2, 1], epi=epi, ksplit=int(ksplit), in_stride=1, out_stride=2,
-                                  prec=3, v2=True, up2=True))
+    _recorded(lambda: L.check(L.lib().eg3d_conv2d_up2(C.byref(p), L.stream_ptr()), 'conv2d_up2'), UP2_CONFIG, PRECISIONS['f16x3'], algo_flops,
+              lambda: 2.0 * ck * nc * n * hi * wi * 9,
+              lambda: dict(N=n, Hi=hi, Wi=wi, Ck=ck, Nc=nc, Ho=ho, Wo=wo, taps=[4, 2, 2, 1], epi=epi, ksplit=int(ksplit), in_stride=1, out_stride=2,
+                           prec=3, v2=True, up2=True))
     return out
 
 
@@ -1132,14 +1027,19 @@ def conv_wgrad(x, g, Ck, Nc, dwp, classes, in_stride=1, out_stride=1, in_scale=N
 WGRAD_V2 = os.environ.get('EG3D_WGRAD_V2', '1') != '0'       # weight gradients of split-image layers on csrc/conv_wgrad_v2.hip
 
 
-def conv_wgrad_v2_ok(gimg, ximg, classes):
-    """Both operands as SplitImages of equal geometry, channel counts multiples of 64, one stride-1 class of 9 (3x3) or 1 taps."""
-    if not (WGRAD_V2 and USE_V2) or gimg is None or ximg is None or len(classes) != 1 or classes[0].ntaps not in (9, 1):
+def conv_wgrad_v2_shapes_ok(gshape, xshape, classes):
+    """Operand images of equal geometry, channel counts multiples of 64, one stride-1 class of 9 (3x3) or 1 taps."""
+    if not (WGRAD_V2 and USE_V2) or len(classes) != 1 or classes[0].ntaps not in (9, 1):
         return False
-    n, co, h, w = gimg.shape
-    n2, ci, h2, w2 = ximg.shape
+    n, co, h, w = gshape
+    n2, ci, h2, w2 = xshape
     c = classes[0]
     return (n, h, w) == (n2, h2, w2) and co % 64 == 0 and ci % 64 == 0 and (c.Ha, c.Wa) == (h, w) and c.out_py == 0 and c.out_px == 0
+
+
+def conv_wgrad_v2_ok(gimg, ximg, classes):
+    """Both operands at hand as SplitImages that conv_wgrad_v2_shapes_ok accepts."""
+    return gimg is not None and ximg is not None and conv_wgrad_v2_shapes_ok(gimg.shape, ximg.shape, classes)
 
 
 WGRAD_SLABS = os.environ.get('EG3D_WGRAD_SLABS', '0') != '0'   # partial weight-gradient tiles stored to slabs and summed in order (no atomics)

@@ -28,7 +28,7 @@ import torch
 
 from . import _lib as L
 from . import hipops as H
-from .fused import _auto_ksplit
+from .conv_plan import _auto_ksplit
 from .torch_utils.ops import bias_act
 
 WGRAD_PRECISION = os.environ.get('EG3D_POSE_WGRAD', 'f16x3')        # weight gradients of the in-loop pose estimator: 'f16x3' | 'f32' (v_mfma_f32_32x32x2_f32)
@@ -96,8 +96,7 @@ def _presplit_plan(Ck, Nc, classes, N, H_, W_):
         return 'ws', None
     if Nc % 64 or not H.USE_V3 or N * H_ * W_ < 1024:
         return None
-    wg4 = N * -(-H_ // 4) * -(-W_ // 32) * (Nc // 64)
-    return 'v3', ((4, 4) if wg4 >= 192 else (2, 8))
+    return 'v3', H.conv_v3_tiling(classes, N, Nc)
 
 
 class _ConvActFn(torch.autograd.Function):

@@ -1,10 +1,11 @@
 """Stand-alone timing of the wave-split pre-split conv (csrc/conv_v3.hip) against what it replaces, on the backbone's under-filled 3x3 layers
 at one image per GPU, forward with the fused epilogue, COLD weights (each launch of a replayed graph reads another copy of the weights: inside
 the step every layer's weight image arrives from HBM / MALL).   python tools/bench_v3.py [n_images]"""
-import sys, math
-sys.path.insert(0, '/root/repo'); sys.path.insert(0, '/root/repo/3dgan-inversion_amd')
+import os, sys, math
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, '3dgan-inversion_amd'))
 import torch
-from inv3d_amd import hipops as H, _lib as L, fused as F
+from inv3d_amd import hipops as H, _lib as L, fused as F, conv_plan as P
 dev = torch.device('cuda')
 NWT = 8
 N = int(sys.argv[1]) if len(sys.argv) > 1 else 1
@@ -47,7 +48,7 @@ for (ci, res, co) in ((512, 32, 512), (512, 64, 512), (256, 128, 256), (128, 256
     amax = torch.zeros(1, device=dev)
     epi = dict(noise=noise, noise_nstride=0, noise_strength=strength, bias=bias, act='lrelu', alpha=0.2, gain=1.4, clamp=-1.0)
     gf = 2.0 * N * res * res * ci * co * 9 / 1e9
-    ks_old = F._auto_ksplit(cls, N, co, ci)
+    ks_old = P._auto_ksplit(cls, N, co, ci)
     z = torch.zeros(N, co, res, res, device=dev).contiguous(memory_format=torch.channels_last)
     aimg = H.split_activation(x, ax, in_scale=s)
 
@@ -100,7 +101,7 @@ for (ci, res, co) in ((512, 32, 512), (512, 64, 256), (256, 128, 128)):
     dx, ds = H.empty_cl(N, ci, res, res, dev), torch.zeros(N, ci, device=dev)
     gf = 2.0 * N * res * res * ci * co * 9 / 1e9
     gfull = H.empty_cl(N, co, 2 * res + 1, 2 * res + 1, dev)
-    ks_old = F._auto_ksplit(cls, N, ci, co)
+    ks_old = P._auto_ksplit(cls, N, ci, co)
     z = torch.zeros(N, ci, res, res, device=dev).contiguous(memory_format=torch.channels_last)
 
     def old(k):
@@ -140,7 +141,7 @@ for (ci, res, co) in ((512, 4, 512), (512, 8, 512), (512, 16, 512), (512, 32, 51
     cls = H.classes_corr(res, res, 3, 3, 1)
     z = torch.zeros(N, co, res, res, device=dev).contiguous(memory_format=torch.channels_last)
     gf = 2.0 * N * res * res * ci * co * 9 / 1e9
-    ks_old = F._auto_ksplit(cls, N, co, ci)
+    ks_old = P._auto_ksplit(cls, N, co, ci)
 
     def old(k):
         H.conv_atomic(x, wfs[k], ci, co, z, cls, in_scale=s, ksplit=ks_old, precision='f16x3', w_pieces=wps[k])

@@ -1,8 +1,58 @@
-"""Every implicit-GEMM conv launch of one eager C2 step, in order: geometry, epilogue, time, algorithmic TFLOP/s (in-situ, HIP events)."""
+"""Every implicit-GEMM conv launch of one eager C2 step, in order: geometry, epilogue, time, algorithmic TFLOP/s (in-situ, HIP events).
+
+    python tools/conv_launch_table.py                  # needs a GPU
+    python tools/conv_launch_table.py --plan [N]       # no GPU: what inv3d_amd/conv_plan.py routes every modulated 3x3 layer of the full-size generator to
+    python tools/conv_launch_table.py --plan --json    # ... as tests/golden/conv_routes.json (N in 1, 2, 8; frozen / trainable weights; f16x3 / f16x1)
+"""
+import json
+import os
 import sys
-sys.path.insert(0, '/root/repo'); sys.path.insert(0, '/root/repo/3dgan-inversion_amd')
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, '3dgan-inversion_amd'))
 import torch
-from inv3d_amd import synthetic as S, hipops as H
+from inv3d_amd import synthetic as S, hipops as H, conv_plan as P
+
+
+def modconv_layers():
+    """(name, Ci, Co, Hi, Wi, up) of every SynthesisLayer of the full-size generator (built on the CPU)."""
+    from inv3d_amd.training.networks_stylegan2 import SynthesisLayer
+    G = S.make_generator(device='cpu')
+    return [(n, m.in_channels, m.out_channels, m.resolution // m.up, m.resolution // m.up, m.up) for n, m in G.named_modules() if isinstance(m, SynthesisLayer)]
+
+
+def plan_json():
+    lines = []
+    for name, ci, co, hi, wi, up in modconv_layers():
+        rows = [f'   "N{n} {"frozen" if frozen else "trainable"} {prec}": {json.dumps(P.describe(n, ci, co, hi, wi, 3, up, prec, frozen), sort_keys=True)}'
+                for n in (1, 2, 8) for frozen in (True, False) for prec in ('f16x3', 'f16x1')]
+        lines.append(f' "{name}": {{\n  "geometry": {json.dumps(dict(Ci=ci, Co=co, Hi=hi, Wi=wi, up=up))},\n  "routes": {{\n' + ',\n'.join(rows) + '\n  }\n }')
+    return '{\n' + ',\n'.join(lines) + '\n}'
+
+
+def plan_table(n):
+    def short(p):
+        if p is None:
+            return '-'
+        extra = [f'rows {p.rows}' if getattr(p, 'rows', 0) else '', f'rows,waves {p.v3}' if getattr(p, 'v3', None) else '',
+                 f'ks {p.ksplit}' if getattr(p, 'ksplit', 1) > 1 else '', 'ragged' if getattr(p, 'ragged', False) else '', '+rgb' if getattr(p, 'rgb_head', False) else '']
+        return ' '.join([str(p.form)] + [e for e in extra if e])
+    print(f'N = {n}, f16x3.  forward / data gradient with frozen weights; [..] where trainable weights differ; weight gradient')
+    print(f'{"layer":30s} {"in":>14} up  {"forward":26s} {"dgrad":26s} wgrad')
+    for name, ci, co, hi, wi, up in modconv_layers():
+        g = (n, ci, co, hi, wi, 3, up, 'f16x3')
+        f, d, ft, dt = P.plan_forward(*g, True), P.plan_dgrad(*g, True), P.plan_forward(*g, False), P.plan_dgrad(*g, False, need_w=True)
+        fs = short(f) + (f' [{short(ft)}]' if ft != f else '')
+        ds = short(d) + (f' [{short(dt)}]' if dt.form != d.form else '')
+        print(f'{name.replace("synthesis.", ""):30s} {hi:4d}x{wi:<4d}x{ci:<4d} {up:2d}  {fs:26s} {ds:26s} {P.plan_wgrad(*g).form}')
+
+
+if '--plan' in sys.argv:
+    if '--json' in sys.argv:
+        print(plan_json())
+    else:
+        plan_table(int(sys.argv[-1]) if sys.argv[-1].isdigit() else 1)
+    sys.exit(0)
+
 from inv3d_amd.inversion import LatentProjector
 dev = torch.device('cuda')
 G = S.make_generator(device=dev); S.load_synthetic_weights(G, seed=0)

@@ -1,10 +1,15 @@
 """Two runs of an optimisation loop from the same state, compared bit for bit (run with EG3D_DETERMINISTIC=1 for the deterministic build;
-with the normal build the runs differ after the first step).  Usage: det_runs.py [c2|c3|phase_b] [steps] [graph|eager]
+with the normal build the runs differ after the first step).  Usage: det_runs.py [c2|c3|phase_b] [steps] [graph|eager] [--save FILE]
+--save FILE: torch.save the final tensors of the first compared run (CPU copies) -- two source trees are compared by comparing their files.
 Prints one JSON line: {"config", "steps", "graph", "deterministic_build", "equal", "max_abs_diff", "misses", "ms_per_step"}."""
 import sys, json, time, copy
 sys.path.insert(0, __import__('os').path.join(__import__('os').path.dirname(__import__('os').path.dirname(__import__('os').path.abspath(__file__))), '3dgan-inversion_amd'))
 import torch
 from inv3d_amd import synthetic as S, _lib as L
+save = None
+if '--save' in sys.argv:
+    save = sys.argv[sys.argv.index('--save') + 1]
+    del sys.argv[sys.argv.index('--save'):sys.argv.index('--save') + 2]
 from inv3d_amd.inversion import LatentProjector, PivotalTuner
 which = sys.argv[1] if len(sys.argv) > 1 else 'c2'
 steps = int(sys.argv[2]) if len(sys.argv) > 2 else 150
@@ -45,6 +50,8 @@ def run():
 
 run()                                  # (captures, caches and the arena reach their steady state)
 a, ms = run(); b, _ = run()
+if save:
+    torch.save([t.cpu() for t in a], save)
 diff = max(float((x.double() - y.double()).abs().max()) for x, y in zip(a, b))
 print(json.dumps(dict(config=which, steps=steps, graph=graph, deterministic_build=bool(L.lib().eg3d_det_enabled()),
                       equal=all(torch.equal(x, y) for x, y in zip(a, b)), max_abs_diff=diff, misses=L.det_misses(), ms_per_step=round(ms, 3))))

@@ -380,6 +380,13 @@ _SIGS = {
     'eg3d_batchnorm_backward': (C.c_int, [C.POINTER(BatchNormParams), C.c_void_p]),
     'eg3d_face_pool': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     'eg3d_sample_decode': (C.c_int, [C.POINTER(RenderParams), C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    'eg3d_pca_moments_slabs': (C.c_int, [C.c_int64, C.c_int]),
+    'eg3d_pca_moments': (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    'eg3d_pca_moments_accumulate': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    'eg3d_pca_covariance': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    'eg3d_sym_eig_workspace': (C.c_int, [C.c_int, C.POINTER(C.c_int64)]),
+    'eg3d_sym_eig': (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_void_p, C.POINTER(C.c_int32), C.c_void_p]),
+    'eg3d_image_grid_u8': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGS)

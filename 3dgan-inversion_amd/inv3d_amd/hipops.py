@@ -1914,3 +1914,106 @@ def batch_norm_train(x, gamma, beta, running_mean=None, running_var=None, num_ba
         return y
     y, save = _BatchNormTrainFn.apply(x, gamma, beta, residual, running_mean, running_var, num_batches_tracked, float(momentum), float(eps), act)
     return (y, save) if return_stats else y
+
+
+# ------------------------------------------------------------------------------------------------- GANSpace: PCA of W, edit grids (csrc/pca.hip)
+PCA_SLAB_ROWS = 256              # EG3D_PCA_SLAB_ROWS: the rows one fp32 sum of pca_moments runs over
+PCA_MAX_DIM = 512
+
+
+class PcaMoments:
+    """Running second moments of row data about `shift`: fp64 device accumulators gram [D,D], sum [D], and the rows seen so far."""
+
+    def __init__(self, shift):
+        D = shift.numel()
+        self.shift = shift
+        self.gram = torch.zeros((D, D), dtype=torch.float64, device=shift.device)
+        self.sum = torch.zeros(D, dtype=torch.float64, device=shift.device)
+        self.n = 0
+
+
+def pca_moments_slabs(S: int, D: int) -> int:
+    """Slabs eg3d_pca_moments splits S rows of D columns into: each slab's sums run in fp32 over at most PCA_SLAB_ROWS rows."""
+    r = L.lib().eg3d_pca_moments_slabs(int(S), int(D))
+    L.check(min(r, 0), 'pca_moments_slabs')
+    return r
+
+
+def pca_moments(x: torch.Tensor, shift: Optional[torch.Tensor], state: Optional[PcaMoments] = None) -> PcaMoments:
+    """Adds the rows of x [S,D] (fp32, D <= 512, unit column stride) to `state` (a new one about `shift` [D] when None; a later chunk's
+    `shift` is ignored: the state keeps its own).  Per-slab exact fp32 products, slabs added in order into fp64: no atomics."""
+    L.require_cuda(x, shift)
+    if x.dim() != 2 or x.dtype != torch.float32 or x.shape[0] < 1 or not 1 <= x.shape[1] <= PCA_MAX_DIM:
+        raise L.Eg3dHipError(f'pca_moments: fp32 rows [S >= 1, 1 <= D <= {PCA_MAX_DIM}], got {tuple(x.shape)} {x.dtype}')
+    if x.stride(1) != 1 or x.stride(0) < x.shape[1]:
+        x = x.contiguous()
+    S, D = x.shape
+    if state is None:
+        if shift is None or shift.numel() != D:
+            raise L.Eg3dHipError(f'pca_moments: the first chunk needs a shift of {D} values')
+        state = PcaMoments(shift.detach().to(torch.float32).reshape(D).contiguous().clone())
+    elif state.shift.numel() != D or state.shift.device != x.device:
+        raise L.Eg3dHipError(f'pca_moments: the state holds {state.shift.numel()} columns on {state.shift.device}, the chunk {D} on {x.device}')
+    slabs = pca_moments_slabs(S, D)
+    part = torch.empty(slabs * (D * D + D), dtype=torch.float32, device=x.device)
+    gp, sp = part[:slabs * D * D], part[slabs * D * D:]
+    lib = L.lib()
+    L.check(lib.eg3d_pca_moments(L.ptr(x), S, D, x.stride(0), L.ptr(state.shift), L.ptr(gp), L.ptr(sp), L.stream_ptr()), 'pca_moments')
+    L.check(lib.eg3d_pca_moments_accumulate(L.ptr(gp), L.ptr(sp), slabs, D, L.ptr(state.gram), L.ptr(state.sum), L.stream_ptr()), 'pca_moments_accumulate')
+    state.n += S
+    return state
+
+
+def pca_covariance(state: PcaMoments):
+    """(cov fp32 [D,D] with ddof 0, bit-symmetric; mean fp32 [D]; rows seen) of everything added to `state`."""
+    if state.n < 1:
+        raise L.Eg3dHipError('pca_covariance: no rows were added')
+    D = state.shift.numel()
+    cov = torch.empty((D, D), dtype=torch.float32, device=state.shift.device)
+    mean = torch.empty(D, dtype=torch.float32, device=state.shift.device)
+    L.check(L.lib().eg3d_pca_covariance(L.ptr(state.gram), L.ptr(state.sum), state.n, D, L.ptr(state.shift), L.ptr(cov), L.ptr(mean), L.stream_ptr()),
+            'pca_covariance')
+    return cov, mean, state.n
+
+
+def sym_eig(a: torch.Tensor, max_sweeps: int = 60, tol: Optional[float] = None):
+    """(evals [n] descending, evecs [n,n] with eigenvector i as row i and its largest-magnitude entry positive, sweeps, converged) of the
+    symmetric fp32 matrix a [n,n], n <= 512 (eg3d_sym_eig: parallel-ordered Jacobi, one launch per round).  Synchronises once per sweep: not
+    capturable.  Reaching max_sweeps is reported (converged False, outputs still written), not raised.  tol None: 8 * 2^-23."""
+    L.require_cuda(a)
+    if a.dim() != 2 or a.shape[0] != a.shape[1] or a.dtype != torch.float32 or not 1 <= a.shape[0] <= PCA_MAX_DIM:
+        raise L.Eg3dHipError(f'sym_eig: a square fp32 matrix of side 1..{PCA_MAX_DIM}, got {tuple(a.shape)} {a.dtype}')
+    if torch.cuda.is_current_stream_capturing():
+        raise L.Eg3dHipError('sym_eig reads its convergence flag back every sweep: it cannot be captured into a graph')
+    a = a.contiguous()
+    n = a.shape[0]
+    nbytes = C.c_int64(0)
+    lib = L.lib()
+    L.check(lib.eg3d_sym_eig_workspace(n, C.byref(nbytes)), 'sym_eig_workspace')
+    ws = torch.empty(nbytes.value, dtype=torch.uint8, device=a.device)
+    evals = torch.empty(n, dtype=torch.float32, device=a.device)
+    evecs = torch.empty((n, n), dtype=torch.float32, device=a.device)
+    info = (C.c_int32 * 2)(0, 0)
+    L.check(lib.eg3d_sym_eig(L.ptr(a), n, L.ptr(evals), L.ptr(evecs), int(max_sweeps), float(tol or 0.0), L.ptr(ws), info, L.stream_ptr()), 'sym_eig')
+    return evals, evecs, int(info[0]), bool(info[1])
+
+
+def image_grid_size(N: int, H: int, W: int, nrow: int, padding: int = 2):
+    """(Ht, Wt) of torchvision.utils.make_grid for N images of H x W."""
+    xmaps = min(int(nrow), N)
+    ymaps = -(-N // xmaps)
+    return ymaps * (H + padding) + padding, xmaps * (W + padding) + padding
+
+
+def image_grid_u8(img: torch.Tensor, nrow: int, padding: int = 2, pad_value: int = 0) -> torch.Tensor:
+    """uint8 [Ht,Wt,3]: the fp32 [N,3,H,W] batch as uint8(clamp(x * 127.5 + 128, 0, 255)), tiled HWC the way torchvision.utils.make_grid(nrow,
+    padding, pad_value) tiles (eg3d_image_grid_u8); padding=0 is a plain tiling, nrow=1 with padding=0 a column of images.  One launch."""
+    L.require_cuda(img)
+    if img.dim() != 4 or img.shape[1] != 3 or img.dtype != torch.float32 or img.shape[0] < 1:
+        raise L.Eg3dHipError(f'image_grid_u8: fp32 [N >= 1,3,H,W], got {tuple(img.shape)} {img.dtype}')
+    img = img.contiguous()
+    N, _, Hh, Ww = img.shape
+    Ht, Wt = image_grid_size(N, Hh, Ww, nrow, padding)
+    out = torch.empty((Ht, Wt, 3), dtype=torch.uint8, device=img.device)
+    L.check(L.lib().eg3d_image_grid_u8(L.ptr(img), N, Hh, Ww, int(nrow), int(padding), int(pad_value), L.ptr(out), L.stream_ptr()), 'image_grid_u8')
+    return out

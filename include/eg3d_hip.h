@@ -1100,6 +1100,45 @@ int eg3d_batchnorm_query_workspace(int64_t M, int32_t C, int64_t* workspace_byte
 int eg3d_batchnorm_forward(const eg3d_batchnorm_params* p, void* stream);
 int eg3d_batchnorm_backward(const eg3d_batchnorm_params* p, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * GANSpace latent editing (ganspace/pca_anlaysis.py, estimator.py, run_ganspace.py; csrc/pca.hip): a PCA of W on the device and the
+ *   uint8 grids of the edits.  Nothing here accumulates with atomics: both builds of the library give the same bits.
+ *
+ * Second moments of row data x [S,D] fp32 (leading dimension ldx >= D), 1 <= D <= 512, S >= 1, about a caller-chosen shift [D] (W has a mean
+ *   that is large against its spread: the host passes the first chunk's column mean, which is what makes fp32 products viable):
+ *     eg3d_pca_moments_slabs       host only: slabs = ceil(S / EG3D_PCA_SLAB_ROWS) -- the rows one fp32 sum runs over -- or a negative status
+ *     eg3d_pca_moments             one launch: gram_part [slabs][D][D] = per-slab (x-shift)^T (x-shift), the elements i <= j ONLY (the rest is
+ *                                  not written), sum_part [slabs][D] = per-slab column sums of (x-shift).  Exact fp32 products and sums
+ *                                  (v_mfma_f32_32x32x2_f32).
+ *     eg3d_pca_moments_accumulate  gram [D][D] (full, symmetric) and sum [D], fp64, += the slabs in slab order.  The caller zeroes them before
+ *                                  the first chunk; they persist across chunks.
+ *     eg3d_pca_covariance          cov [D][D] fp32 = gram / S_total - d d^T with d = sum / S_total (ddof 0, computed in fp64 from the upper
+ *                                  triangle and mirrored: exactly symmetric), mean [D] = shift + d. */
+#define EG3D_PCA_SLAB_ROWS 256
+int eg3d_pca_moments_slabs(int64_t S, int D);
+int eg3d_pca_moments(const float* x, int64_t S, int D, int64_t ldx, const float* shift, float* gram_part, float* sum_part, void* stream);
+int eg3d_pca_moments_accumulate(const float* gram_part, const float* sum_part, int slabs, int D, double* gram, double* sum, void* stream);
+int eg3d_pca_covariance(const double* gram, const double* sum, int64_t S_total, int D, const float* shift, float* cov, float* mean, void* stream);
+
+/* Eigen-decomposition of a symmetric fp32 matrix a [n][n], 1 <= n <= 512: one-sided (Hestenes) Jacobi, round-robin ordering; the n/2 disjoint
+ *   rotations of a round are one launch (one wave per pair), so a sweep is n - 1 (n even) or n (n odd, one bye per round) launches plus two.
+ *   A pair is rotated when |a_p.a_q| > tol |a_p||a_q| (tol <= 0: 8 * 2^-23) and left alone when its smaller squared norm is below
+ *   (n 2^-24)^2 times the largest of the sweep (columns of the numerical null space).  After every sweep the largest criterion seen is read
+ *   back: the function SYNCHRONISES the stream once per sweep and cannot be captured into a graph.  It stops after the first sweep that
+ *   rotated nothing (converged) or after max_sweeps (>= 1) sweeps, whichever comes first, and reports which in info (HOST memory):
+ *   info[0] = sweeps run, info[1] = 1 converged / 0 not.  Either way the outputs are written: evals [n] descending (Rayleigh quotients), evecs
+ *   [n][n] with eigenvector i as ROW i, unit length, signed so that its largest-magnitude entry (the first of equals) is positive -- what
+ *   sklearn's svd_flip gives the reference's estimator.  Only the symmetric part's upper/lower agreement is assumed, not checked.
+ *   workspace: eg3d_sym_eig_workspace bytes of device memory, 16-byte aligned.  Bit-identical from run to run and between the builds. */
+int eg3d_sym_eig_workspace(int n, int64_t* bytes);
+int eg3d_sym_eig(const float* a, int n, float* evals, float* evecs, int max_sweeps, float tol, void* workspace, int32_t* info, void* stream);
+
+/* img [N,3,H,W] fp32 -> out uint8 [Ht][Wt][3], every value uint8(clamp(x * 127.5 + 128, 0, 255)) (truncated; the reference's
+ *   (img * 127.5 + 128).clamp(0, 255).to(torch.uint8)), tiled as torchvision.utils.make_grid(nrow, padding, pad_value) tiles: xmaps = min(nrow, N),
+ *   ymaps = ceil(N / xmaps), Ht = ymaps (H + padding) + padding, Wt = xmaps (W + padding) + padding, image k at cell (k / xmaps, k % xmaps)
+ *   offset by padding; borders and unused cells = pad_value (0..255).  padding = 0: the plain tiling of gen_videos.layout_grid.  NaN undefined. */
+int eg3d_image_grid_u8(const float* img, int N, int H, int W, int nrow, int padding, int pad_value, uint8_t* out, void* stream);
+
 /* Measurement aid (bench.py): a register-only v_mfma_f32_32x32x16_f16 loop on caller-supplied fp16 data -- what the matrix pipe sustains on
  * this chip at its current power / clock state, timed inside the benchmark run.  in: 4096 x 8 fp16 (64 KiB); out: blocks x 256 floats;
  * executes blocks x 4 waves x iters x 24 MFMAs of 32 x 32 x 16.  No reference counterpart. */

@@ -237,8 +237,8 @@ __global__ void __launch_bounds__(256 * KH, KH == 1 ? 2 : 1) conv_v2_kernel(cons
                 for (int r = 0; r < 16; ++r) acc[i][j][r] += xch[((i * 2 + j) * 16 + r) * 256];
     }
 
-    if constexpr (KH == 2) v2_epilogue<ATOMIC, RPW, false, RGB>(p, acc, Ha, Wa, cl.out_py, cl.out_px, n, y0, x0, n0, smem, 1.f / (*p.a_scale * *p.w_scale), 5, 4);
-    else v2_epilogue<ATOMIC, RPW, false, RGB>(p, acc, Ha, Wa, cl.out_py, cl.out_px, n, y0, x0, n0, smem, 1.f / (*p.a_scale * *p.w_scale));
+    if constexpr (KH == 2) v2_epilogue<ATOMIC, RPW, RGB>(p, acc, Ha, Wa, cl.out_py, cl.out_px, n, y0, x0, n0, smem, 1.f / (*p.a_scale * *p.w_scale), 4);
+    else v2_epilogue<ATOMIC, RPW, RGB>(p, acc, Ha, Wa, cl.out_py, cl.out_px, n, y0, x0, n0, smem, 1.f / (*p.a_scale * *p.w_scale));
 }
 
 // ---- operand preparation (split8 / range_mul: conv_v2_common.h) ------------------------------------------------------------

@@ -825,8 +825,7 @@ int launch_decode(const DecodeArgs& a, bool bwd, hipStream_t st) {
         return EG3D_ERR_UNSUPPORTED;      // 32-bit row and texel-offset arithmetic in the kernels
     const int64_t ntiles = (a.M + 31) / 32;
     const int blocks = (int)std::min<int64_t>((ntiles + 3) / 4, 256 * (bwd ? DEC_GRID_BWD : DEC_GRID_FWD));     // persistent: resident blocks per CU x 256 CUs
-    static const bool gc_split = [] { const char* e = getenv("EG3D_GC_SPLIT"); return e ? atoi(e) != 0 : true; }();
-    if (bwd && gc_split && a.gc_rows != nullptr && a.df_rows != nullptr && a.pos_stride == 4) {
+    if (bwd && a.gc_rows != nullptr && a.df_rows != nullptr && a.pos_stride == 4) {
         // position gradient from the df rows this launch writes, in a high-occupancy pass of its own (gather_grad_rows_kernel)
         DecodeArgs b = a;
         b.gc_rows = nullptr;

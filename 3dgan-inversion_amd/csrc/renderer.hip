@@ -707,10 +707,12 @@ __global__ void __launch_bounds__(256) render_coord_reduce_kernel(const float4* 
 // =========================================================================================================
 // Tile-binned scatter of the per-sample feature gradients into the tri-plane gradient.
 //   A float-atomic scatter costs 12 corners x 32 channels = 384 atomics per sample (604 M per backward at the FFHQ
-//   config; measured 30 ms on MI355X = the atomic rate of the memory fabric).  Instead: (1) count the (sample, plane)
-//   pairs per 16x16-texel tile, (2) exclusive scan, (3) counting-sort the pair ids by tile, (4) one block per tile
-//   accumulates its pairs into a 17x17x32 LDS tile with conflict-free ds_add_f32 (lane = channel) and flushes the tile
-//   once.  Global atomics drop to ~9 K per tile.
+//   config; measured 30 ms on MI355X = the atomic rate of the memory fabric).  Instead the (sample, plane) pairs are
+//   counting-sorted by (16x16-texel tile, upper texel row) -- count, exclusive scan, place -- and every (tile, row)
+//   list is accumulated by one wave as a small GEMM on the matrix cores: a pair adds  wy_half * wx_x * g[c]  to
+//   (half, column x, channel c) for half in {upper, lower} and x in {lx, lx+1}, i.e.  Acc[(half,x)][c] += sum_e C[(half,x)][e] * G[e][c]
+//   with a 32 x E coefficient matrix (two rows x 16 columns) that has four non-zeros per pair.  Global atomics drop to
+//   one per touched (texel, channel) of a list.  The earlier generations of this scatter and their measurements: DESIGN_HISTORY.md 3.2.
 // =========================================================================================================
 constexpr int TS = 15;          // interior texels per tile side; a tile's accumulator covers TS + 1 = 16 rows / columns (the last one is shared with the neighbour)
 
@@ -730,423 +732,20 @@ __device__ __forceinline__ int tile_of(int x0, int y0, int ntx, int nty) {
     return (ty < nty ? ty : nty - 1) * ntx + (tx < ntx ? tx : ntx - 1);
 }
 
-// pass 0: count; pass 1: place.  One thread per (sample row, plane).  Bin counters are pre-aggregated in an LDS histogram so
-// that the global counters see one atomic per (block, touched bin) instead of one per pair (the pairs of neighbouring rows
-// fall into the same few tiles: same-address atomics would serialise).
-constexpr int BIN_ITEMS = 16;           // pairs per thread (block-strided).  4 per thread took 87 + 99 us for the two passes, 16: 36 + 41 -- the per-block flush
-                                        // (an LDS sweep + global atomics for every touched bin) is the cost, not the per-pair work; 32 / 64 are slower again
-template <int PASS>
-__global__ void __launch_bounds__(256) scatter_bin_kernel(const float4* __restrict__ pos, int64_t S, int64_t rows_per_image, float cs, int Hp, int Wp,
-                                                          int ntx, int nty, int nb, int* __restrict__ counts, const int* __restrict__ offsets,
-                                                          int* __restrict__ fill, int* __restrict__ ids) {
-    extern __shared__ int hist[];       // [nb] local counts, then (pass 1) [nb] reserved bases
-    for (int i = threadIdx.x; i < nb; i += 256) hist[i] = 0;
-    __syncthreads();
-    int bin[BIN_ITEMS], lrank[BIN_ITEMS], rowi[BIN_ITEMS];
-    const int64_t base = (int64_t)blockIdx.x * 256 * BIN_ITEMS + threadIdx.x;          // consecutive lanes -> consecutive (row, plane) pairs
-#pragma unroll
-    for (int k = 0; k < BIN_ITEMS; ++k) {
-        bin[k] = -1;
-        const int64_t i = base + (int64_t)k * 256;
-        if (i >= S * 3) continue;
-        const int64_t row = i / 3;
-        const int pl = (int)(i - row * 3);
-        const float4 ps = pos[row];
-        if (isnan(ps.x)) continue;
-        int x0, y0; float wx1, wy1;
-        if (!plane_cell(ps, pl, cs, Hp, Wp, x0, y0, wx1, wy1)) continue;
-        const int n = (int)(row / rows_per_image);
-        bin[k] = (n * 3 + pl) * (ntx * nty) + tile_of(x0, y0, ntx, nty);
-        rowi[k] = (int)row;
-        lrank[k] = atomicAdd(&hist[bin[k]], 1);
-    }
-    __syncthreads();
-    if constexpr (PASS == 0) {
-        for (int i = threadIdx.x; i < nb; i += 256) { int c = hist[i]; if (c) atomicAdd(counts + i, c); }
-    } else {
-        int* basep = hist + nb;
-        for (int i = threadIdx.x; i < nb; i += 256) { int c = hist[i]; basep[i] = c ? offsets[i] + atomicAdd(fill + i, c) : 0; }
-        __syncthreads();
-#pragma unroll
-        for (int k = 0; k < BIN_ITEMS; ++k)
-            if (bin[k] >= 0) {
-                if (PASS == 1) {
-                    ids[basep[bin[k]] + lrank[k]] = rowi[k] << 2;       // row id (the plane is implied by the bin)
-                } else {            // PASS 2: the whole pair record, so that the accumulate pass streams it (no id -> position gather there)
-                    const int ntile = ntx * nty, t = bin[k] % ntile, pl = (bin[k] / ntile) % 3;
-                    int x0, y0; float wx1, wy1;
-                    plane_cell(pos[rowi[k]], pl, cs, Hp, Wp, x0, y0, wx1, wy1);
-                    const int lx = x0 - (t % ntx) * TS, ly = y0 - (t / ntx) * TS;                  // in [-1, TS-1]
-                    reinterpret_cast<float4*>(ids)[basep[bin[k]] + lrank[k]] =
-                        make_float4(__int_as_float(rowi[k]), __int_as_float(((ly + 1) << 16) | (lx + 1)), wx1, wy1);
-                }
-            }
-    }
-}
-
-constexpr int CHUNK = 4096;             // pairs per accumulate block
-
-// single block: exclusive scan of `n` counts -> offsets[n+1], and of ceil(count/CHUNK) -> chunk_offsets[n+1]
-__global__ void __launch_bounds__(1024) scatter_scan_kernel(const int* __restrict__ counts, int* __restrict__ offsets, int* __restrict__ chunk_offsets, int n) {
-    __shared__ int part[1024], partc[1024];
-    const int t = threadIdx.x;
-    const int per = (n + 1023) / 1024;
-    int sum = 0, sumc = 0;
-    for (int k = 0; k < per; ++k) { int idx = t * per + k; if (idx < n) { int c = counts[idx]; sum += c; sumc += (c + CHUNK - 1) / CHUNK; } }
-    part[t] = sum; partc[t] = sumc;
-    __syncthreads();
-    for (int off = 1; off < 1024; off <<= 1) {
-        int v = t >= off ? part[t - off] : 0, vc = t >= off ? partc[t - off] : 0;
-        __syncthreads();
-        part[t] += v; partc[t] += vc;
-        __syncthreads();
-    }
-    int run = part[t] - sum, runc = partc[t] - sumc;
-    for (int k = 0; k < per; ++k) {
-        int idx = t * per + k;
-        if (idx < n) { int c = counts[idx]; offsets[idx] = run; if (chunk_offsets) chunk_offsets[idx] = runc; run += c; runc += (c + CHUNK - 1) / CHUNK; }
-    }
-    if (t == 1023) { offsets[n] = part[1023]; if (chunk_offsets) chunk_offsets[n] = partc[1023]; }
-}
-
-// One block per (bin, chunk of <= CHUNK pairs): the accumulation of a tile-row pair is a small GEMM on the fp32 matrix cores.
-//   * wave w owns the pairs whose upper texel row is tile row w - 1 (list w; each pair is in exactly one list; list 0 = the pairs above
-//     the first row, image border only).  A pair adds  wy_half * wx_x * g[c]  to (half, column x, channel c) for half in {upper, lower}
-//     and x in {lx, lx+1}:  Acc[(half,x)][c] += sum_e C[(half,x)][e] * G[e][c]  with a 32 x E coefficient matrix (two rows x 16 columns)
-//     that has four non-zeros per pair.  v_mfma_f32_32x32x2_f32 takes two pairs per instruction: lane (m, k) builds C[m][e_k] from the
-//     pair record, lane (c, k) supplies g[e_k][c]; exact fp32 products and accumulation.  No read-modify-write chain, no atomics, no
-//     dynamically indexed registers in the loop: per two pairs three LDS reads, ~10 VALU and one MFMA.
-//   * the chunk is streamed in batches of 256 pairs: gradient rows + (cell, weights) records staged in LDS, bucketed by tile row;
-//   * at the end the 16 row pairs are combined in the LDS tile (every tile row has exactly one "lower" and one "upper" owner) and the
-//     16 x 16 x 32 tile is flushed with one atomic per touched cell channel.
-// History of this scatter on MI355X (1.57 M samples x 3 planes x 4 corners x 32 channels): global float atomics 30 ms, LDS float
-// atomics 4.0 ms (~0.3 lane-op/clk/CU), one-thread-per-cell owner-computes 1.7 ms, half-wave row owner with LDS read-modify-write
-// 0.82 ms (a chain of ~5 dependent LDS round trips per pair and row), register accumulators selected by a scalar switch 0.48 ms /
-// by indexed-VGPR moves 0.40 ms (0.14 ms of it the row gather), this form: see DESIGN.md.
-constexpr int ACC_THREADS = 1024;
-constexpr int ACC_BATCH = 256;
 constexpr int TROWS = TS + 1;
-static_assert(TROWS == 16 && ACC_THREADS == 64 * TROWS, "one wave per list, two rows x 16 columns = the 32 rows of the MFMA tile");
+static_assert(TROWS == 16, "a list's two texel rows x 16 columns = the 32 rows of the MFMA tile");
 typedef float acc16_t __attribute__((ext_vector_type(16)));
 
-__global__ void __launch_bounds__(ACC_THREADS) scatter_accum_kernel(const float* __restrict__ df, const float4* __restrict__ pos,
-                                                                    const int* __restrict__ offsets, const int* __restrict__ chunk_offsets,
-                                                                    const int* __restrict__ ids, float* __restrict__ d_planes, float cs, int Hp, int Wp,
-                                                                    int ldp, int ntx, int nty, int nb) {
-    constexpr int STAGE_FLOATS = ACC_BATCH * FC + ACC_BATCH * 4;          // gradient rows + pair records
-    constexpr int TILE_FLOATS = TROWS * TROWS * FC;
-    __shared__ __attribute__((aligned(16))) float sbuf[STAGE_FLOATS > TILE_FLOATS ? STAGE_FLOATS : TILE_FLOATS];
-    __shared__ int cnt[TROWS];                                           // list k holds the pairs with ly == k - 1
-    __shared__ unsigned short lists[TROWS * ACC_BATCH];
-    __shared__ int sbin;
-    float* dfb = sbuf;
-    float4* meta = reinterpret_cast<float4*>(sbuf + ACC_BATCH * FC);     // (lx, ly) as int bits, wx1, wy1
-    float* tile = sbuf;                                                  // after the last batch
-    const int tid = threadIdx.x;
-    if (tid == 0) {
-        int lo = 0, hi = nb;
-        const int me = blockIdx.x;
-        if (me >= chunk_offsets[nb]) lo = -1;
-        else while (hi - lo > 1) { int mid = (lo + hi) >> 1; if (chunk_offsets[mid] <= me) lo = mid; else hi = mid; }
-        sbin = lo;
-    }
-    if (tid < TROWS) cnt[tid] = 0;
-    __syncthreads();
-    const int bin = sbin;
-    if (bin < 0) return;
-    const int chunk = blockIdx.x - chunk_offsets[bin];
-    const int beg = offsets[bin] + chunk * CHUNK;
-    const int end = min(offsets[bin + 1], beg + CHUNK);
-    const int ntile = ntx * nty;
-    const int n = bin / (3 * ntile);
-    const int pl = (bin / ntile) % 3;
-    const int t = bin % ntile;
-    const int ty0 = (t / ntx) * TS, tx0 = (t % ntx) * TS;
-    const int wave = tid >> 6, lane = tid & 63, c = lane & 31, kk = lane >> 5;
-    const int mx = c & 15, mhalf = c >> 4;                               // this lane's row of the coefficient matrix: (half, column)
-
-    acc16_t acc;
-#pragma unroll
-    for (int i = 0; i < 16; ++i) acc[i] = 0.f;
-
-    // software pipeline: the (id -> position, id -> gradient row) loads of batch b+1 are in flight while batch b is accumulated
-    static_assert(ACC_BATCH * (FC / 4) == 2 * ACC_THREADS, "two float4 of the gradient rows per thread");
-    float4 r_meta = make_float4(0, 0, 0, 0), r_df0, r_df1;
-    int r_ly = 0;
-    // (batches are 256 CONSECUTIVE pairs of the chunk: taking every nbat-th pair instead, or placing the pairs of a bin in a pseudo-random
-    //  order, evens out the 16 lists further -- the largest list of a batch holds ~30 of 256 pairs as it is -- but was measured slower,
-    //  426 / 608 vs 389 us: the gather of the 128-byte gradient rows loses its locality)
-    auto pair_at = [&](int b0, int i) { return b0 + i; };
-    auto count_of = [&](int b0) { return min(ACC_BATCH, end - b0); };
-    auto fetch = [&](int b0) {
-        const int nbatch = count_of(b0);
-        if (tid < nbatch) {
-            const int row = ids[pair_at(b0, tid)] >> 2;
-            int x0, y0; float wx1, wy1;
-            plane_cell(pos[row], pl, cs, Hp, Wp, x0, y0, wx1, wy1);
-            r_ly = y0 - ty0;                                             // in [-1, TS-1]
-            r_meta = make_float4(__int_as_float(x0 - tx0), __int_as_float(r_ly), wx1, wy1);
-        }
-        const int j0 = tid >> 3, q = tid & 7;                           // rows j0 and j0 + 128
-        r_df0 = j0 < nbatch ? reinterpret_cast<const float4*>(df + (int64_t)(ids[pair_at(b0, j0)] >> 2) * FC)[q] : make_float4(0, 0, 0, 0);
-        r_df1 = j0 + 128 < nbatch ? reinterpret_cast<const float4*>(df + (int64_t)(ids[pair_at(b0, j0 + 128)] >> 2) * FC)[q] : make_float4(0, 0, 0, 0);
-    };
-    auto commit = [&](int b0) {
-        const int nbatch = count_of(b0);
-        if (tid < nbatch) {
-            meta[tid] = r_meta;
-            const int k = r_ly + 1;
-            lists[k * ACC_BATCH + atomicAdd(&cnt[k], 1)] = (unsigned short)tid;
-        }
-        reinterpret_cast<float4*>(dfb)[tid] = r_df0;
-        reinterpret_cast<float4*>(dfb)[tid + ACC_THREADS] = r_df1;
-    };
-    if (beg < end) { fetch(beg); commit(beg); }
-    __syncthreads();
-    for (int b0 = beg; b0 < end; b0 += ACC_BATCH) {
-        const bool more = b0 + ACC_BATCH < end;
-        if (more) fetch(b0 + ACC_BATCH);
-        {
-            const int m = cnt[wave];
-            const unsigned short* lst = lists + wave * ACC_BATCH;
-            // lanes 0-31 take pair e, lanes 32-63 pair e + 1; four MFMA steps per trip with all of their LDS reads issued up front (the
-            // list is a pointer chase: entry -> record -> gradient row; unpipelined it costs ~5x the MFMA time when one wave holds a
-            // whole batch, which happens: consecutive samples of a ray fall into the same texel row)
-            for (int e = 0; e < m; e += 8) {
-                int j[4];
-                float4 mt[4];
-                float g[4];
-#pragma unroll
-                for (int q = 0; q < 4; ++q) j[q] = lst[min(e + 2 * q + kk, ACC_BATCH - 1)] & (ACC_BATCH - 1);      // stale entries past m: masked below
-#pragma unroll
-                for (int q = 0; q < 4; ++q) { mt[q] = meta[j[q]]; g[q] = dfb[j[q] * FC + c]; }
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    const bool live = e + 2 * q + kk < m;
-                    const int lx = __float_as_int(mt[q].x);
-                    const float wx = mx == lx ? 1.f - mt[q].z : (mx == lx + 1 ? mt[q].z : 0.f);
-                    const float wy = mhalf ? mt[q].w : 1.f - mt[q].w;
-                    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(live ? wx * wy : 0.f, live ? g[q] : 0.f, acc, 0, 0, 0);
-                }
-            }
-        }
-        __syncthreads();
-        if (tid < TROWS) cnt[tid] = 0;
-        __syncthreads();
-        if (more) commit(b0 + ACC_BATCH);
-        __syncthreads();
-    }
-    // Combine the row pairs in the LDS tile.  Accumulator element r of a lane is coefficient row m = (r&3) + 8 (r>>2) + 4 (lane>>5), i.e.
-    // (half, column) = (m >> 4, m & 15), for channel lane & 31.  List `wave` covers tile rows wave - 1 (upper) and wave (lower).
-    // Lower halves first (rows 0..15, one owner each: plain stores), then the upper halves (rows 0..14: one read-modify-write owner each).
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-        const int m = (r & 3) + 8 * (r >> 2) + 4 * kk;
-        if (m >= 16) tile[(wave * TROWS + (m & 15)) * FC + c] = acc[r];
-    }
-    __syncthreads();
-    if (wave >= 1) {
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int m = (r & 3) + 8 * (r >> 2) + 4 * kk;
-            if (m < 16) tile[((wave - 1) * TROWS + m) * FC + c] += acc[r];
-        }
-    }
-    __syncthreads();
-    for (int i = tid; i < TILE_FLOATS; i += ACC_THREADS) {
-        const float v = tile[i];
-        if (v != 0.f) {
-            const int cell = i / FC, ch = i - cell * FC;
-            const int yy = ty0 + cell / TROWS, xx = tx0 + cell % TROWS;
-            if (yy < Hp && xx < Wp) eg3d_acc(d_planes + (int64_t)n * Hp * Wp * ldp + ((int64_t)yy * Wp + xx) * ldp + pl * FC + ch, v);
-        }
-    }
-}
-
-// ---- the same accumulation with every global -> LDS movement done by LDS-DMA, two batches ahead ---------------------------------------
-// scatter_accum_kernel above has ONE batch of gradient rows in flight per block (in registers) behind a dependent chain
-// ids -> (position, gradient row): 70 VGPRs x 16 waves = one block per CU, MfmaUtil 18 %, 2.3 TB/s of 128-byte row gathers.  Here
-//   * the binning pass writes 16-byte pair records (row, cell, weights) in list order: the record stream of a chunk is contiguous and
-//     goes to LDS with one dword-DMA instruction per wave and batch, three batches ahead (M);
-//   * the gradient rows of batch b+2 are gathered by two 16-byte-DMA instructions per wave (eight lanes per 128-byte row, row ids read
-//     from the records of batch b+2 in LDS) while batch b is accumulated (R): two batches of rows in flight per block, no registers;
-//   * issue order per iteration is M(b+3), R(b+2), so `s_waitcnt vmcnt(2)` at the top of iteration b = "R(b) and M(b+2) have landed";
-//   * WAVES x 64 threads, 16 / WAVES texel-row lists per wave; with 8 waves and 128-pair batches 2 blocks share a CU.
-__device__ __forceinline__ void glds_b32(__amdgpu_buffer_rsrc_t rs, unsigned lds_byte, unsigned voff) {
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (__attribute__((address_space(3))) void*)(uintptr_t)lds_byte, 4, voff, 0, 0, 0);
-}
-__device__ __forceinline__ void glds_b128(__amdgpu_buffer_rsrc_t rs, unsigned lds_byte, unsigned voff) {
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (__attribute__((address_space(3))) void*)(uintptr_t)lds_byte, 16, voff, 0, 0, 0);
-}
-
-// workgroup barrier without the fence of __syncthreads() (that fence waits for every outstanding LDS-DMA: vmcnt(0)); LDS writes of this
-// wave are complete (lgkmcnt) before it arrives
-__device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-// LDS atomic add by address (the compiler orders atomicAdd() on __shared__ behind pending LDS-DMA with vmcnt(0))
-__device__ __forceinline__ int lds_add_rtn(unsigned lds_byte, int v) {
-    int old;
-    asm volatile("ds_add_rtn_u32 %0, %1, %2\n\ts_waitcnt lgkmcnt(0)" : "=v"(old) : "v"(lds_byte), "v"(v) : "memory");
-    return old;
-}
-
-template <int WAVES, int BATCH>
-__global__ void __launch_bounds__(WAVES * 64) scatter_accum2_kernel(const float* __restrict__ df, int64_t S, const int* __restrict__ offsets,
-                                                                     const int* __restrict__ chunk_offsets, const float4* __restrict__ recs, int64_t nrec,
-                                                                     float* __restrict__ d_planes, int Hp, int Wp, int ldp, int ntx, int nty, int nb) {
-    constexpr int NT = WAVES * 64;
-    constexpr int LPW = TROWS / WAVES;                    // lists (upper texel rows) per wave
-    constexpr int NRB = 3, NMB = 4;                       // row / record buffers in flight
-    constexpr int ROWB = BATCH * FC * 4, RECB = BATCH * 16;
-    static_assert(TROWS % WAVES == 0 && BATCH * 16 == NT * 4 && BATCH * FC * 4 == NT * 2 * 16, "one record dword and two row quads per thread and batch");
-    constexpr int TILE_FLOATS = TROWS * TROWS * FC;
-    static_assert(NRB * ROWB >= TILE_FLOATS * 4, "the flush tile reuses the row buffers");
-    __shared__ __attribute__((aligned(16))) char sm[NRB * ROWB + NMB * RECB];
-    __shared__ int cnt[2][TROWS];
-    __shared__ unsigned short lists[TROWS * BATCH];
-    __shared__ int sbin;
-    float* tile = reinterpret_cast<float*>(sm);
-    const unsigned lds0 = (unsigned)(uintptr_t)sm;
-    const int tid = threadIdx.x;
-    if (tid == 0) {
-        int lo = 0, hi = nb;
-        const int me = blockIdx.x;
-        if (me >= chunk_offsets[nb]) lo = -1;
-        else while (hi - lo > 1) { int mid = (lo + hi) >> 1; if (chunk_offsets[mid] <= me) lo = mid; else hi = mid; }
-        sbin = lo;
-    }
-    if (tid < 2 * TROWS) (&cnt[0][0])[tid] = 0;
-    __syncthreads();
-    const int bin = sbin;
-    if (bin < 0) return;
-    const int chunk = blockIdx.x - chunk_offsets[bin];
-    const int beg = offsets[bin] + chunk * CHUNK;
-    const int end = min(offsets[bin + 1], beg + CHUNK);
-    const int ntile = ntx * nty;
-    const int n = bin / (3 * ntile);
-    const int pl = (bin / ntile) % 3;
-    const int t = bin % ntile;
-    const int ty0 = (t / ntx) * TS, tx0 = (t % ntx) * TS;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63, c = lane & 31, kk = lane >> 5;
-    const int mx = c & 15, mhalf = c >> 4;                               // this lane's row of the coefficient matrix: (half, column)
-    const int nbat = (end - beg + BATCH - 1) / BATCH;
-
-    const __amdgpu_buffer_rsrc_t rrs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float4*>(recs), 0, (int)(nrec * 16), 0x00020000);
-    const __amdgpu_buffer_rsrc_t drs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(df), 0, (int)(S * FC * 4), 0x00020000);
-    constexpr unsigned OOB = 0xfffffff0u;
-    // M(b): thread tid moves dword tid of the batch's record stream; R(b): quad q of rows j0 and j0 + BATCH / 2
-    auto issue_M = [&](int b) {
-        const int i = beg + b * BATCH + (tid >> 2);
-        glds_b32(rrs, lds0 + NRB * ROWB + (b % NMB) * RECB + wave * 256, (b < nbat && i < end) ? (unsigned)(i * 16 + (tid & 3) * 4) : OOB);
-    };
-    auto issue_R = [&](int b) {
-        const float4* mb = reinterpret_cast<const float4*>(sm + NRB * ROWB + (b % NMB) * RECB);
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-            const int j = h * (BATCH / 2) + (tid >> 3);
-            const bool ok = b < nbat && beg + b * BATCH + j < end;
-            const unsigned row = (unsigned)__float_as_int(mb[j].x);
-            glds_b128(drs, lds0 + (b % NRB) * ROWB + h * (ROWB / 2) + wave * 1024, ok ? row * (FC * 4) + (tid & 7) * 16 : OOB);
-        }
-    };
-
-    acc16_t acc[LPW];
-#pragma unroll
-    for (int l = 0; l < LPW; ++l)
-#pragma unroll
-        for (int i = 0; i < 16; ++i) acc[l][i] = 0.f;
-
-    // prologue -> outstanding at the top of iteration 0: M(2), R(1) x 2 (everything older has landed)
-    issue_M(0); issue_M(1);
-    asm volatile("s_waitcnt vmcnt(1)" ::: "memory");
-    lds_barrier();
-    issue_R(0); issue_M(2);
-    asm volatile("s_waitcnt vmcnt(3)" ::: "memory");
-    lds_barrier();
-    issue_R(1);
-    // (order is now R(0) x 2, M(2), R(1) x 2: vmcnt(2) below = R(0) and M(2) done)
-    for (int b = 0; b < nbat; ++b) {
-        asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
-        lds_barrier();
-        issue_M(b + 3);
-        issue_R(b + 2);
-        const float4* meta = reinterpret_cast<const float4*>(sm + NRB * ROWB + (b % NMB) * RECB);
-        const float* dfb = reinterpret_cast<const float*>(sm + (b % NRB) * ROWB);
-        int* cn = cnt[b & 1];
-        if (tid < TROWS) cnt[(b + 1) & 1][tid] = 0;
-        if (tid < BATCH && beg + b * BATCH + tid < end) {
-            const int k = __float_as_int(meta[tid].y) >> 16;              // ly + 1
-            lists[k * BATCH + lds_add_rtn((unsigned)(uintptr_t)&cn[k], 1)] = (unsigned short)tid;
-        }
-        lds_barrier();
-#pragma unroll
-        for (int l = 0; l < LPW; ++l) {
-            const int li = wave * LPW + l;
-            const int m = cn[li];
-            const unsigned short* lst = lists + li * BATCH;
-            for (int e = 0; e < m; e += 8) {
-                int j[4];
-                float4 mt[4];
-                float g[4];
-#pragma unroll
-                for (int q = 0; q < 4; ++q) j[q] = lst[min(e + 2 * q + kk, BATCH - 1)] & (BATCH - 1);      // stale entries past m: masked below
-#pragma unroll
-                for (int q = 0; q < 4; ++q) { mt[q] = meta[j[q]]; g[q] = dfb[j[q] * FC + c]; }
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    const bool live = e + 2 * q + kk < m;
-                    const int lx = (__float_as_int(mt[q].y) & 0xffff) - 1;
-                    const float wx = mx == lx ? 1.f - mt[q].z : (mx == lx + 1 ? mt[q].z : 0.f);
-                    const float wy = mhalf ? mt[q].w : 1.f - mt[q].w;
-                    acc[l] = __builtin_amdgcn_mfma_f32_32x32x2f32(live ? wx * wy : 0.f, live ? g[q] : 0.f, acc[l], 0, 0, 0);
-                }
-            }
-        }
-    }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");           // the masked tail DMAs still write zeros: drain before the buffers become the tile
-    __syncthreads();
-    // combine the row pairs (see scatter_accum_kernel): lower halves first, then the upper halves
-#pragma unroll
-    for (int l = 0; l < LPW; ++l) {
-        const int li = wave * LPW + l;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int m = (r & 3) + 8 * (r >> 2) + 4 * kk;
-            if (m >= 16) tile[(li * TROWS + (m & 15)) * FC + c] = acc[l][r];
-        }
-    }
-    __syncthreads();
-#pragma unroll
-    for (int l = 0; l < LPW; ++l) {
-        const int li = wave * LPW + l;
-        if (li >= 1) {
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int m = (r & 3) + 8 * (r >> 2) + 4 * kk;
-                if (m < 16) tile[((li - 1) * TROWS + m) * FC + c] += acc[l][r];
-            }
-        }
-    }
-    __syncthreads();
-    for (int i = tid; i < TILE_FLOATS; i += NT) {
-        const float v = tile[i];
-        if (v != 0.f) {
-            const int cell = i / FC, ch = i - cell * FC;
-            const int yy = ty0 + cell / TROWS, xx = tx0 + cell % TROWS;
-            if (yy < Hp && xx < Wp) eg3d_acc(d_planes + (int64_t)n * Hp * Wp * ldp + ((int64_t)yy * Wp + xx) * ldp + pl * FC + ch, v);
-        }
-    }
-}
-
-// ---- row-keyed variant (default): the pairs are sorted by (tile, upper texel row); every (tile, row) list is streamed by ONE wave ---------
-// The batch lists above are rebuilt per 256 consecutive pairs of a tile, and consecutive pairs come from neighbouring rays: on the plane
-// the camera faces, a ray's 96 samples fall into one texel and a strip of rays into one texel ROW -- one or two of the 16 waves do the work
-// of a batch while the others wait at its barriers (MfmaUtil 18 %, 384 us; with the DMA pipeline above 311 us).  Sorting by (tile, row) in
-// the binning passes gives contiguous record lists that need no batches, no per-batch lists and no barriers:
-//   * binning (scatter_bin16_kernel): same two passes, 16 x the bins (3 x 18 x 18 x 16 = 15.5 K for one image: 62 KB of LDS histogram),
-//     flushed sparsely -- the first arrival of a bin in a block owns its global atomic -- instead of by a sweep over all bins;
+// ---- row-keyed lists: the pairs are sorted by (tile, upper texel row); every (tile, row) list is streamed by ONE wave ------------------
+// Consecutive pairs come from neighbouring rays: on the plane the camera faces, a ray's 96 samples fall into one texel and a strip of rays
+// into one texel ROW.  Lists rebuilt per batch of consecutive pairs of a tile therefore leave one or two waves of a block with the work of a
+// batch while the others wait at its barriers.  Sorting by (tile, row) in the binning passes gives contiguous record lists that need no
+// batches, no per-batch lists and no barriers:
+//   * binning (scatter_bin16_kernel): pass 0 counts, pass 1 places; one thread per (sample row, plane) pair.  3 x 18 x 18 x 16 = 15.5 K bins for
+//     one image: 62 KB of LDS histogram, flushed sparsely -- the first arrival of a bin in a block owns its global atomic -- instead of by
+//     a sweep over all bins;
 //   * accumulate (scatter_accum16p_kernel): see there.
-// Measured per launch (1.57 M samples, 4.5 M pairs): zero 5 + count 32 + scan 9 + place 72 + accumulate 138 = 256 us against 470 us for
-// the round-2 chain (zero 5 + 36 + 5 + 44 + 384).
+// Measured per launch (1.57 M samples, 4.5 M pairs): zero 5 + count 32 + scan 9 + place 72 + accumulate 138 = 256 us.
 // (the 62 KB histogram allows two blocks per CU: 1024-thread blocks keep the CU's wave slots full)
 // What the two passes cost is the GLOBAL atomics of the flush (one per bin a block touched): a block of consecutive rows = ~57 whole rays
 // crosses every depth tile of the two side planes, ~2 K bins per block, 0.6 M atomics per pass (77 us against 24 us with the flush
@@ -1416,7 +1015,7 @@ __global__ void __launch_bounds__(ACCP_WAVES * 64) scatter_accum16p_kernel(const
     }
 }
 
-// ---- the same accumulation on the 16-bit matrix cores (opt-in: eg3d_render_bwd_params.df_amax; EG3D_SCATTER_F16=1 in the host package) -------
+// ---- the same accumulation on the 16-bit matrix cores (opt-in: eg3d_render_bwd_params.df_amax; hipops.SCATTER_F16 = True in the host package) ----
 // Written on the assumption that scatter_accum16p_kernel is bound by the fp32 matrix pipe (v_mfma_f32_32x32x2_f32: two pairs per 64-cycle
 // instruction).  It is not, or not only: 128 -> 112 us.  With the gradient rows coming from eight cached rows this kernel takes 93 us, with
 // no row loads at all 77 us, without its MFMAs 116 us -- the random 128-byte row reads (0.6 GB per launch) and the per-pair instruction
@@ -1743,99 +1342,69 @@ extern "C" int eg3d_render_query_sizes(const eg3d_render_params* p, eg3d_render_
 }
 
 extern "C" int64_t eg3d_triplane_scatter_workspace_ints(int64_t S, int N, int Hp, int Wp) {
-    const int64_t nb = (int64_t)N * 3 * ((Hp + TS - 1) / TS) * ((Wp + TS - 1) / TS);
-    const int64_t nb16 = 3 * ((Hp + TS - 1) / TS) * ((Wp + TS - 1) / TS) * (TS + 1);        // row-keyed bins of one image (3 arrays)
-    return (4 * nb + 2 > 3 * nb16 + 2 ? 4 * nb + 2 : 3 * nb16 + 2) + 3 + 12 * S;            // counts, fill, offsets (+1), chunk_offsets (+1), [pad to 16 bytes] pair records (16 bytes per (sample, plane))
+    (void)N;                                                                                 // bins, records and row ids are per image
+    const int64_t nb16 = 3 * ((Hp + TS - 1) / TS) * ((Wp + TS - 1) / TS) * TROWS;            // (plane, tile, texel row) bins of one image
+    return 3 * nb16 + 1 + 3 + 12 * S;            // counts, fill, offsets (+1), [pad to 16 bytes] pair records (16 bytes per (sample, plane))
 }
 
+// Supported range (include/eg3d_hip.h): 3 * ntx * nty * 16 <= 16384 bins per image and S = N * rows_per_image; everything else is refused
+// here, before the first HIP call.
 extern "C" int eg3d_triplane_scatter(const float* df_rows, const float* df_pos, int64_t S, int64_t rows_per_image, float* d_planes, int N, int Hp,
                                      int Wp, int ldp, float box_warp, int32_t* workspace, int ray_w, int rows_per_ray, const float* df_amax, void* stream) {
     if (!df_rows || !df_pos || !d_planes || !workspace || S <= 0 || N <= 0 || rows_per_image <= 0) return EG3D_ERR_INVALID;
     if (ldp < 3 * FC || 3 * S > INT32_MAX / 4) return EG3D_ERR_UNSUPPORTED;
     const int ntx = (Wp + TS - 1) / TS, nty = (Hp + TS - 1) / TS;
-    const int nb = N * 3 * ntx * nty;
-    if ((size_t)nb * 2 * sizeof(int) > 64 * 1024) return EG3D_ERR_UNSUPPORTED;       // LDS histogram of the binning kernels
-    int* counts = workspace;
-    int* fill = counts + nb;
-    int* offsets = fill + nb;
-    int* chunk_offsets = offsets + nb + 1;
-    int* ids = chunk_offsets + nb + 1;
-    ids += (4 - ((ids - workspace) & 3)) & 3;          // the records are float4 (the workspace itself is at least 16-byte aligned)
+    const int64_t nb16_64 = (int64_t)3 * ntx * nty * TROWS;     // (plane, tile, texel row) bins of ONE image
+    if (nb16_64 > 16384) return EG3D_ERR_UNSUPPORTED;           // LDS histogram of the binning kernel, LDS image of the scan
+    if (S % N != 0 || rows_per_image != S / N) return EG3D_ERR_UNSUPPORTED;
+    if (rows_per_image * FC * 4 >= ((int64_t)1 << 32) || rows_per_image >= (1 << 27)) return EG3D_ERR_UNSUPPORTED;   // 32-bit buffer offsets; 27-bit row ids in the records
+    const int nb16_img = (int)nb16_64;
     hipStream_t st = (hipStream_t)stream;
     const float cs = 2.f / box_warp;
     EG3D_DET_SCOPE(det, stream); EG3D_DET_BIND(det, d_planes, (int64_t)N * Hp * Wp * ldp); EG3D_DET_COMMIT(det);
-    const int blocks = eg3d_cdiv(S * 3, 256 * BIN_ITEMS);
     const float4* pos4 = reinterpret_cast<const float4*>(df_pos);
-    static const int variant0 = [] { const char* e = getenv("EG3D_SCATTER"); return e ? atoi(e) : 4; }();
-    const int nb16_img = 3 * ntx * nty * TROWS;                 // row-keyed bins of ONE image
-    if (variant0 == 4 && nb16_img <= 16384 && S % N == 0 && rows_per_image == S / N && rows_per_image * FC * 4 < ((int64_t)1 << 32)
-        && rows_per_image < (1 << 27)) {
-        // row-keyed sort + wave-streamed accumulation, image by image (bins, records and row ids are per image)
-        int* counts16 = workspace;
-        int* fill16 = counts16 + nb16_img;
-        int* offsets16 = fill16 + nb16_img;
-        int* recs_i = offsets16 + nb16_img + 1;
-        recs_i += (4 - ((recs_i - workspace) & 3)) & 3;
-        float4* recs = reinterpret_cast<float4*>(recs_i);
-        const int64_t Si = rows_per_image;
-        // brick mode: 16 x 16 rays x SL rows per block
-        int SL = 0;
-        if (ray_w > 0 && rows_per_ray > 0 && ray_w % 16 == 0 && Si % ((int64_t)rows_per_ray * ray_w) == 0 && (Si / ((int64_t)rows_per_ray * ray_w)) % 16 == 0)
-            SL = rows_per_ray % 24 == 0 ? 24 : (rows_per_ray % 16 == 0 ? 16 : 0);
-        const int blocks_i = SL ? (int)(Si / rows_per_ray / 256 * (rows_per_ray / SL)) : eg3d_cdiv(Si * 3, BIN16_THREADS * BIN16_ITEMS);
-        auto bin_pass = [&](int pass, const float4* pos_n) {
+    // row-keyed sort + wave-streamed accumulation, image by image
+    int* counts16 = workspace;
+    int* fill16 = counts16 + nb16_img;
+    int* offsets16 = fill16 + nb16_img;
+    int* recs_i = offsets16 + nb16_img + 1;
+    recs_i += (4 - ((recs_i - workspace) & 3)) & 3;          // the records are float4 (the workspace itself is at least 16-byte aligned)
+    float4* recs = reinterpret_cast<float4*>(recs_i);
+    const int64_t Si = rows_per_image;
+    // brick mode: 16 x 16 rays x SL rows per block
+    int SL = 0;
+    if (ray_w > 0 && rows_per_ray > 0 && ray_w % 16 == 0 && Si % ((int64_t)rows_per_ray * ray_w) == 0 && (Si / ((int64_t)rows_per_ray * ray_w)) % 16 == 0)
+        SL = rows_per_ray % 24 == 0 ? 24 : (rows_per_ray % 16 == 0 ? 16 : 0);
+    const int blocks_i = SL ? (int)(Si / rows_per_ray / 256 * (rows_per_ray / SL)) : eg3d_cdiv(Si * 3, BIN16_THREADS * BIN16_ITEMS);
+    auto bin_pass = [&](int pass, const float4* pos_n) {
 #define EG3D_BIN16(P, L) hipLaunchKernelGGL((scatter_bin16_kernel<P, L>), dim3(blocks_i), dim3(BIN16_THREADS), sizeof(int) * nb16_img, st, pos_n, Si, cs, Hp, \
                                             Wp, ntx, nty, nb16_img, counts16, offsets16, fill16, recs, ray_w, rows_per_ray)
-            if (pass == 0) { if (SL == 24) EG3D_BIN16(0, 24); else if (SL == 16) EG3D_BIN16(0, 16); else EG3D_BIN16(0, 0); }
-            else           { if (SL == 24) EG3D_BIN16(1, 24); else if (SL == 16) EG3D_BIN16(1, 16); else EG3D_BIN16(1, 0); }
+        if (pass == 0) { if (SL == 24) EG3D_BIN16(0, 24); else if (SL == 16) EG3D_BIN16(0, 16); else EG3D_BIN16(0, 0); }
+        else           { if (SL == 24) EG3D_BIN16(1, 24); else if (SL == 16) EG3D_BIN16(1, 16); else EG3D_BIN16(1, 0); }
 #undef EG3D_BIN16
-        };
-        for (int n = 0; n < N; ++n) {
-            const float4* pos_n = pos4 + (int64_t)n * Si;
-            eg3d_zero_words(counts16, 2 * (int64_t)nb16_img, st);
-            bin_pass(0, pos_n);
-            hipLaunchKernelGGL(scatter_scan16_kernel, dim3(1), dim3(1024), 0, st, counts16, offsets16, nb16_img);
-            bin_pass(1, pos_n);
+    };
+    for (int n = 0; n < N; ++n) {
+        const float4* pos_n = pos4 + (int64_t)n * Si;
+        eg3d_zero_words(counts16, 2 * (int64_t)nb16_img, st);          // counts + fill cursors (a kernel, not a memset node: see common.h)
+        bin_pass(0, pos_n);
+        hipLaunchKernelGGL(scatter_scan16_kernel, dim3(1), dim3(1024), 0, st, counts16, offsets16, nb16_img);
+        bin_pass(1, pos_n);
 #if EG3D_DET
-            hipLaunchKernelGGL(scatter_sort16_kernel, dim3(nb16_img), dim3(256), 0, st, offsets16, recs);
+        hipLaunchKernelGGL(scatter_sort16_kernel, dim3(nb16_img), dim3(256), 0, st, offsets16, recs);
 #endif
-            constexpr int split = 1;
-            // one block of four waves per four lists: the hardware's block dispatch does the load balancing (lists differ 0 .. 990 pairs); with
-            // 1024 persistent blocks taking lists w, w + 4096, ... the launch lasted as long as its unluckiest wave (fp32: 142 -> 128 us)
-            const int accb = (nb16_img + ACCP_WAVES - 1) / ACCP_WAVES;
-            if (df_amax != nullptr) {
-                hipLaunchKernelGGL(scatter_accum16h_kernel, dim3(accb), dim3(ACCP_WAVES * 64), 0, st, df_rows + (int64_t)n * Si * FC, Si, offsets16, recs,
-                                   d_planes + (int64_t)n * Hp * Wp * ldp, Hp, Wp, ldp, ntx, nty, df_amax);
-                continue;
-            }
-            hipLaunchKernelGGL(scatter_accum16p_kernel, dim3(accb), dim3(ACCP_WAVES * 64), 0, st, df_rows + (int64_t)n * Si * FC, Si, offsets16, recs,
-                               d_planes + (int64_t)n * Hp * Wp * ldp, Hp, Wp, ldp, ntx, nty, split);
+        constexpr int split = 1;
+        // one block of four waves per four lists: the hardware's block dispatch does the load balancing (lists differ 0 .. 990 pairs); with
+        // 1024 persistent blocks taking lists w, w + 4096, ... the launch lasted as long as its unluckiest wave (fp32: 142 -> 128 us)
+        const int accb = (nb16_img + ACCP_WAVES - 1) / ACCP_WAVES;
+        if (df_amax != nullptr) {
+            hipLaunchKernelGGL(scatter_accum16h_kernel, dim3(accb), dim3(ACCP_WAVES * 64), 0, st, df_rows + (int64_t)n * Si * FC, Si, offsets16, recs,
+                               d_planes + (int64_t)n * Hp * Wp * ldp, Hp, Wp, ldp, ntx, nty, df_amax);
+            continue;
         }
-        EG3D_DET_END(det);
-        EG3D_LAUNCH_CHECK();
-        return EG3D_OK;
+        hipLaunchKernelGGL(scatter_accum16p_kernel, dim3(accb), dim3(ACCP_WAVES * 64), 0, st, df_rows + (int64_t)n * Si * FC, Si, offsets16, recs,
+                           d_planes + (int64_t)n * Hp * Wp * ldp, Hp, Wp, ldp, ntx, nty, split);
     }
-#if EG3D_DET
-    return EG3D_ERR_UNSUPPORTED;          // the older scatter variants sum in an order their LDS cursors decide
-#endif
-    eg3d_zero_words(counts, 2 * (int64_t)nb, st);          // counts + fill cursors (a kernel, not a memset node: see common.h)
-    hipLaunchKernelGGL(scatter_bin_kernel<0>, dim3(blocks), dim3(256), sizeof(int) * nb, st, pos4, S, rows_per_image, cs, Hp, Wp, ntx, nty, nb, counts,
-                       offsets, fill, ids);
-    hipLaunchKernelGGL(scatter_scan_kernel, dim3(1), dim3(1024), 0, st, counts, offsets, chunk_offsets, nb);
-    const int max_chunks = (int)((3 * S + CHUNK - 1) / CHUNK) + nb;
-    const int variant = variant0 == 4 ? 3 : variant0;      // 1: round-2 kernel; 2 / 3: DMA-pipelined batches (8 / 16 waves); 4 (default, above): row-keyed
-    if (variant == 1 || S * FC * 4 >= ((int64_t)1 << 32) || 3 * S * 16 >= ((int64_t)1 << 32)) {
-        hipLaunchKernelGGL(scatter_bin_kernel<1>, dim3(blocks), dim3(256), sizeof(int) * 2 * nb, st, pos4, S, rows_per_image, cs, Hp, Wp, ntx, nty, nb, counts,
-                           offsets, fill, ids);
-        hipLaunchKernelGGL(scatter_accum_kernel, dim3(max_chunks), dim3(ACC_THREADS), 0, st, df_rows, pos4, offsets, chunk_offsets, ids, d_planes, cs, Hp, Wp, ldp,
-                           ntx, nty, nb);
-    } else {
-        hipLaunchKernelGGL(scatter_bin_kernel<2>, dim3(blocks), dim3(256), sizeof(int) * 2 * nb, st, pos4, S, rows_per_image, cs, Hp, Wp, ntx, nty, nb, counts,
-                           offsets, fill, ids);
-        const float4* recs = reinterpret_cast<const float4*>(ids);
-        hipLaunchKernelGGL((scatter_accum2_kernel<16, 256>), dim3(max_chunks), dim3(1024), 0, st, df_rows, S, offsets, chunk_offsets, recs, 3 * S, d_planes, Hp, Wp,
-                           ldp, ntx, nty, nb);
-    }
+    EG3D_DET_END(det);
     EG3D_LAUNCH_CHECK();
     return EG3D_OK;
 }

@@ -844,7 +844,13 @@ int eg3d_render_bwd(const eg3d_render_bwd_params* p, void* stream);
  * forward/backward -> df_rows/df_pos, gc_rows, optional decoder dumps) + a per-ray reduction of gc_rows.
  *
  * d_planes[N,Hp,Wp,ldp] (pre-zeroed) += bilinear-adjoint scatter of the S dumped rows (grid_sample backward w.r.t. the
- * planes, renderer.py:64 under autograd).  rows_per_image = R*2*D.  workspace: eg3d_triplane_scatter_workspace_ints() int32. */
+ * planes, renderer.py:64 under autograd).  rows_per_image = R*2*D.  workspace: eg3d_triplane_scatter_workspace_ints() int32.
+ *
+ * Supported range (both builds; EG3D_ERR_UNSUPPORTED outside it, decided from the arguments before any GPU work):
+ *   - planes up to 270 x 270: 3 * ceil(Hp / 15) * ceil(Wp / 15) * 16 <= 16384 (tile, texel row) lists per image;
+ *   - S = N * rows_per_image exactly, rows_per_image < 2^25 (one image's df_rows below 2^32 bytes; the records hold 27-bit row ids), 12 * S <= INT32_MAX, ldp >= 96.
+ * There is one accumulation path (the row-keyed lists of csrc/renderer.hip); earlier versions of the normal build ran calls outside this
+ * range on older, unmaintained kernels -- those are gone, and the normal build now refuses what the deterministic build always refused. */
 int64_t eg3d_triplane_scatter_workspace_ints(int64_t S, int N, int Hp, int Wp);
 /* ray_w, rows_per_ray: optional hint (0, 0 = unknown) -- rays per image row and dumped rows per ray (2 D) of the row layout above; the
  * binning passes then walk the rows in bricks of 16 x 16 rays (fewer bins per block); the result does not depend on it.

@@ -77,6 +77,9 @@ def test_product_does_not_import_oracle():
                 src = open(os.path.join(dirpath, f)).read()
                 assert not re.search(r'^\s*(from|import)\s+oracle\b', src, re.M), f'{f} imports the oracle'
                 assert '/root/reference' not in src
+    # ... and the library reads no environment: what an entry does is a function of its arguments, every switch is one test_default_switch_state sees
+    csrc = os.path.join(ROOT, '3dgan-inversion_amd', 'csrc')
+    assert [f for f in sorted(os.listdir(csrc)) if 'getenv' in open(os.path.join(csrc, f)).read()] == []
 
 
 def test_tap_lists():
@@ -295,6 +298,31 @@ def test_round2_entry_points_reject_bad_arguments_before_touching_the_gpu():
     assert lib.eg3d_conv2d_igemm_f32(C.byref(p), None) < 0
 
 
+def test_triplane_scatter_refuses_what_is_outside_its_range_before_touching_the_gpu():
+    """eg3d_triplane_scatter has one path (row-keyed lists): planes up to 270 x 270 and S = N * rows_per_image (include/eg3d_hip.h).  Outside
+    that range both builds answer EG3D_ERR_UNSUPPORTED from the arguments alone -- no HIP call, hence answerable here."""
+    import ctypes as C
+    from inv3d_amd import _lib as L
+    INVALID, UNSUPPORTED = -1, -2
+    assert L.lib().eg3d_status_string(INVALID) == b'invalid argument' and L.lib().eg3d_status_string(UNSUPPORTED) == b'unsupported configuration'
+    libs = [L.lib()]
+    if not L.DETERMINISTIC:
+        det = C.CDLL(os.path.join(os.path.dirname(L.LIB_PATH), 'libeg3d_hip_det.so'))
+        det.eg3d_triplane_scatter.restype, det.eg3d_triplane_scatter.argtypes = L.lib().eg3d_triplane_scatter.restype, L.lib().eg3d_triplane_scatter.argtypes
+        libs.append(det)
+    a = 0x10000                                            # non-null fake addresses (never dereferenced: validation fails first)
+    for lib in libs:
+        #                              df_rows df_pos S rows_per_image d_planes N Hp Wp ldp box_warp workspace ray_w rows_per_ray df_amax stream
+        assert lib.eg3d_triplane_scatter(a, a, 96, 96, a, 1, 512, 512, 96, 1.0, a, 0, 0, None, None) == UNSUPPORTED      # 3 * 35 * 35 * 16 > 16384 lists
+        assert lib.eg3d_triplane_scatter(a, a, 3, 1, a, 2, 32, 32, 96, 1.0, a, 0, 0, None, None) == UNSUPPORTED          # S != N * rows_per_image
+        assert lib.eg3d_triplane_scatter(a, a, 96, 96, a, 1, 32, 32, 64, 1.0, a, 0, 0, None, None) == UNSUPPORTED        # ldp < 96
+        assert lib.eg3d_triplane_scatter(None, a, 96, 96, a, 1, 32, 32, 96, 1.0, a, 0, 0, None, None) == INVALID
+        assert lib.eg3d_triplane_scatter(a, a, 96, 96, a, 1, 32, 32, 96, 1.0, None, 0, 0, None, None) == INVALID         # no workspace
+    # the workspace covers what the entry carves: counts, fill, offsets (+ 1), up to 3 ints of alignment, one 16-byte record per (sample, plane)
+    nb16 = 3 * 18 * 18 * 16
+    assert L.lib().eg3d_triplane_scatter_workspace_ints(1000, 2, 256, 256) == 3 * nb16 + 1 + 3 + 12 * 1000
+
+
 def test_default_switch_state():
     """Every EG3D_* environment switch of the package, read in a process with NO EG3D_* variable set, has the value committed in
     tests/golden/default_switches.json -- a default that flips (or a new switch) must show up in a diff of that file, not silently in the
@@ -332,7 +360,8 @@ def test_ctypes_structures_match_the_header():
              ('eg3d_torgb_small_params', L.TorgbSmallParams), ('eg3d_torgb_small_bwd_params', L.TorgbSmallBwdParams),
              ('eg3d_conv3x3_direct_params', L.Conv3x3DirectParams), ('eg3d_adam_item', L.AdamItem), ('eg3d_adam_list', L.AdamList),
              ('eg3d_unit_level', L.UnitLevel), ('eg3d_unit_levels', L.UnitLevels), ('eg3d_flrelu_params', L.FlreluParams),
-             ('eg3d_style_layer', L.StyleLayer), ('eg3d_style_bank', L.StyleBank), ('eg3d_wgf_item', L.WgfItem), ('eg3d_pack_item', L.PackItem)]
+             ('eg3d_style_layer', L.StyleLayer), ('eg3d_style_bank', L.StyleBank), ('eg3d_wgf_item', L.WgfItem), ('eg3d_pack_item', L.PackItem),
+             ('eg3d_mc_params', L.McParams), ('eg3d_ssim_params', L.SsimParams), ('eg3d_batchnorm_params', L.BatchNormParams)]
     header = open(os.path.join(ROOT, 'include', 'eg3d_hip.h')).read()
     src = ['#include <stdio.h>', '#include <stddef.h>', '#include "eg3d_hip.h"', 'int main(void) {']
     want = []

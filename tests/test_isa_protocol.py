@@ -68,7 +68,7 @@ def test_every_lds_dma_kernel_of_the_library_keeps_the_step_boundary():
     assert r.returncode == 0, tail
     assert 'VIOLATION' not in r.stdout
     lines = [l for l in r.stdout.splitlines() if 'LDS-DMA kernels' in l]
-    assert sum(int(l.split(':')[1].split()[0]) for l in lines) >= 30, tail        # conv_v2 x15, s2adj x4, up2 x2, v3 x8, wgrad_v2 x6, scatter_accum2
+    assert sum(int(l.split(':')[1].split()[0]) for l in lines) >= 30, tail        # conv_v2 x15, s2adj x4, up2 x2, v3 x8, wgrad_v2 x6
 
 
 def test_shipped_libraries_have_no_lds_operation_in_flight_at_a_barrier_and_no_low_lane_op_sel():

@@ -1,4 +1,4 @@
-"""List-length statistics of the row-keyed plane-gradient scatter (EG3D_SCATTER=4): how the (tile, texel row) lists are balanced."""
+"""List-length statistics of the row-keyed plane-gradient scatter: how the (tile, texel row) lists are balanced."""
 import sys, torch
 sys.path.insert(0, '/root/repo'); sys.path.insert(0, '/root/repo/3dgan-inversion_amd')
 from inv3d_amd import synthetic as S, _lib as L, hipops as H

@@ -247,6 +247,16 @@ class BatchNormParams(C.Structure):
                 ('dresidual', C.c_void_p), ('dgamma', C.c_void_p), ('dbeta', C.c_void_p)]
 
 
+class JpegParams(C.Structure):
+    """eg3d_jpeg_params: baseline JPEG encoder (eg3d_jpeg_query_workspace / eg3d_jpeg_encode / eg3d_jpeg_pack)."""
+    _fields_ = [('img', C.c_void_p), ('header', C.c_void_p), ('workspace', C.c_void_p), ('workspace_bytes', C.c_int64), ('offsets', C.c_void_p),
+                ('out', C.c_void_p), ('out_capacity', C.c_int64), ('dtype', C.c_int32), ('N', C.c_int32), ('C', C.c_int32), ('H', C.c_int32),
+                ('W', C.c_int32), ('subsampling', C.c_int32), ('quality', C.c_int32), ('restart_interval', C.c_int32), ('header_bytes', C.c_int32)]
+
+
+JPEG_F32, JPEG_U8 = 0, 1
+JPEG_444, JPEG_420 = 0, 1
+
 _SIGS = {
     'eg3d_abi_version': (C.c_int, []),
     'eg3d_status_string': (C.c_char_p, [C.c_int]),
@@ -387,6 +397,9 @@ _SIGS = {
     'eg3d_sym_eig_workspace': (C.c_int, [C.c_int, C.POINTER(C.c_int64)]),
     'eg3d_sym_eig': (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_void_p, C.POINTER(C.c_int32), C.c_void_p]),
     'eg3d_image_grid_u8': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    'eg3d_jpeg_query_workspace': (C.c_int, [C.POINTER(JpegParams), C.POINTER(C.c_int64)]),
+    'eg3d_jpeg_encode': (C.c_int, [C.POINTER(JpegParams), C.c_void_p]),
+    'eg3d_jpeg_pack': (C.c_int, [C.POINTER(JpegParams), C.c_void_p]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGS)

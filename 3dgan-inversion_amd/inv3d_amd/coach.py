@@ -16,8 +16,10 @@ with `gen_mesh` every image's tuned generator writes {mesh_dir}/{name}_pti.mrc (
 global_config.gen_mesh -> create_geometry does (single_id_coach.py:109-110,120-163; inference.density_grid / extract_mesh / write_mrc /
 write_ply).  Evaluation is here too: with `do_evaluation` the tuned reconstruction's mse / lpips / msssim / identity (metrics.py: GPU
 MS-SSIM, the ArcFace IR-SE-50 identity distance) go to {eval_dir}/{name}metrics.txt, and `save_pivot` writes {name}_ws.npy /
-{name}_cam.npy (single_id_coach.py:87-117).  Image / video file I/O and logging of the reference loop are outside this package; the
-e4e encoder, the pose head and ArcFace are in e4e.py, pose_net.py and metrics.py.
+{name}_cam.npy (single_id_coach.py:87-117).  Media export is here as well: with `save_grid` / `gen_video` the pivot grid PNG and the orbit video
+are written before Phase B to {media_dir}/pivot/ and again after it to {media_dir}/ (single_id_coach.py:57-62,80-85; video.py: the GPU JPEG
+encoder in a Motion-JPEG AVI, since there is no H.264 encoder to call).  Image loading, face alignment and wandb logging of the reference loop
+are outside this package; the e4e encoder, the pose head and ArcFace are in e4e.py, pose_net.py and metrics.py.
 """
 from dataclasses import dataclass, field
 from typing import Callable, Dict, List, Optional, Sequence, Tuple
@@ -31,6 +33,7 @@ from . import dist as D
 from .inference import density_grid, estimate_w_stats, extract_mesh, write_mrc, write_ply
 from .inversion import LatentProjector, PivotalTuner, psnr_01
 from .metrics import IDLoss, format_metrics_txt, reconstruction_metrics
+from .video import pivot_grid, write_orbit_video, write_png
 
 
 @dataclass
@@ -46,6 +49,9 @@ class InversionResult:
     tuned_state: Optional[Dict[str, torch.Tensor]] = field(default=None, repr=False)    # generator weights after Phase B (opt-in)
     mesh_path: Optional[str] = None                                                       # the shape written with gen_mesh
     metrics: Optional[Dict[str, float]] = None                                            # mse / lpips / msssim / identity with do_evaluation
+    # media export: plain attributes that the coach sets after construction, not constructor arguments (the field list ends with `metrics`)
+    grid_paths = None                                                                     # (pivot, tuned) grid PNGs with save_grid
+    video_paths = None                                                                    # (pivot, tuned) orbit videos with gen_video
 
 
 class InversionCoach:
@@ -57,7 +63,8 @@ class InversionCoach:
                  start_w_fn: Optional[Callable[[torch.Tensor], torch.Tensor]] = None, sr_fp16: bool = True, gen_mesh: bool = False,
                  mesh_dir: Optional[str] = None, mesh_res: int = 512, mesh_level: float = 10.0, mesh_format: str = '.mrc',
                  do_evaluation: bool = False, eval_dir: Optional[str] = None, lpips_eval_net: Optional[Callable] = None,
-                 id_net: Optional[Callable] = None, save_pivot: bool = False, pivot_dir: Optional[str] = None):
+                 id_net: Optional[Callable] = None, save_pivot: bool = False, pivot_dir: Optional[str] = None, save_grid: bool = False,
+                 gen_video: bool = False, media_dir: Optional[str] = None, video_quality: int = 90):
         """Hyper-parameter names and defaults follow configs/hyperparameters.py.  `early_stop_interval` = how often Phase B reads the
         early-stop state back to the host (1 = every step like the reference).  With the library's Adam the TEST itself runs on the device
         in every step whatever the interval (PivotalTuner.device_stop): the interval then only bounds how many masked no-op steps are
@@ -70,7 +77,13 @@ class InversionCoach:
         `do_evaluation` (global_config.do_evaluation): after Phase B render G.synthesis(w_pivot[:, :14], cam[:, :25]) with the tuned generator and
         write metrics.reconstruction_metrics to {eval_dir}/{name}metrics.txt; `lpips_eval_net` (LPIPSAlex) and `id_net` (IDLoss) are built
         once per coach when None.  `save_pivot` writes {pivot_dir}/{name}_ws.npy and {name}_cam.npy; in the reference it only takes effect
-        under do_evaluation, here it is independent of it (like gen_mesh)."""
+        under do_evaluation, here it is independent of it (like gen_mesh).
+        `save_grid`: video.pivot_grid (target, the render at the pivot camera, three look_at views; noise_mode='const') as
+        {media_dir}/pivot/{name}.png before Phase B and {media_dir}/{name}.png after it.  `gen_video` (global_config.gen_video):
+        video.write_orbit_video (240 frames, 60 fps, JPEG quality `video_quality`) as {media_dir}/pivot/{name}_pivot.avi and {media_dir}/{name}.avi."""
+        if (save_grid or gen_video) and not media_dir:
+            raise ValueError('save_grid / gen_video need a media_dir')
+        self.save_grid, self.gen_video, self.media_dir, self.video_quality = save_grid, gen_video, media_dir, int(video_quality)
         if do_evaluation and not eval_dir:
             raise ValueError('do_evaluation needs an eval_dir')
         if save_pivot and not pivot_dir:
@@ -145,6 +158,7 @@ class InversionCoach:
         with torch.no_grad():
             img = G.synthesis(w_pivot, cam_pivot, noise_mode='const', force_fp32=True, **self.synth_kwargs)['image']
             psnr_pivot = float(psnr_01(img, target))
+        grid_pivot, video_pivot = self.write_media(name, w_pivot, cam_pivot, target, pivot=True)
         # ---- Phase B: generator weights around the pivot ------------------------------------------------------------------------
         tuner = PivotalTuner(G, target, w_pivot, cam_pivot, lr=self.pti_lr, lpips_threshold=self.thr, feature_net=self.feature_net,
                              synth_kwargs=self.synth_kwargs, sr_fp16=self.sr_fp16, use_graph=self.use_graph)
@@ -177,11 +191,15 @@ class InversionCoach:
         G.requires_grad_(False)
         mesh_path = self.write_mesh(name, w_pivot) if self.gen_mesh else None
         metrics = self.evaluate(name, w_pivot, cam_pivot, target) if self.do_evaluation else None
+        grid_tuned, video_tuned = self.write_media(name, w_pivot, cam_pivot, target, pivot=False)
         if self.save_pivot:
             os.makedirs(self.pivot_dir, exist_ok=True)
             np.save(os.path.join(self.pivot_dir, f'{name}_cam.npy'), cam_pivot.detach().cpu().numpy())
             np.save(os.path.join(self.pivot_dir, f'{name}_ws.npy'), w_pivot.detach().cpu().numpy())
-        return InversionResult(name, w_pivot, cam_pivot, psnr_pivot, psnr_tuned, mse, self.first_inv_steps, steps_b, state, mesh_path, metrics)
+        res = InversionResult(name, w_pivot, cam_pivot, psnr_pivot, psnr_tuned, mse, self.first_inv_steps, steps_b, state, mesh_path, metrics)
+        res.grid_paths = (grid_pivot, grid_tuned) if self.save_grid else None
+        res.video_paths = (video_pivot, video_tuned) if self.gen_video else None
+        return res
 
     def evaluate(self, name: str, w_pivot: torch.Tensor, cam: torch.Tensor, target: torch.Tensor) -> Dict[str, float]:
         """single_id_coach.py:87-106 with the generator as it is now (the tuned one): the metrics, written to {eval_dir}/{name}metrics.txt."""
@@ -192,6 +210,22 @@ class InversionCoach:
         with open(os.path.join(self.eval_dir, f'{name}metrics.txt'), 'w') as f:
             f.write(format_metrics_txt(m))
         return m
+
+    def write_media(self, name: str, w_pivot: torch.Tensor, cam: torch.Tensor, target: torch.Tensor, pivot: bool):
+        """(grid path | None, video path | None) of the generator as it is now: single_id_coach.py:57-62 (pivot=True: before Phase B, into
+        {media_dir}/pivot/, the video named {name}_pivot) and :80-85 (after Phase B, into {media_dir}/)."""
+        if not (self.save_grid or self.gen_video):
+            return None, None
+        d = os.path.join(self.media_dir, 'pivot') if pivot else self.media_dir
+        os.makedirs(d, exist_ok=True)
+        grid_path = video_path = None
+        if self.save_grid:
+            grid_path = os.path.join(d, f'{name}.png')
+            write_png(grid_path, pivot_grid(self.G, w_pivot, cam, target, **self.synth_kwargs))
+        if self.gen_video:
+            video_path = os.path.join(d, f'{name}_pivot.avi' if pivot else f'{name}.avi')
+            write_orbit_video(self.G, w_pivot, video_path, quality=self.video_quality, **self.synth_kwargs)
+        return grid_path, video_path
 
     def write_mesh(self, name: str, w_pivot: torch.Tensor) -> str:
         """create_geometry(G, w_pivot, outdir=mesh_dir, fname=name + '_pti') with the generator as it is now (the tuned one)."""

@@ -2017,3 +2017,48 @@ def image_grid_u8(img: torch.Tensor, nrow: int, padding: int = 2, pad_value: int
     out = torch.empty((Ht, Wt, 3), dtype=torch.uint8, device=img.device)
     L.check(L.lib().eg3d_image_grid_u8(L.ptr(img), N, Hh, Ww, int(nrow), int(padding), int(pad_value), L.ptr(out), L.stream_ptr()), 'image_grid_u8')
     return out
+
+
+_jpeg_headers = {}
+
+
+def jpeg_encode(img: torch.Tensor, quality: int = 90, subsampling: str = '420', restart_interval: Optional[int] = None):
+    """(bytes uint8 [total], offsets int64 [N+1] on the host): N baseline JFIF files back to back, frame n = bytes[offsets[n]:offsets[n+1]]
+    (eg3d_jpeg_*; include/eg3d_hip.h).  img [N,C,H,W], C = 3 (RGB) or 1 (grey): fp32 in [-1,1], quantised as image_grid_u8, or uint8 as is.
+    subsampling '420' | '444' (grey ignores it); restart_interval in MCUs, None = MCUs per row capped at 32 -- every interval is coded by its
+    own wave.  The header (video.jpeg_header) is built and uploaded once per configuration.  Four launches, workspace from the caching
+    allocator, one host synchronise (the total)."""
+    from . import video as V
+    L.require_cuda(img)
+    if img.dim() != 4 or img.shape[1] not in (1, 3) or img.dtype not in (torch.float32, torch.uint8) or min(img.shape) < 1:
+        raise L.Eg3dHipError(f'jpeg_encode: fp32 or uint8 [N >= 1, 1 | 3, H, W], got {tuple(img.shape)} {img.dtype}')
+    if subsampling not in ('420', '444'):
+        raise L.Eg3dHipError(f"jpeg_encode: subsampling '420' | '444', got {subsampling!r}")
+    img = img.contiguous()
+    N, Ch, Hh, Ww = img.shape
+    dev = img.device
+    R = V.default_restart_interval(Hh, Ww, subsampling, Ch) if restart_interval is None else int(restart_interval)
+    if not (1 <= R <= V.MAX_RESTART_INTERVAL and 1 <= int(quality) <= 100):
+        raise L.Eg3dHipError(f'jpeg_encode: restart interval 1..{V.MAX_RESTART_INTERVAL} and quality 1..100, got {R}, {quality}')
+    key = (Hh, Ww, Ch, subsampling, int(quality), R, dev)
+    hdr = _jpeg_headers.get(key)
+    if hdr is None:
+        if len(_jpeg_headers) >= 64:
+            _jpeg_headers.clear()
+        raw = V.jpeg_header(Hh, Ww, quality=int(quality), subsampling=subsampling, restart_interval=R, channels=Ch)
+        hdr = _jpeg_headers[key] = torch.frombuffer(bytearray(raw), dtype=torch.uint8).to(dev)
+    p = L.JpegParams(img=img.data_ptr(), header=hdr.data_ptr(), header_bytes=hdr.numel(), dtype=L.JPEG_F32 if img.dtype == torch.float32 else L.JPEG_U8,
+                     N=N, C=Ch, H=Hh, W=Ww, subsampling=L.JPEG_420 if subsampling == '420' else L.JPEG_444, quality=int(quality), restart_interval=R)
+    lib = L.lib()
+    nbytes = C.c_int64(0)
+    L.check(lib.eg3d_jpeg_query_workspace(C.byref(p), C.byref(nbytes)), 'jpeg_query_workspace')
+    ws = torch.empty(nbytes.value, dtype=torch.uint8, device=dev)
+    offsets = torch.empty(N + 1, dtype=torch.int64, device=dev)
+    p.workspace, p.workspace_bytes, p.offsets = ws.data_ptr(), nbytes.value, offsets.data_ptr()
+    L.check(lib.eg3d_jpeg_encode(C.byref(p), L.stream_ptr()), 'jpeg_encode')
+    offsets = offsets.cpu()
+    total = int(offsets[N])
+    out = torch.empty(total, dtype=torch.uint8, device=dev)
+    p.out, p.out_capacity = out.data_ptr(), total
+    L.check(lib.eg3d_jpeg_pack(C.byref(p), L.stream_ptr()), 'jpeg_pack')
+    return out, offsets

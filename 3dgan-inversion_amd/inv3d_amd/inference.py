@@ -2,8 +2,8 @@
 G.mapping / ImportanceRenderer.run_model on the gfx950 kernels.
 
   lookat_pose, orbit_cameras   <- utils/camera_utils.py:87-105,137-156 and the per-frame cameras of gen_videos.py:105-117
-  render_orbit                 <- gen_interp_video, gen_videos.py:63-146 (one latent, 240-frame orbit; no video encoder here: frames are
-                                  returned as tensors)
+  render_orbit                 <- gen_interp_video, gen_videos.py:63-146 (one latent, 240-frame orbit; frames are returned as tensors:
+                                  video.write_orbit_video encodes them on the GPU and writes the file)
   estimate_w_stats             <- mean latent / spread of the projector, training/projectors/w_projector.py:88-97
   density_grid                 <- create_geometry + create_samples, training/coaches/single_id_coach.py:120-186 (sigma on a res^3 grid)
   extract_mesh, write_ply      <- create_geometry's '.ply' branch (single_id_coach.py:155-157) and convert_sdf_samples_to_ply /

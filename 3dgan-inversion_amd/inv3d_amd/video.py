@@ -1,0 +1,264 @@
+"""Media export: the files the reference writes per image next to the numbers.
+
+  jpeg_tables, jpeg_header     <- the constant part of a baseline JFIF file: what hipops.jpeg_encode (csrc/jpeg.hip) puts in front of every
+                                  frame's entropy-coded scan; quantisation tables scaled as libjpeg's jpeg_quality_scaling, Annex K Huffman tables
+  MjpegAviWriter               <- imageio.get_writer(mp4, mode='I', fps=60, codec='libx264') of gen_interp_video, gen_videos.py:74-146: there
+                                  is no video encoder to call, so the container is a Motion-JPEG AVI (RIFF 'AVI ', one 'MJPG' video stream,
+                                  'idx1' index) written here, the frames are the GPU encoder's JFIF files
+  write_png                    <- PIL.Image.fromarray(...).save(png), single_id_coach.py:60,83 (zlib only)
+  write_orbit_video            <- gen_interp_video(G, w_pivot, path), single_id_coach.py:61-62,84-85
+  look_at_small, pivot_grid    <- BaseCoach.forward(ws, needs_img_grid='small', grid_num=5, need_gt_ingrid=(target, cam)) with look_at /
+                                  gen_eyes(num='small'), base_coach.py:128-159,216-291
+
+Everything but the rendering and hipops.jpeg_encode / image_grid_u8 is host code on the standard library."""
+import math
+import struct
+import zlib
+from typing import List, Optional, Tuple
+
+import numpy as np
+import torch
+
+# ---- ITU-T T.81 Annex K ------------------------------------------------------------------------------------------------------------------
+# K.1 / K.2: quantisation tables in natural (row-major) order
+QUANT_LUMA = (16, 11, 10, 16, 24, 40, 51, 61, 12, 12, 14, 19, 26, 58, 60, 55, 14, 13, 16, 24, 40, 57, 69, 56, 14, 17, 22, 29, 51, 87, 80, 62,
+              18, 22, 37, 56, 68, 109, 103, 77, 24, 35, 55, 64, 81, 104, 113, 92, 49, 64, 78, 87, 103, 121, 120, 101, 72, 92, 95, 98, 112, 100, 103, 99)
+QUANT_CHROMA = (17, 18, 24, 47, 99, 99, 99, 99, 18, 21, 26, 66, 99, 99, 99, 99, 24, 26, 56, 99, 99, 99, 99, 99, 47, 66, 99, 99, 99, 99, 99, 99) + (99,) * 32
+# zigzag position k -> natural index
+ZIGZAG = (0, 1, 8, 16, 9, 2, 3, 10, 17, 24, 32, 25, 18, 11, 4, 5, 12, 19, 26, 33, 40, 48, 41, 34, 27, 20, 13, 6, 7, 14, 21, 28,
+          35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23, 30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63)
+# K.3 - K.6: Huffman tables as (BITS[1..16], HUFFVAL)
+DC_LUMA = ((0, 1, 5, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0, 0, 0), tuple(range(12)))
+DC_CHROMA = ((0, 3, 1, 1, 1, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0), tuple(range(12)))
+AC_LUMA = ((0, 2, 1, 3, 3, 2, 4, 3, 5, 5, 4, 4, 0, 0, 1, 0x7d),
+           (0x01, 0x02, 0x03, 0x00, 0x04, 0x11, 0x05, 0x12, 0x21, 0x31, 0x41, 0x06, 0x13, 0x51, 0x61, 0x07, 0x22, 0x71, 0x14, 0x32, 0x81, 0x91, 0xa1, 0x08,
+            0x23, 0x42, 0xb1, 0xc1, 0x15, 0x52, 0xd1, 0xf0, 0x24, 0x33, 0x62, 0x72, 0x82, 0x09, 0x0a, 0x16, 0x17, 0x18, 0x19, 0x1a, 0x25, 0x26, 0x27, 0x28,
+            0x29, 0x2a, 0x34, 0x35, 0x36, 0x37, 0x38, 0x39, 0x3a, 0x43, 0x44, 0x45, 0x46, 0x47, 0x48, 0x49, 0x4a, 0x53, 0x54, 0x55, 0x56, 0x57, 0x58, 0x59,
+            0x5a, 0x63, 0x64, 0x65, 0x66, 0x67, 0x68, 0x69, 0x6a, 0x73, 0x74, 0x75, 0x76, 0x77, 0x78, 0x79, 0x7a, 0x83, 0x84, 0x85, 0x86, 0x87, 0x88, 0x89,
+            0x8a, 0x92, 0x93, 0x94, 0x95, 0x96, 0x97, 0x98, 0x99, 0x9a, 0xa2, 0xa3, 0xa4, 0xa5, 0xa6, 0xa7, 0xa8, 0xa9, 0xaa, 0xb2, 0xb3, 0xb4, 0xb5, 0xb6,
+            0xb7, 0xb8, 0xb9, 0xba, 0xc2, 0xc3, 0xc4, 0xc5, 0xc6, 0xc7, 0xc8, 0xc9, 0xca, 0xd2, 0xd3, 0xd4, 0xd5, 0xd6, 0xd7, 0xd8, 0xd9, 0xda, 0xe1, 0xe2,
+            0xe3, 0xe4, 0xe5, 0xe6, 0xe7, 0xe8, 0xe9, 0xea, 0xf1, 0xf2, 0xf3, 0xf4, 0xf5, 0xf6, 0xf7, 0xf8, 0xf9, 0xfa))
+AC_CHROMA = ((0, 2, 1, 2, 4, 4, 3, 4, 7, 5, 4, 4, 0, 1, 2, 0x77),
+             (0x00, 0x01, 0x02, 0x03, 0x11, 0x04, 0x05, 0x21, 0x31, 0x06, 0x12, 0x41, 0x51, 0x07, 0x61, 0x71, 0x13, 0x22, 0x32, 0x81, 0x08, 0x14, 0x42, 0x91,
+              0xa1, 0xb1, 0xc1, 0x09, 0x23, 0x33, 0x52, 0xf0, 0x15, 0x62, 0x72, 0xd1, 0x0a, 0x16, 0x24, 0x34, 0xe1, 0x25, 0xf1, 0x17, 0x18, 0x19, 0x1a, 0x26,
+              0x27, 0x28, 0x29, 0x2a, 0x35, 0x36, 0x37, 0x38, 0x39, 0x3a, 0x43, 0x44, 0x45, 0x46, 0x47, 0x48, 0x49, 0x4a, 0x53, 0x54, 0x55, 0x56, 0x57, 0x58,
+              0x59, 0x5a, 0x63, 0x64, 0x65, 0x66, 0x67, 0x68, 0x69, 0x6a, 0x73, 0x74, 0x75, 0x76, 0x77, 0x78, 0x79, 0x7a, 0x82, 0x83, 0x84, 0x85, 0x86, 0x87,
+              0x88, 0x89, 0x8a, 0x92, 0x93, 0x94, 0x95, 0x96, 0x97, 0x98, 0x99, 0x9a, 0xa2, 0xa3, 0xa4, 0xa5, 0xa6, 0xa7, 0xa8, 0xa9, 0xaa, 0xb2, 0xb3, 0xb4,
+              0xb5, 0xb6, 0xb7, 0xb8, 0xb9, 0xba, 0xc2, 0xc3, 0xc4, 0xc5, 0xc6, 0xc7, 0xc8, 0xc9, 0xca, 0xd2, 0xd3, 0xd4, 0xd5, 0xd6, 0xd7, 0xd8, 0xd9, 0xda,
+              0xe2, 0xe3, 0xe4, 0xe5, 0xe6, 0xe7, 0xe8, 0xe9, 0xea, 0xf2, 0xf3, 0xf4, 0xf5, 0xf6, 0xf7, 0xf8, 0xf9, 0xfa))
+HUFFMAN = (DC_LUMA, AC_LUMA, DC_CHROMA, AC_CHROMA)
+MAX_RESTART_INTERVAL = 32               # EG3D_JPEG_MAX_RESTART: one wave codes an interval out of an LDS bit buffer sized for this many MCUs
+
+
+def huffman_codes(bits, vals):
+    """{symbol: (code, length)} of a (BITS, HUFFVAL) table: canonical codes in order of increasing length (T.81 Annex C)."""
+    out, code, k = {}, 0, 0
+    for length in range(1, 17):
+        for _ in range(bits[length - 1]):
+            out[vals[k]] = (code, length)
+            code += 1
+            k += 1
+        code <<= 1
+    return out
+
+
+def jpeg_tables(quality: int) -> Tuple[Tuple[int, ...], Tuple[int, ...]]:
+    """(luma, chroma) quantisation tables in natural order for a libjpeg quality 1..100: jpeg_quality_scaling, then
+    (base * scale + 50) / 100 clamped to 1..255 (jpeg_add_quant_table with force_baseline)."""
+    q = min(max(int(quality), 1), 100)
+    scale = 5000 // q if q < 50 else 200 - 2 * q
+    return tuple(tuple(min(max((b * scale + 50) // 100, 1), 255) for b in base) for base in (QUANT_LUMA, QUANT_CHROMA))
+
+
+def default_restart_interval(height: int, width: int, subsampling: str = '420', channels: int = 3) -> int:
+    """MCUs per row, capped at MAX_RESTART_INTERVAL."""
+    mcu = 16 if (channels == 3 and subsampling == '420') else 8
+    return min(-(-int(width) // mcu), MAX_RESTART_INTERVAL)
+
+
+def _segment(marker: int, payload: bytes) -> bytes:
+    return struct.pack('>BBH', 0xFF, marker, len(payload) + 2) + payload
+
+
+def jpeg_header(height: int, width: int, quality: int = 90, subsampling: str = '420', restart_interval: Optional[int] = None, channels: int = 3) -> bytes:
+    """Everything of a baseline JFIF file in front of the entropy-coded data: SOI, APP0 'JFIF' 1.01, two DQT (luma id 0, chroma id 1, zigzag
+    order), SOF0, four DHT (DC/AC luma, DC/AC chroma), DRI, SOS.  channels = 1 (grey): one component, the same tables."""
+    if subsampling not in ('420', '444') or channels not in (1, 3):
+        raise ValueError(f"jpeg_header: subsampling '420' | '444', channels 1 | 3, got {subsampling!r}, {channels}")
+    if not (1 <= height <= 65535 and 1 <= width <= 65535):
+        raise ValueError(f'jpeg_header: sides 1..65535, got {height} x {width}')
+    R = default_restart_interval(height, width, subsampling, channels) if restart_interval is None else int(restart_interval)
+    if not 1 <= R <= MAX_RESTART_INTERVAL:
+        raise ValueError(f'jpeg_header: restart interval 1..{MAX_RESTART_INTERVAL}, got {R}')
+    ql, qc = jpeg_tables(quality)
+    h = b'\xff\xd8' + _segment(0xE0, b'JFIF\x00\x01\x01\x00\x00\x01\x00\x01\x00\x00')
+    for tid, tab in ((0, ql), (1, qc)):
+        h += _segment(0xDB, bytes([tid]) + bytes(tab[ZIGZAG[k]] for k in range(64)))
+    ysamp = 0x22 if (channels == 3 and subsampling == '420') else 0x11
+    comps = [(1, ysamp, 0)] + ([(2, 0x11, 1), (3, 0x11, 1)] if channels == 3 else [])
+    h += _segment(0xC0, struct.pack('>BHHB', 8, height, width, len(comps)) + b''.join(bytes(c) for c in comps))
+    for tc_th, (bits, vals) in zip((0x00, 0x10, 0x01, 0x11), HUFFMAN):
+        h += _segment(0xC4, bytes([tc_th]) + bytes(bits) + bytes(vals))
+    h += _segment(0xDD, struct.pack('>H', R))
+    h += _segment(0xDA, bytes([len(comps)]) + b''.join(bytes([cid, 0x00 if cid == 1 else 0x11]) for cid, _, _ in comps) + b'\x00\x3f\x00')
+    return h
+
+
+# ---- containers ------------------------------------------------------------------------------------------------------------------------------
+class MjpegAviWriter:
+    """Motion-JPEG AVI 1.0: RIFF 'AVI ' { LIST 'hdrl' { 'avih', LIST 'strl' { 'strh' vids/MJPG, 'strf' BITMAPINFOHEADER } }, LIST 'movi' { '00dc'
+    chunks, each padded to an even length }, 'idx1' }.  write() appends one complete JFIF file per frame; close() writes the index and patches
+    the RIFF / movi sizes and the frame counts.  One RIFF chunk: files up to 4 GiB."""
+    _AVIH, _STRH_LEN, _MOVI = 32, 108 + 32, 212        # offsets of avih's payload, strh's dwLength and the 'movi' LIST header (fixed layout below)
+
+    def __init__(self, path: str, width: int, height: int, fps: int = 60):
+        self.path, self.width, self.height, self.fps = path, int(width), int(height), int(fps)
+        if self.fps < 1 or self.width < 1 or self.height < 1:
+            raise ValueError('MjpegAviWriter: width, height, fps >= 1')
+        self._index: List[Tuple[int, int]] = []       # (offset from the 'movi' fourcc, size) per frame
+        self._max = 0
+        self._f = open(path, 'wb')
+        avih = struct.pack('<14I', 1000000 // self.fps, 0, 0, 0x10, 0, 0, 1, 0, self.width, self.height, 0, 0, 0, 0)       # AVIF_HASINDEX
+        strh = struct.pack('<4s4sIHHIIIIIIIIhhhh', b'vids', b'MJPG', 0, 0, 0, 0, 1, self.fps, 0, 0, 0, 0xFFFFFFFF, 0, 0, 0, self.width, self.height)
+        strf = struct.pack('<IiiHH4sIiiII', 40, self.width, self.height, 1, 24, b'MJPG', self.width * self.height * 3, 0, 0, 0, 0)
+        strl = b'strl' + self._chunk(b'strh', strh) + self._chunk(b'strf', strf)
+        hdrl = b'hdrl' + self._chunk(b'avih', avih) + self._chunk(b'LIST', strl)
+        head = b'RIFF' + struct.pack('<I', 0) + b'AVI ' + self._chunk(b'LIST', hdrl) + b'LIST' + struct.pack('<I', 0) + b'movi'
+        assert len(head) == self._MOVI + 12 and head[self._AVIH - 8:self._AVIH - 4] == b'avih', len(head)
+        self._f.write(head)
+        self._pos = 4                                  # bytes of the movi LIST payload so far (its fourcc)
+
+    @staticmethod
+    def _chunk(fourcc: bytes, payload: bytes) -> bytes:
+        return fourcc + struct.pack('<I', len(payload)) + payload + (b'\x00' if len(payload) & 1 else b'')
+
+    def write(self, frame_bytes) -> None:
+        data = bytes(frame_bytes)
+        self._index.append((self._pos, len(data)))
+        self._max = max(self._max, len(data))
+        self._f.write(self._chunk(b'00dc', data))
+        self._pos += 8 + len(data) + (len(data) & 1)
+
+    def close(self) -> None:
+        if self._f is None:
+            return
+        f, n = self._f, len(self._index)
+        f.write(b'idx1' + struct.pack('<I', 16 * n) + b''.join(struct.pack('<4sIII', b'00dc', 0x10, off, size) for off, size in self._index))     # AVIIF_KEYFRAME
+        end = f.tell()
+        f.seek(4)
+        f.write(struct.pack('<I', end - 8))
+        f.seek(self._AVIH + 4)                         # avih dwMaxBytesPerSec, then dwTotalFrames and dwSuggestedBufferSize
+        f.write(struct.pack('<I', self._max * self.fps))
+        f.seek(self._AVIH + 16)
+        f.write(struct.pack('<I', n))
+        f.seek(self._AVIH + 28)
+        f.write(struct.pack('<I', self._max))
+        f.seek(self._STRH_LEN)
+        f.write(struct.pack('<II', n, self._max))      # strh dwLength, dwSuggestedBufferSize
+        f.seek(self._MOVI + 4)
+        f.write(struct.pack('<I', self._pos))
+        f.close()
+        self._f = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
+def write_png(path: str, u8_hwc) -> None:
+    """8-bit PNG of a uint8 [H,W,3] (RGB) or [H,W] / [H,W,1] (grey) array: IHDR, one IDAT (filter 0 rows, zlib), IEND."""
+    a = u8_hwc.detach().cpu().numpy() if isinstance(u8_hwc, torch.Tensor) else np.asarray(u8_hwc)
+    if a.ndim == 2:
+        a = a[:, :, None]
+    if a.dtype != np.uint8 or a.ndim != 3 or a.shape[2] not in (1, 3) or a.shape[0] < 1 or a.shape[1] < 1:
+        raise ValueError(f'write_png: uint8 [H,W,3] or [H,W], got {a.dtype} {a.shape}')
+    hh, ww, ch = a.shape
+    rows = np.zeros((hh, 1 + ww * ch), np.uint8)
+    rows[:, 1:] = a.reshape(hh, ww * ch)
+
+    def chunk(tag, payload):
+        return struct.pack('>I', len(payload)) + tag + payload + struct.pack('>I', zlib.crc32(tag + payload) & 0xFFFFFFFF)
+    with open(path, 'wb') as f:
+        f.write(b'\x89PNG\r\n\x1a\n' + chunk(b'IHDR', struct.pack('>IIBBBBB', ww, hh, 8, 2 if ch == 3 else 0, 0, 0, 0)) +
+                chunk(b'IDAT', zlib.compress(rows.tobytes(), 6)) + chunk(b'IEND', b''))
+
+
+# ---- the per-image outputs -----------------------------------------------------------------------------------------------------------------------
+@torch.no_grad()
+def write_orbit_video(G, ws: torch.Tensor, path: str, num_frames: int = 240, image_mode: str = 'image', fps: int = 60, quality: int = 90,
+                      batch: int = 16, **synthesis_kwargs) -> int:
+    """gen_interp_video for one latent: inference.render_orbit's frames, `batch` at a time through hipops.jpeg_encode (4:2:0; grey for
+    image_depth), one device-to-host copy per batch, into a Motion-JPEG AVI at `path`.  Returns the number of frames written."""
+    from .hipops import jpeg_encode
+    from .inference import render_orbit
+    if batch < 1:
+        raise ValueError('write_orbit_video: batch >= 1')
+    writer, pending, n = None, [], 0
+
+    def flush():
+        nonlocal writer, n
+        data, offsets = jpeg_encode(torch.stack(pending), quality=quality)
+        host, off = data.cpu().numpy(), offsets.tolist()                 # (offsets are already on the host: one copy, the bytes)
+        if writer is None:
+            writer = MjpegAviWriter(path, pending[0].shape[-1], pending[0].shape[-2], fps=fps)
+        for i in range(len(pending)):
+            writer.write(host[off[i]:off[i + 1]].tobytes())
+        n += len(pending)
+        pending.clear()
+    try:
+        for frame in render_orbit(G, ws, num_frames=num_frames, image_mode=image_mode, **synthesis_kwargs):
+            pending.append(frame.float().clone())                          # (the frame may be a view of a buffer the next render reuses)
+            if len(pending) == batch:
+                flush()
+        if pending:
+            flush()
+    finally:
+        if writer is not None:
+            writer.close()
+    return n
+
+
+def small_eyes(coeff: int = 8) -> List[Tuple[float, float, float]]:
+    """gen_eyes(num='small'), base_coach.py:252-271: right, centre, left on the unit circle of the x-y plane, pi / coeff off the y axis."""
+    x, y = math.sin(math.pi / coeff), math.cos(math.pi / coeff)
+    return [(x, y, 0.0), (0.0, 1.0, 0.0), (-x, y, 0.0)]
+
+
+def look_at_small(radius: float = 2.7) -> torch.Tensor:
+    """look_at(num='small'), base_coach.py:216-249: fp32 [3,16] cam2world matrices (row-major 4 x 4) of the right / centre / left views.
+    Per eye: z = eye, x = up x z normalised (up = (0,0,1)), y = z x x normalised, M = [x y z] as columns; the EG3D convention is the rows
+    (-M0, -M2, -M1), and the camera sits at -radius times that matrix's third column."""
+    up = torch.tensor([0., 0., 1.])
+    mats = []
+    for eye in small_eyes():
+        z_axis = torch.tensor(eye, dtype=torch.float32)
+        x_axis = torch.linalg.cross(up, z_axis)
+        x_axis = x_axis / torch.norm(x_axis)
+        y_axis = torch.linalg.cross(z_axis, x_axis)
+        y_axis = y_axis / torch.norm(y_axis)
+        mat = torch.stack([x_axis, y_axis, z_axis], dim=-1)
+        rot = torch.stack([-mat[0], -mat[2], -mat[1]], dim=0)
+        loc = -rot[:, 2] * radius
+        mats.append(torch.cat([torch.cat([rot, loc.unsqueeze(1)], dim=1).reshape(12), torch.tensor([0., 0., 0., 1.])]))
+    return torch.stack(mats)
+
+
+@torch.no_grad()
+def pivot_grid(G, ws: torch.Tensor, cam: torch.Tensor, target: torch.Tensor, **synthesis_kwargs) -> torch.Tensor:
+    """uint8 [H',W',3] on the device: the reference's forward(ws, needs_img_grid='small', grid_num=5, need_gt_ingrid=(target, cam)) after its
+    (grid * 127.5 + 128).clamp(0, 255).to(uint8): target, the render at `cam`, and the right / centre / left look_at views, one row of five
+    tiled as make_grid(nrow=5, padding=2) (hipops.image_grid_u8; make_grid's float padding 0 is the grey 128 here).
+    Rendered with noise_mode='const': the reference calls G.synthesis with its default 'random', which would make the file differ from run
+    to run; everything else (full ws, intrinsics 4.2647 / 0.5) is the reference's.  The renderer's stratified-sampling draws are still random
+    unless render_uniforms=(u1, u2) is among the synthesis kwargs."""
+    from .hipops import image_grid_u8
+    dev = ws.device
+    K = torch.tensor([4.2647, 0, 0.5, 0, 4.2647, 0.5, 0, 0, 1.])
+    cams = [cam[:1].to(dev).float()] + [torch.cat([m, K]).unsqueeze(0).to(dev) for m in look_at_small()]
+    kw = dict(noise_mode='const', **synthesis_kwargs)
+    images = [target[:1].to(dev).float()]
+    for i, c in enumerate(cams):
+        images.append(G.synthesis(ws[:1], c, cache_backbone=(i == 0), use_cached_backbone=(i > 0), **kw)['image'].float())
+    return image_grid_u8(torch.cat(images, 0), nrow=5, padding=2, pad_value=128)

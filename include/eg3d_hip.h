@@ -1145,6 +1145,54 @@ int eg3d_sym_eig(const float* a, int n, float* evals, float* evecs, int max_swee
  *   offset by padding; borders and unused cells = pad_value (0..255).  padding = 0: the plain tiling of gen_videos.layout_grid.  NaN undefined. */
 int eg3d_image_grid_u8(const float* img, int N, int H, int W, int nrow, int padding, int pad_value, uint8_t* out, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Baseline JPEG encoder (media export: the frames of gen_interp_video's orbit, gen_videos.py:74-146; csrc/jpeg.hip).
+ *   img: contiguous [N,C,H,W], C = 3 (RGB) or 1 (grey), H, W >= 1; dtype EG3D_JPEG_F32 = fp32 in [-1,1], quantised as eg3d_image_grid_u8
+ *   (uint8(clamp(x * 127.5 + 128, 0, 255)), truncated), or EG3D_JPEG_U8 taken as is.  Output: N complete JFIF files back to back.
+ *   Integer arithmetic throughout (a host restatement equals it bit for bit):
+ *     Y  = (19595 R + 38470 G + 7471 B + 32768) >> 16,  Cb = (-11059 R - 21709 G + 32768 B + 8388608 + 32767) >> 16,
+ *     Cr = (32768 R - 27439 G - 5329 B + 8388608 + 32767) >> 16; grey: Y = the channel;
+ *     the full-resolution planes are extended by replicating the last row / column to a multiple of the MCU (8; 16 with 4:2:0);
+ *     4:2:0 chroma = (a + b + c + d + 2) >> 2 per 2 x 2 block;  s = p - 128;  T = (CI S + 1024) >> 11;  D = (T CI^T + 16384) >> 15 (arithmetic
+ *     shifts, CI = jpeg_ci of csrc/jpeg_tables.h);  q = sign(D) ((|D| + (Q >> 1)) / Q), Q = the Annex K table scaled by `quality` as libjpeg's
+ *     jpeg_quality_scaling (clamped to 1..255);  Annex K Huffman tables;  one interleaved scan, 4:2:0 MCU = Y00 Y01 Y10 Y11 Cb Cr.
+ *   Restart interval R MCUs (0 = MCUs per row capped at EG3D_JPEG_MAX_RESTART; at most EG3D_JPEG_MAX_RESTART): every interval is coded on
+ *   its own (DC prediction restarts, the last byte is filled with 1-bits, 0xFF is followed by 0x00) and followed by RSTm, m = interval index
+ *   mod 8, the last one by EOI.  `header` (device, header_bytes): everything of the file up to and including SOS, identical for the N frames;
+ *   the caller builds it for the same H, W, C, subsampling, quality and R (inv3d_amd/video.py jpeg_header).
+ *   No atomics on global memory and no floating-point sums: bit-identical between runs and between the two builds.
+ *   Protocol:
+ *     eg3d_jpeg_query_workspace  host only: workspace bytes (coefficients + one worst-case slot per interval: a block is at most
+ *                                22 + 63 * 26 bits, doubled by byte stuffing, + the marker)
+ *     eg3d_jpeg_encode           three launches: fills the workspace and writes offsets[0..N] (device int64: frame n is out[offsets[n] ..
+ *                                offsets[n+1]), offsets[N] = the total)
+ *     (host reads offsets[N]: one synchronise; allocates out)
+ *     eg3d_jpeg_pack             one launch: headers and interval slots into out, never beyond out_capacity
+ */
+#define EG3D_JPEG_F32 0
+#define EG3D_JPEG_U8 1
+#define EG3D_JPEG_444 0
+#define EG3D_JPEG_420 1
+#define EG3D_JPEG_MAX_RESTART 32
+typedef struct eg3d_jpeg_params {
+    const void* img;                   /* [N,C,H,W] */
+    const uint8_t* header;             /* device, header_bytes */
+    void* workspace;                   /* eg3d_jpeg_query_workspace's bytes, 16-byte aligned */
+    int64_t workspace_bytes;
+    int64_t* offsets;                  /* device int64[N+1] */
+    uint8_t* out;                      /* pack: out_capacity bytes */
+    int64_t out_capacity;
+    int32_t dtype;                     /* EG3D_JPEG_F32 | EG3D_JPEG_U8 */
+    int32_t N, C, H, W;
+    int32_t subsampling;               /* EG3D_JPEG_444 | EG3D_JPEG_420 (ignored for C = 1) */
+    int32_t quality;                   /* 1..100 */
+    int32_t restart_interval;          /* MCUs; 0 = default */
+    int32_t header_bytes;
+} eg3d_jpeg_params;
+int eg3d_jpeg_query_workspace(const eg3d_jpeg_params* p, int64_t* workspace_bytes);
+int eg3d_jpeg_encode(const eg3d_jpeg_params* p, void* stream);
+int eg3d_jpeg_pack(const eg3d_jpeg_params* p, void* stream);
+
 /* Measurement aid (bench.py): a register-only v_mfma_f32_32x32x16_f16 loop on caller-supplied fp16 data -- what the matrix pipe sustains on
  * this chip at its current power / clock state, timed inside the benchmark run.  in: 4096 x 8 fp16 (64 KiB); out: blocks x 256 floats;
  * executes blocks x 4 waves x iters x 24 MFMAs of 32 x 32 x 16.  No reference counterpart. */

@@ -1,0 +1,53 @@
+"""Orbit video from the command line: a pivot latent in, a Motion-JPEG AVI out (gen_interp_video, gen_videos.py:74-146, as
+single_id_coach.py:61-62,84-85 calls it), frames encoded by the GPU JPEG encoder of this package (inv3d_amd/video.py, csrc/jpeg.hip).
+
+  python tools/render_video.py --ws pivot_ws.npy --out orbit.avi [--weights G.safetensors] [--depth] [--frames 240] [--fps 60] [--quality 90]
+
+--weights: a generator archive (inv3d_amd.weights, tools/convert_eg3d_pickle.py); without it, the full-size synthetic generator
+(inv3d_amd.synthetic, seed --seed).  --ws: a [1, num_ws, w_dim] (or [num_ws, w_dim]) .npy latent, e.g. the coach's {image}_ws.npy.
+--depth renders image_depth (grey frames) instead of the colour image."""
+import argparse
+import os
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, '3dgan-inversion_amd'))
+
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__.splitlines()[0])
+    ap.add_argument('--ws', required=True, help='latent .npy, [1, num_ws, w_dim] or [num_ws, w_dim]')
+    ap.add_argument('--out', required=True, help='output .avi')
+    ap.add_argument('--weights', default=None, help='generator archive; default: the synthetic full-size generator')
+    ap.add_argument('--seed', type=int, default=0, help='synthetic generator weights seed')
+    ap.add_argument('--depth', action='store_true', help="render image_depth instead of image")
+    ap.add_argument('--frames', type=int, default=240)
+    ap.add_argument('--fps', type=int, default=60)
+    ap.add_argument('--quality', type=int, default=90)
+    ap.add_argument('--batch', type=int, default=16, help='frames per encoder call')
+    a = ap.parse_args()
+    from inv3d_amd import video as V
+    dev = torch.device('cuda')
+    if a.weights:
+        from inv3d_amd.weights import load_generator
+        G = load_generator(a.weights, device=dev)
+    else:
+        from inv3d_amd import synthetic as S
+        G = S.make_generator(device=dev)
+        S.load_synthetic_weights(G, seed=a.seed)
+    ws = torch.from_numpy(np.load(a.ws)).float().to(dev)
+    if ws.dim() == 2:
+        ws = ws.unsqueeze(0)
+    t0 = time.perf_counter()
+    n = V.write_orbit_video(G, ws, a.out, num_frames=a.frames, image_mode='image_depth' if a.depth else 'image', fps=a.fps, quality=a.quality,
+                            batch=a.batch)
+    dt = time.perf_counter() - t0
+    print(f'{a.out}: {n} frames, {os.path.getsize(a.out)} bytes ({dt * 1e3:.1f} ms, {n / dt:.1f} frames/s)')
+
+
+if __name__ == '__main__':
+    main()

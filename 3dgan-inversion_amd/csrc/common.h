@@ -213,6 +213,9 @@ __device__ __forceinline__ float eg3d_row_group_sum(float s, int group) {
     return s;
 }
 
+// barrier that orders LDS traffic only (__syncthreads also drains the vector-memory counter: it would wait for prefetched global loads and for stores)
+__device__ __forceinline__ void eg3d_lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
+
 // XCD-aware block-id remap (bijective for any grid size): hardware places block b on XCD b % 8; give each XCD a
 // contiguous chunk of logical tiles so that tiles sharing operands share an L2.
 __device__ __forceinline__ int eg3d_xcd_remap(int bid, int nblocks) {

@@ -179,86 +179,137 @@ __global__ void __launch_bounds__(256, 2) conv_v2_s2adj_kernel(const eg3d_conv_v
 // g = upfirdn2d(dz, outer([1,3,3,1]) / 64, padding 2, gain) on [N, 2 Hi, 2 Wi, C] -> (2 Hi + 1) x (2 Wi + 1), written as the four parity images
 // in the split fp16 layout [N][piece][C/8][parity][Hp = Hi + 1][Wp = Wi + 1][8], range-normalised by the bound max|g| <= gain * max|dz|
 // (a non-negative filter of unit sum).  g[2a + py, 2b + px] = gain * sum_{i,j<4} k[i] k[j] dz[2a + py - 2 + i, 2b + px - 2 + j].
-// Block = FA cell rows x 32 cells x 64 channels.  Phase 1 (lanes along channels: whole 256-byte runs of a pixel): each thread walks the
-// 2 FA + 3 input rows of its (column, channel quad) and leaves the vertical sums of both row parities in LDS.  Phase 2 (lanes along cells:
-// 16-byte stores contiguous over a plane's row): horizontal sums, split, store.  The thread-per-(cell, octet) form without LDS measured
-// ~5x slower (32-byte reads from 64 different pixel rows per instruction, 16-byte stores into 16 different planes).
+// Phase 1 (lanes along channels: whole 256-byte runs of a pixel): each thread walks the input rows of its (column, channel quad) and leaves the
+// vertical sums of both row parities in LDS.  Phase 2 (lanes along cells: 16-byte stores contiguous over a plane's row): horizontal sums, split,
+// store.  The thread-per-(cell, octet) form without LDS measured ~5x slower (32-byte reads from 64 different pixel rows per instruction, 16-byte
+// stores into 16 different planes).
+// The pass is a column strip walked in bands: a block owns (image, 16 cells of a parity row, 64 channels, `seg_rows` cell rows) and
+// walks down it two cell rows (four dz rows) at a time; same arithmetic, element for element, as the one-shot 2 x 32-cell tile kernel it replaces (7 rows
+// loaded for 4, 72.9 KB of LDS, two blocks of four waves per CU).  A phase-1 thread keeps the last three dz rows of its (column, channel quad) in
+// registers (rolling window: a band loads 4 rows for 4), requests the next band's rows before this band's horizontal sums, split and stores, and
+// waits for them at the top of the next trip; the barriers order LDS only.  576 threads: 35 input columns x 16 quads = 560 phase-1 items, one per thread
+// (wave 8 holds the three halo columns and only loads); phase 2 = 2 cell rows x 2 row parities x 8 octets x 16 cells = 512 items on waves 0-7, lanes along
+// cells (16 x 16 bytes contiguous in a plane's row).  38 KB of LDS.
 #ifndef UE_XCD_REMAP
 #define UE_XCD_REMAP 1
 #endif
-constexpr int FA = 2, FW = 32, FCH = 64, FCOLS = 2 * FW + 3;        // input columns 2 b0 - 2 .. 2 b0 + 2 FW
-__global__ void __launch_bounds__(256) fir44_adjoint_split_kernel(const float* __restrict__ dz, const float* dz_amax, f16x8* __restrict__ out, float* scale_out,
-                                                                  int N, int Hi, int Wi, int C, int ldz, float gain) {
+constexpr int FA = 2, FCH = 64;                    // cell rows per band, channels per block
+constexpr int SA_FW = 16, SA_COLS = 2 * SA_FW + 3, SA_THREADS = 576, SA_BLOCKS_PER_CU = 2;
+
+__global__ void __launch_bounds__(SA_THREADS) fir44_adjoint_split_strip_kernel(const float* __restrict__ dz, const float* dz_amax, f16x8* __restrict__ out, float* scale_out,
+                                                                                int N, int Hi, int Wi, int C, int ldz, float gain, int seg_rows) {
     constexpr int PITCH = FCH + 4;
-    __shared__ __attribute__((aligned(16))) float V[FA * 2 * FCOLS * PITCH];          // [cell row][py][column][channel]
+    __shared__ __attribute__((aligned(16))) float V[FA * 2 * SA_COLS * PITCH];          // [cell row][py][column][channel]
     const float mul = range_mul(*dz_amax * gain);
     if (blockIdx.x == 0 && blockIdx.y == 0 && blockIdx.z == 0 && threadIdx.x == 0) *scale_out = mul;
     const int Hp = Hi + 1, Wp = Wi + 1, Ho = 2 * Hi, Wo = 2 * Wi;
-    const int tiles_x = (Wp + FW - 1) / FW, tiles_y = (Hp + FA - 1) / FA;
-    const int bid = UE_XCD_REMAP ? eg3d_xcd_remap(blockIdx.x, gridDim.x) : (int)blockIdx.x;       // vertical neighbours (3 shared input rows) on one XCD: see upconv_epilogue_kernel
-    const int n = bid / (tiles_x * tiles_y);
-    const int t = bid - n * tiles_x * tiles_y;
-    const int a0 = (t / tiles_x) * FA, b0 = (t % tiles_x) * FW;
+    const int tiles_x = (Wp + SA_FW - 1) / SA_FW, segs = (Hp + seg_rows - 1) / seg_rows;
+    const int bid = UE_XCD_REMAP ? eg3d_xcd_remap(blockIdx.x, gridDim.x) : (int)blockIdx.x;
+    const int n = bid / (tiles_x * segs);
+    const int t = bid - n * tiles_x * segs;
+    const int as = (t / tiles_x) * seg_rows, b0 = (t % tiles_x) * SA_FW;
+    const int ae = min(Hp, as + seg_rows);
     const int c0 = blockIdx.y * FCH;
     const float k[4] = {0.125f, 0.375f, 0.375f, 0.125f};
-    // ---- phase 1: vertical sums.  item = (column, channel quad): 67 x 16 items over 256 threads
-    for (int it = threadIdx.x; it < FCOLS * (FCH / 4); it += 256) {
-        const int col = it / (FCH / 4), c4 = it - col * (FCH / 4);
-        const int x = 2 * b0 - 2 + col;
-        float4 r[2 * FA + 3];
+    const int tid = threadIdx.x;
+    // phase-1 identity: (input column, channel quad); rows 2 a - 2 + q
+    const int col = tid >> 4, c4 = tid & 15;
+    const int x = 2 * b0 - 2 + col;
+    const bool ldok = col < SA_COLS && (unsigned)x < (unsigned)Wo;
+    const float* const zcol = dz + ((int64_t)n * Ho * Wo + (ldok ? x : 0)) * ldz + c0 + c4 * 4;
+    const int ylast = 2 * ae;                                 // last dz row this strip needs: 2 (ae - 1) + 2
+    auto ldrow = [&](int y) {
+        float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (ldok && (unsigned)y < (unsigned)Ho && y <= ylast) v = *reinterpret_cast<const float4*>(zcol + (int64_t)y * Wo * ldz);
+        return v;
+    };
+    float4 win[3], nxt[2 * FA];
 #pragma unroll
-        for (int q = 0; q < 2 * FA + 3; ++q) {
-            const int y = 2 * a0 - 2 + q;
-            r[q] = make_float4(0.f, 0.f, 0.f, 0.f);
-            if ((unsigned)y < (unsigned)Ho && (unsigned)x < (unsigned)Wo) r[q] = *reinterpret_cast<const float4*>(dz + ((int64_t)(n * Ho + y) * Wo + x) * ldz + c0 + c4 * 4);
-        }
+    for (int q = 0; q < 3; ++q) win[q] = ldrow(2 * as - 2 + q);
 #pragma unroll
-        for (int ar = 0; ar < FA; ++ar)
-#pragma unroll
-            for (int py = 0; py < 2; ++py) {
-                const int q0 = 2 * ar + py;                         // rows 2 (a0 + ar) + py - 2 + i  =  index q0 + i
-                float4 s;
-                s.x = (r[q0].x * k[0] + r[q0 + 1].x * k[1]) + (r[q0 + 2].x * k[2] + r[q0 + 3].x * k[3]);
-                s.y = (r[q0].y * k[0] + r[q0 + 1].y * k[1]) + (r[q0 + 2].y * k[2] + r[q0 + 3].y * k[3]);
-                s.z = (r[q0].z * k[0] + r[q0 + 1].z * k[1]) + (r[q0 + 2].z * k[2] + r[q0 + 3].z * k[3]);
-                s.w = (r[q0].w * k[0] + r[q0 + 1].w * k[1]) + (r[q0 + 2].w * k[2] + r[q0 + 3].w * k[3]);
-                *reinterpret_cast<float4*>(V + ((ar * 2 + py) * FCOLS + col) * PITCH + c4 * 4) = s;
-            }
-    }
-    __syncthreads();
-    // ---- phase 2: horizontal sums + split.  item = (cell row, py, octet, cell): lanes along the 32 cells
+    for (int q = 0; q < 2 * FA; ++q) nxt[q] = ldrow(2 * as + 1 + q);
+    // phase-2 identity: (cell row, py, octet, cell)
+    const int bl = tid % SA_FW, kl = (tid / SA_FW) % (FCH / 8), py = (tid / (SA_FW * (FCH / 8))) & 1, ar = tid / (2 * SA_FW * (FCH / 8));
+    const int b = b0 + bl;
     const float gm = gain * mul;
-    const int noct = C / 8;
-    for (int it = threadIdx.x; it < FA * 2 * (FCH / 8) * FW; it += 256) {
-        const int bl = it % FW;
-        int rest = it / FW;
-        const int kl = rest % (FCH / 8); rest /= (FCH / 8);
-        const int py = rest & 1, ar = rest >> 1;
-        const int a = a0 + ar, b = b0 + bl;
-        if (a >= Hp || b >= Wp) continue;
-        const float* vp = V + ((ar * 2 + py) * FCOLS + 2 * bl) * PITCH + kl * 8;           // columns 2 bl .. 2 bl + 4  <->  x = 2 b - 2 .. 2 b + 2
-        float v[5][8];
+    const int noct = C / 8, ko = c0 / 8 + kl;
+    // Stores are raw buffer stores on the image of batch item n; a lane without a cell stores outside the descriptor (dropped by the hardware): no branch
+    // around a store, so the compiler can count them -- the wait at the top of a band is vmcnt(4), for the prefetched rows, and not vmcnt(0), which would
+    // also wait for the previous band's stores to reach memory.  Four dropped stores in front of the loop put the first trip in the same state.
+    const int plane = Hp * Wp * 16;                           // bytes of one (piece, octet, parity) plane
+    const __amdgpu_buffer_rsrc_t ors = __builtin_amdgcn_make_buffer_rsrc(out + (int64_t)n * 2 * noct * 4 * Hp * Wp, 0, 2 * noct * 4 * plane, 0x00020000);
+    constexpr unsigned SA_OOB = 0x7ffffff0u;
+    auto store16 = [&](const f16x8& v, unsigned off) {
+        typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), ors, (int)off, 0, 0);          // default cache policy: nt stores cost the 512^2 instance 40 %
+    };
+    {
+        f16x8 zero;
 #pragma unroll
-        for (int j = 0; j < 5; ++j) {
-            const float4 lo = *reinterpret_cast<const float4*>(vp + j * PITCH), hi = *reinterpret_cast<const float4*>(vp + j * PITCH + 4);
-            v[j][0] = lo.x; v[j][1] = lo.y; v[j][2] = lo.z; v[j][3] = lo.w; v[j][4] = hi.x; v[j][5] = hi.y; v[j][6] = hi.z; v[j][7] = hi.w;
+        for (int q = 0; q < 8; ++q) zero[q] = (_Float16)0.f;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) store16(zero, SA_OOB - 16u * q);
+    }
+    for (int ab = as; ab < ae; ab += FA) {
+        // ---- phase 1: vertical sums of both row parities from the window + the rows requested one trip ago
+        if (col < SA_COLS) {
+            const float4 r[2 * FA + 3] = {win[0], win[1], win[2], nxt[0], nxt[1], nxt[2], nxt[3]};
+#pragma unroll
+            for (int a2 = 0; a2 < FA; ++a2)
+#pragma unroll
+                for (int p = 0; p < 2; ++p) {
+                    const int q0 = 2 * a2 + p;                         // rows 2 (ab + a2) + p - 2 + i  =  index q0 + i
+                    float4 s;
+                    s.x = (r[q0].x * k[0] + r[q0 + 1].x * k[1]) + (r[q0 + 2].x * k[2] + r[q0 + 3].x * k[3]);
+                    s.y = (r[q0].y * k[0] + r[q0 + 1].y * k[1]) + (r[q0 + 2].y * k[2] + r[q0 + 3].y * k[3]);
+                    s.z = (r[q0].z * k[0] + r[q0 + 1].z * k[1]) + (r[q0 + 2].z * k[2] + r[q0 + 3].z * k[3]);
+                    s.w = (r[q0].w * k[0] + r[q0 + 1].w * k[1]) + (r[q0 + 2].w * k[2] + r[q0 + 3].w * k[3]);
+                    *reinterpret_cast<float4*>(V + ((a2 * 2 + p) * SA_COLS + col) * PITCH + c4 * 4) = s;
+                }
+#pragma unroll
+            for (int q = 0; q < 3; ++q) win[q] = r[2 * FA + q];
         }
-        const int ko = c0 / 8 + kl;
+        // ---- the next band's rows: in flight under everything below
+        if (ab + FA < ae) {
+#pragma unroll
+            for (int q = 0; q < 2 * FA; ++q) nxt[q] = ldrow(2 * (ab + FA) + 1 + q);
+        }
+        eg3d_lds_barrier();
+        // ---- phase 2: horizontal sums + split
+        const int a = ab + ar;
+        const bool live = tid < FA * 2 * (FCH / 8) * SA_FW && a < ae && b < Wp;
+        f16x8 oh[2], ol[2];
+#pragma unroll
+        for (int px = 0; px < 2; ++px)
+#pragma unroll
+            for (int q = 0; q < 8; ++q) { oh[px][q] = (_Float16)0.f; ol[px][q] = (_Float16)0.f; }
+        if (live) {
+            const float* vp = V + ((ar * 2 + py) * SA_COLS + 2 * bl) * PITCH + kl * 8;           // columns 2 bl .. 2 bl + 4  <->  x = 2 b - 2 .. 2 b + 2
+            float v[5][8];
+#pragma unroll
+            for (int j = 0; j < 5; ++j) {
+                const float4 lo = *reinterpret_cast<const float4*>(vp + j * PITCH), hi = *reinterpret_cast<const float4*>(vp + j * PITCH + 4);
+                v[j][0] = lo.x; v[j][1] = lo.y; v[j][2] = lo.z; v[j][3] = lo.w; v[j][4] = hi.x; v[j][5] = hi.y; v[j][6] = hi.z; v[j][7] = hi.w;
+            }
+#pragma unroll
+            for (int px = 0; px < 2; ++px) {
+                const bool exists = (a < Hi || py == 0) && (b < Wi || px == 0);
+                float o[8];
+#pragma unroll
+                for (int q = 0; q < 8; ++q) {
+                    const float h = (v[px][q] * k[0] + v[px + 1][q] * k[1]) + (v[px + 2][q] * k[2] + v[px + 3][q] * k[3]);
+                    o[q] = exists ? h : 0.f;
+                }
+                split8(o, gm, oh[px], ol[px], 2048.f);
+            }
+        }
 #pragma unroll
         for (int px = 0; px < 2; ++px) {
-            const bool exists = (a < Hi || py == 0) && (b < Wi || px == 0);
-            float o[8];
-#pragma unroll
-            for (int q = 0; q < 8; ++q) {
-                const float h = (v[px][q] * k[0] + v[px + 1][q] * k[1]) + (v[px + 2][q] * k[2] + v[px + 3][q] * k[3]);
-                o[q] = exists ? h : 0.f;
-            }
-            f16x8 h, l;
-            split8(o, gm, h, l, 2048.f);
-            const int par = py * 2 + px;
-            out[((((int64_t)(n * 2 + 0) * noct + ko) * 4 + par) * Hp + a) * Wp + b] = h;
-            out[((((int64_t)(n * 2 + 1) * noct + ko) * 4 + par) * Hp + a) * Wp + b] = l;
+            const unsigned off = (unsigned)(((ko * 4 + py * 2 + px) * Hp + a) * Wp + b) * 16u;       // piece 0; piece 1 lies 4 noct planes further
+            store16(oh[px], live ? off : SA_OOB - 32u * px);
+            store16(ol[px], live ? off + (unsigned)(noct * 4 * plane) : SA_OOB - 32u * px - 16u);
         }
+        if (ab + FA < ae) eg3d_lds_barrier();          // this band's reads of V are over before the next band's vertical sums land
     }
 }
 
@@ -323,9 +374,13 @@ extern "C" int eg3d_fir44_adjoint_split(const float* dz, const float* dz_amax, v
     if (!dz || !dz_amax || !image || !scale_out || N <= 0 || Hi <= 0 || Wi <= 0 || C < 8 || (C & 7) || (ldz & 3) || ldz < C || !(gain > 0.f)) return EG3D_ERR_INVALID;
     if ((reinterpret_cast<uintptr_t>(dz) & 15) || (reinterpret_cast<uintptr_t>(image) & 15)) return EG3D_ERR_UNSUPPORTED;
     if (C % FCH) return EG3D_ERR_UNSUPPORTED;
-    const int tiles = N * eg3d_cdiv(Hi + 1, FA) * eg3d_cdiv(Wi + 1, FW);
-    hipLaunchKernelGGL(fir44_adjoint_split_kernel, dim3(tiles, C / FCH), dim3(256), 0, (hipStream_t)stream, dz, dz_amax,
-                       reinterpret_cast<f16x8*>(image), scale_out, N, Hi, Wi, C, ldz, gain);
+    if (eg3d_fir44_adjoint_split_bytes(1, Hi, Wi, C) > 0x7fffffe0ll) return EG3D_ERR_UNSUPPORTED;        // 32-bit offsets into one image's buffer descriptor
+    // as many row segments per strip as it takes to fill every CU's resident blocks in one round (256 CUs: a constant, no device query in a captured step)
+    const int strips = N * eg3d_cdiv(Wi + 1, SA_FW) * (C / FCH);
+    const int want = std::max(1, 256 * SA_BLOCKS_PER_CU / strips);
+    const int seg_rows = eg3d_cdiv(eg3d_cdiv(Hi + 1, std::min(want, eg3d_cdiv(Hi + 1, FA))), FA) * FA;
+    hipLaunchKernelGGL(fir44_adjoint_split_strip_kernel, dim3(N * eg3d_cdiv(Hi + 1, seg_rows) * eg3d_cdiv(Wi + 1, SA_FW), C / FCH), dim3(SA_THREADS), 0,
+                       (hipStream_t)stream, dz, dz_amax, reinterpret_cast<f16x8*>(image), scale_out, N, Hi, Wi, C, ldz, gain, seg_rows);
     EG3D_LAUNCH_CHECK();
     return EG3D_OK;
 }

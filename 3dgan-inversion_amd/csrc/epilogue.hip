@@ -167,15 +167,15 @@ __global__ void __launch_bounds__(256) epilogue_fwd_fir44_kernel(const float* __
 
 // ---- the up layers' epilogue through LDS, optionally writing the consumer's split operand image ---------------------------------------------
 // Same arithmetic as epilogue_fwd_fir44_kernel for a SEPARABLE 4-tap FIR (outer(k, k), the [1,3,3,1] filter of every up layer):
-//   phase 1 (lanes along channels, 256-byte runs of a pixel): each thread walks the TH + 3 input rows of its (column, channel quad) once and
-//           leaves the TH vertical sums in LDS -- every z element is loaded (TH + 3) / TH x (TW + 3) / TW = 1.6 times instead of 25 / 4 = 6.25;
+//   phase 1 (lanes along channels, 256-byte runs of a pixel): each thread walks the input rows of its (column, channel quad) and leaves the
+//           vertical sums of a band in LDS -- every z element is loaded about (TW + 3) / TW = 1.2 times instead of 25 / 4 = 6.25;
 //   phase 2 (lanes along channels): horizontal sums, demodulation, noise, bias, activation, gain, clamp; 16-byte stores; max|out|;
 //   phase 3 (SPLIT only; lanes along pixels): the activated tile, kept in LDS, is multiplied by the CONSUMER's styles and written as that
 //           layer's two-piece fp16 operand image (conv_v2.hip layout) -- the separate split pass (read 4 B + write 4 B per element) of the
 //           consumer disappears.  The image needs its range before the tile exists, so this form requires clamp >= 0 (the super-resolution
 //           head, conv_clamp = 256): |out| <= clamp is the bound; scale = the power of two that brings clamp * max|styles| to [2^13, 2^14).
 // Measured on MI355X, 513^2 x 128 -> 512^2 x 128: 94 us (2.9 TB/s) for the 25-load form.
-constexpr int UE_TH = 8, UE_TW = 16, UE_CH = 64, UE_COLS = UE_TW + 3;
+constexpr int UE_TW = 16, UE_CH = 64, UE_COLS = UE_TW + 3;
 // LDS pitches (floats).  V (vertical sums, read in phase 2 by 16 lanes per pixel x 4 consecutive pixels = one contiguous 1 KB run per wave-instruction when
 // the pitch is exactly 64: conflict-free; with the former 68 the ds_read_b128 lane groups straddled two pixels 4 banks apart -- LdsBankConflict 0.50).
 // O (activated tile of the SPLIT form, read in phase 3 with lanes along PIXELS): 68, so that consecutive pixels are 4 banks apart.
@@ -195,142 +195,204 @@ __device__ __forceinline__ float ue_range_mul(float amax) {
 #ifndef UE_XCD_REMAP
 #define UE_XCD_REMAP 1
 #endif
+__device__ __forceinline__ void lds_barrier() { eg3d_lds_barrier(); }        // (common.h: orders LDS traffic only, leaves vector-memory operations in flight)
+
+// ---- the pass as a column strip walked in bands ----------------------------------------------------------------------------------
+// A block owns (image, 16 output columns, 64 channels, `seg_rows` output rows) and walks down it US_TH rows at a time.  Same arithmetic, element for
+// element, as the one-shot 8 x 16 tile kernel it replaces (load tile + halo, barrier, compute, store, exit); what changed is when memory is touched:
+//   * rolling row window: a phase-1 thread keeps the last three input rows of its (column, channel quad) in registers, so a band LOADS US_TH rows, not
+//     US_TH + 3 -- every input row is loaded once per segment (the one-shot tiles: 11 rows for 8);
+//   * the rows (and the noise values) of band i + 1 are requested before band i's horizontal sums, epilogue, split and stores, and are waited for only
+//     at the top of the next trip: every barrier in the loop is lds_barrier, which leaves vector-memory operations in flight;
+//   * 320 threads: waves 0-3 hold the strip's 16 columns in phase 1 and do all of phases 2 and 3, wave 4 holds the three halo columns (48 lanes) and only
+//     loads -- 19 columns x 16 quads = 304 items is then one item per thread, the window is 7 float4 registers, and no wave walks two columns.
+//   19.5 KB of LDS (37 KB with the split tile): four blocks = 20 waves per CU (SPLIT: three, by registers).
+constexpr int US_TH = 4, US_THREADS = 320;
+constexpr int us_blocks_per_cu(bool split) { return split ? 3 : 4; }       // by registers: 108 (15 waves per CU) / 84 (20 waves)
+// Stores of the strip form are raw buffer stores on a descriptor of the block's image, and a lane without a pixel stores to an offset outside it (the
+// hardware drops it): NO branch around a store.  The compiler counts vector-memory operations statically; with stores under `if` it cannot know how many
+// follow the prefetched loads and waits for everything (vmcnt(0)) at the top of a band -- i.e. for the previous band's stores to reach memory.  With a
+// fixed number of stores per band (and as many dropped ones in front of the loop, so that the first trip looks like every other) the wait is vmcnt(stores
+// per band): it covers the loads and lets the stores drain behind the next band.
+typedef unsigned int ue_u32x4 __attribute__((ext_vector_type(4)));
+constexpr unsigned US_OOB = 0x7ffffff0u;                 // an image is at most 0x7fffffe0 bytes (launcher)
+template <class T>
+__device__ __forceinline__ void us_put16(const T& v, __amdgpu_buffer_rsrc_t rs, unsigned off) {
+    static_assert(sizeof(T) == 16, "us_put16");
+    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(ue_u32x4, v), rs, (int)off, 0, 0);      // default cache policy: nt stores measured equal on the SR sizes
+}
 template <bool SPLIT>
-__global__ void __launch_bounds__(256) upconv_epilogue_kernel(const float* __restrict__ z, float* __restrict__ out, int N, int H, int W, int C, int Hz, int Wz,
+__global__ void __launch_bounds__(US_THREADS) upconv_epilogue_strip_kernel(const float* __restrict__ z, float* __restrict__ out, int N, int H, int W, int C, int Hz, int Wz,
                                                              float k0, float k1, float k2, float k3, int pad0, float fir_gain, const float* __restrict__ d,
                                                              const float* __restrict__ noise, int64_t noise_nstride, const float* __restrict__ noise_strength,
                                                              const float* __restrict__ bias, float slope, float gain, float clamp, float* out_amax,
-                                                             const float* __restrict__ sp_scale_in, _Float16* __restrict__ sp_image, float* sp_scale_out) {
-    constexpr int UE_VFLOATS = UE_TH * UE_COLS * UE_PITCH, UE_OFLOATS = UE_TH * UE_TW * UE_OPITCH;
-    __shared__ __attribute__((aligned(16))) float V[UE_VFLOATS > UE_OFLOATS ? UE_VFLOATS : UE_OFLOATS];                       // vertical sums [row][column][channel]
-    float* const O = V;                  // activated tile (SPLIT): takes V's place once phase 2 has read it (41 KB of LDS: three blocks per CU, not two)
-    __shared__ float red[4];
-    const int tiles_x = (W + UE_TW - 1) / UE_TW, tiles_y = (H + UE_TH - 1) / UE_TH;
-    // (the hardware places block b on XCD b % 8: with the linear order a tile's vertical neighbours -- which re-read three of its input rows --
-    //  sit on other XCDs and miss their L2s; remapped, each XCD owns a band of consecutive tile rows)
-    const int bid = UE_XCD_REMAP ? eg3d_xcd_remap(blockIdx.x, gridDim.x) : (int)blockIdx.x;
-    const int n = bid / (tiles_x * tiles_y);
-    const int t = bid - n * tiles_x * tiles_y;
-    const int y0 = (t / tiles_x) * UE_TH, x0 = (t % tiles_x) * UE_TW;
+                                                             const float* __restrict__ sp_scale_in, _Float16* __restrict__ sp_image, float* sp_scale_out, int seg_rows) {
+    constexpr int VFLOATS = US_TH * UE_COLS * UE_PITCH, OFLOATS = US_TH * UE_TW * UE_OPITCH;
+    __shared__ __attribute__((aligned(16))) float V[VFLOATS];                    // vertical sums [row][column][channel]
+    __shared__ __attribute__((aligned(16))) float O[SPLIT ? OFLOATS : 4];        // activated tile (SPLIT), a region of its own: phase 2 writes it while other waves still read V
+    __shared__ __attribute__((aligned(16))) float S[SPLIT ? UE_CH : 4];          // the consumer's styles of this block's channels
+    __shared__ float red[US_THREADS / 64];
+    const int tiles_x = (W + UE_TW - 1) / UE_TW, segs = (H + seg_rows - 1) / seg_rows;
+    const int bid = UE_XCD_REMAP ? eg3d_xcd_remap(blockIdx.x, gridDim.x) : (int)blockIdx.x;       // an XCD owns consecutive segments: neighbours share halo columns / rows in its L2
+    const int n = bid / (tiles_x * segs);
+    const int t = bid - n * tiles_x * segs;
+    const int ys = (t / tiles_x) * seg_rows, x0 = (t % tiles_x) * UE_TW;
+    const int ye = min(H, ys + seg_rows);
     const int c0 = blockIdx.y * UE_CH;
     const float kk[4] = {k3, k2, k1, k0};                    // true convolution: tap i of the window meets filter element 3 - i
+    const int tid = threadIdx.x;
+    const bool worker = tid < 256;                           // (wave-uniform)
     float sp_mul = 1.f;
-    if (SPLIT) {         // max|consumer styles| (every block derives it from the same few KB): requested here, reduced behind phase 1's loads, published by phase 1's
-                         // barrier -- as a reduction + barrier of its own in front of phase 1 it was a dependent memory round trip per block
+    if (SPLIT) {         // max|consumer styles|: requested with the first loads, published by the first band's barrier
         float m = 0.f;
-        for (int i = threadIdx.x; i < N * C; i += 256) m = fmaxf(m, fabsf(sp_scale_in[i]));
-        sp_mul = m;      // (this thread's partial maximum until the barrier)
+        for (int i = tid; i < N * C; i += US_THREADS) m = fmaxf(m, fabsf(sp_scale_in[i]));
+        sp_mul = m;
     }
-    // the noise values of this thread's eight output pixels are requested here, with phase 1's loads: inside the phase-2 loop each was a load
-    // under a branch followed by its use -- eight memory round trips in sequence per block
-    constexpr int UE_ITEMS = UE_TH * UE_TW * (UE_CH / 4) / 256;
+    // phase-1 identity: (input column, channel quad)
+    const int col = tid >> 4, c4 = tid & 15, c = c0 + c4 * 4;
+    const int xin = x0 - pad0 + col;
+    const bool ldok = col < UE_COLS && (unsigned)xin < (unsigned)Wz;
+    const float* const zcol = z + ((int64_t)n * Hz * Wz + (ldok ? xin : 0)) * C + c;
+    const int ylast = ye + 2 - pad0;                         // last input row this strip needs
+    auto ldrow = [&](int y) {
+        float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (ldok && (unsigned)y < (unsigned)Hz && y <= ylast) v = ld4(zcol + (int64_t)y * Wz * C);
+        return v;
+    };
+    // phase-2 identity: output column tid >> 4 of every band row; noise values one band ahead (a valid address either way: no branch around the load, and
+    // the select that zeroes an absent value sits at the USE -- next to the load it would wait for it, and, in order, for the rows requested before it)
+    const int xo = x0 + col;
     const float strength = noise ? *noise_strength : 0.f;
-    float nzv[UE_ITEMS];
+    auto okn = [&](int y) { return noise != nullptr && worker && y < ye && xo < W; };
+    auto ldnoise = [&](int y) { return (noise != nullptr ? noise : z)[okn(y) ? (int64_t)n * noise_nstride + (int64_t)y * W + xo : 0]; };
+    float4 win[3], nxt[US_TH];
+    float nzv[US_TH];
 #pragma unroll
-    for (int k = 0; k < UE_ITEMS; ++k) {
-        const int pix = (threadIdx.x >> 4) + k * 16;
-        const int y = y0 + pix / UE_TW, x = x0 + pix % UE_TW;
-        const bool okp = noise != nullptr && y < H && x < W;
-        nzv[k] = (noise != nullptr ? noise : z)[okp ? (int64_t)n * noise_nstride + (int64_t)y * W + x : 0];        // (a valid address either way: no branch around the load)
-        if (!okp) nzv[k] = 0.f;
-    }
-    // ---- phase 1
-    for (int it = threadIdx.x; it < UE_COLS * (UE_CH / 4); it += 256) {
-        const int col = it / (UE_CH / 4), c4 = it - col * (UE_CH / 4);
-        const int x = x0 - pad0 + col;
-        float4 r[UE_TH + 3];
+    for (int q = 0; q < 3; ++q) win[q] = ldrow(ys - pad0 + q);
 #pragma unroll
-        for (int q = 0; q < UE_TH + 3; ++q) {
-            const int y = y0 - pad0 + q;
-            r[q] = make_float4(0.f, 0.f, 0.f, 0.f);
-            if ((unsigned)y < (unsigned)Hz && (unsigned)x < (unsigned)Wz) r[q] = ld4(z + ((int64_t)(n * Hz + y) * Wz + x) * C + c0 + c4 * 4);
-        }
-#pragma unroll
-        for (int oy = 0; oy < UE_TH; ++oy) {
-            float4 v;
-            v.x = (r[oy].x * kk[0] + r[oy + 1].x * kk[1]) + (r[oy + 2].x * kk[2] + r[oy + 3].x * kk[3]);
-            v.y = (r[oy].y * kk[0] + r[oy + 1].y * kk[1]) + (r[oy + 2].y * kk[2] + r[oy + 3].y * kk[3]);
-            v.z = (r[oy].z * kk[0] + r[oy + 1].z * kk[1]) + (r[oy + 2].z * kk[2] + r[oy + 3].z * kk[3]);
-            v.w = (r[oy].w * kk[0] + r[oy + 1].w * kk[1]) + (r[oy + 2].w * kk[2] + r[oy + 3].w * kk[3]);
-            *reinterpret_cast<float4*>(V + (oy * UE_COLS + col) * UE_PITCH + c4 * 4) = v;
-        }
-    }
+    for (int q = 0; q < US_TH; ++q) { nxt[q] = ldrow(ys - pad0 + 3 + q); nzv[q] = ldnoise(ys + q); }
+    float4 dv = make_float4(1.f, 1.f, 1.f, 1.f), bv = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (d != nullptr) dv = ld4(d + (int64_t)n * C + c);
+    if (bias != nullptr) bv = ld4(bias + c);
     if (SPLIT) {
         float m = sp_mul;
 #pragma unroll
         for (int o = 32; o >= 1; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
-        if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = m;
+        if ((tid & 63) == 0) red[tid >> 6] = m;
     }
-    __syncthreads();
-    if (SPLIT) {
-        sp_mul = ue_range_mul(clamp * fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3])));
-        if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) *sp_scale_out = sp_mul;
-    }
-    // ---- phase 2: item = (row, column, channel quad); a thread keeps its channel quad
-    const int c4 = threadIdx.x & 15, c = c0 + c4 * 4;
-    float4 dv = make_float4(1.f, 1.f, 1.f, 1.f), bv = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (d != nullptr) dv = ld4(d + (int64_t)n * C + c);
-    if (bias != nullptr) bv = ld4(bias + c);
+    constexpr int P3_ITEMS = US_TH * UE_TW * (UE_CH / 8) / 256;
+    if (SPLIT && tid < UE_CH) S[tid] = sp_scale_in[(int64_t)n * C + c0 + tid];       // read in phase 3 behind the first band's barriers
     float am = 0.f;
-    float4 keep[SPLIT ? UE_TH * UE_TW * (UE_CH / 4) / 256 : 1];
+    const int noct = C / 8, HW = H * W;
+    const __amdgpu_buffer_rsrc_t ors = __builtin_amdgcn_make_buffer_rsrc(out + (int64_t)n * HW * C, 0, HW * C * 4, 0x00020000);
+    const __amdgpu_buffer_rsrc_t irs = __builtin_amdgcn_make_buffer_rsrc(SPLIT ? sp_image + (int64_t)n * HW * C * 2 : nullptr, 0, SPLIT ? HW * C * 4 : 0, 0x00020000);
+    {   // as many dropped stores as a band issues: the loop is entered in the state its back edge leaves (see us_put16)
+        const float4 zero = make_float4(0.f, 0.f, 0.f, 0.f);
 #pragma unroll
-    for (int k = 0; k < UE_TH * UE_TW * (UE_CH / 4) / 256; ++k) {
-        const int pix = (threadIdx.x >> 4) + k * 16;                                  // 0 .. 127
-        const int oy = pix / UE_TW, ox = pix - oy * UE_TW;
-        const int y = y0 + oy, x = x0 + ox;
-        const float* vp = V + (oy * UE_COLS + ox) * UE_PITCH + c4 * 4;
-        const float4 a0 = *reinterpret_cast<const float4*>(vp), a1 = *reinterpret_cast<const float4*>(vp + UE_PITCH),
-                     a2 = *reinterpret_cast<const float4*>(vp + 2 * UE_PITCH), a3 = *reinterpret_cast<const float4*>(vp + 3 * UE_PITCH);
-        float4 v;
-        v.x = ((a0.x * kk[0] + a1.x * kk[1]) + (a2.x * kk[2] + a3.x * kk[3])) * fir_gain;
-        v.y = ((a0.y * kk[0] + a1.y * kk[1]) + (a2.y * kk[2] + a3.y * kk[3])) * fir_gain;
-        v.z = ((a0.z * kk[0] + a1.z * kk[1]) + (a2.z * kk[2] + a3.z * kk[3])) * fir_gain;
-        v.w = ((a0.w * kk[0] + a1.w * kk[1]) + (a2.w * kk[2] + a3.w * kk[3])) * fir_gain;
-        const bool ok = y < H && x < W;
-        const float nz = nzv[k] * strength;
-        v.x = act1<true>(v.x * dv.x + nz + bv.x, 0, slope, gain, clamp); v.y = act1<true>(v.y * dv.y + nz + bv.y, 0, slope, gain, clamp);
-        v.z = act1<true>(v.z * dv.z + nz + bv.z, 0, slope, gain, clamp); v.w = act1<true>(v.w * dv.w + nz + bv.w, 0, slope, gain, clamp);
-        if (ok) {
-            am = amax4(am, v);
-            st4(out + (((int64_t)n * H + y) * W + x) * C + c, v);
-        }
-        if (SPLIT) keep[k] = v;
+        for (int k = 0; k < (SPLIT ? 2 : 1) * US_TH; ++k) us_put16(zero, ors, US_OOB - 16u * k);
     }
-    if (SPLIT) {
-        __syncthreads();
+    for (int yb = ys; yb < ye; yb += US_TH) {
+        // ---- phase 1: vertical sums of this band from the window + the rows requested one trip ago
+        if (col < UE_COLS) {
+            const float4 r[US_TH + 3] = {win[0], win[1], win[2], nxt[0], nxt[1], nxt[2], nxt[3]};
 #pragma unroll
-        for (int k = 0; k < UE_TH * UE_TW * (UE_CH / 4) / 256; ++k)
-            *reinterpret_cast<float4*>(O + ((threadIdx.x >> 4) + k * 16) * UE_OPITCH + c4 * 4) = keep[k];
-        // ---- phase 3: item = (octet, pixel), lanes along the pixels of a tile row (16 x 16 bytes contiguous in a plane's row)
-        __syncthreads();
-        const int noct = C / 8;
-        const int64_t HW = (int64_t)H * W;
-        f16x8_t* img = reinterpret_cast<f16x8_t*>(sp_image);
-#pragma unroll
-        for (int k = 0; k < UE_TH * UE_TW * (UE_CH / 8) / 256; ++k) {
-            const int item = threadIdx.x + k * 256;
-            const int pix = item & (UE_TH * UE_TW - 1), kl = item >> 7;
-            const int oy = pix / UE_TW, ox = pix - oy * UE_TW;
-            const int y = y0 + oy, x = x0 + ox;
-            if (y >= H || x >= W) continue;
-            const float4 lo = *reinterpret_cast<const float4*>(O + pix * UE_OPITCH + kl * 8), hi = *reinterpret_cast<const float4*>(O + pix * UE_OPITCH + kl * 8 + 4);
-            const float* sr = sp_scale_in + (int64_t)n * C + c0 + kl * 8;
-            const float v[8] = {lo.x * sr[0], lo.y * sr[1], lo.z * sr[2], lo.w * sr[3], hi.x * sr[4], hi.y * sr[5], hi.z * sr[6], hi.w * sr[7]};
-            f16x8_t h, l;
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const float a = v[2 * q] * sp_mul, b = v[2 * q + 1] * sp_mul;
-                const ue_fp16x2 hh = __builtin_amdgcn_cvt_pkrtz(a, b);
-                const float ra = __builtin_amdgcn_fmed3f((a - (float)hh[0]) * 2048.f, -65504.f, 65504.f);
-                const float rb = __builtin_amdgcn_fmed3f((b - (float)hh[1]) * 2048.f, -65504.f, 65504.f);
-                h[2 * q] = (_Float16)hh[0]; h[2 * q + 1] = (_Float16)hh[1];
-                l[2 * q] = (_Float16)ra; l[2 * q + 1] = (_Float16)rb;
+            for (int oy = 0; oy < US_TH; ++oy) {
+                float4 v;
+                v.x = (r[oy].x * kk[0] + r[oy + 1].x * kk[1]) + (r[oy + 2].x * kk[2] + r[oy + 3].x * kk[3]);
+                v.y = (r[oy].y * kk[0] + r[oy + 1].y * kk[1]) + (r[oy + 2].y * kk[2] + r[oy + 3].y * kk[3]);
+                v.z = (r[oy].z * kk[0] + r[oy + 1].z * kk[1]) + (r[oy + 2].z * kk[2] + r[oy + 3].z * kk[3]);
+                v.w = (r[oy].w * kk[0] + r[oy + 1].w * kk[1]) + (r[oy + 2].w * kk[2] + r[oy + 3].w * kk[3]);
+                *reinterpret_cast<float4*>(V + (oy * UE_COLS + col) * UE_PITCH + c4 * 4) = v;
             }
-            const int ko = c0 / 8 + kl;
-            img[((int64_t)(n * 2 + 0) * noct + ko) * HW + (int64_t)y * W + x] = h;
-            img[((int64_t)(n * 2 + 1) * noct + ko) * HW + (int64_t)y * W + x] = l;
+#pragma unroll
+            for (int q = 0; q < 3; ++q) win[q] = r[US_TH + q];
         }
+        float nzc[US_TH];
+#pragma unroll
+        for (int q = 0; q < US_TH; ++q) nzc[q] = okn(yb + q) ? nzv[q] : 0.f;
+        // ---- the next band's rows and noise: in flight under everything below
+        if (yb + US_TH < ye) {
+#pragma unroll
+            for (int q = 0; q < US_TH; ++q) { nxt[q] = ldrow(yb + US_TH - pad0 + 3 + q); nzv[q] = ldnoise(yb + US_TH + q); }
+        }
+        lds_barrier();
+        if (SPLIT && yb == ys) {
+            float m = red[0];
+#pragma unroll
+            for (int w = 1; w < US_THREADS / 64; ++w) m = fmaxf(m, red[w]);
+            sp_mul = ue_range_mul(clamp * m);
+        }
+        // ---- phase 2: item = (band row k, column tid >> 4, channel quad)
+        float4 vv[US_TH];
+#pragma unroll
+        for (int k = 0; k < US_TH; ++k) vv[k] = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (worker) {
+#pragma unroll
+            for (int k = 0; k < US_TH; ++k) {
+                const int y = yb + k;
+                const float* vp = V + (k * UE_COLS + col) * UE_PITCH + c4 * 4;
+                const float4 a0 = *reinterpret_cast<const float4*>(vp), a1 = *reinterpret_cast<const float4*>(vp + UE_PITCH),
+                             a2 = *reinterpret_cast<const float4*>(vp + 2 * UE_PITCH), a3 = *reinterpret_cast<const float4*>(vp + 3 * UE_PITCH);
+                float4 v;
+                v.x = ((a0.x * kk[0] + a1.x * kk[1]) + (a2.x * kk[2] + a3.x * kk[3])) * fir_gain;
+                v.y = ((a0.y * kk[0] + a1.y * kk[1]) + (a2.y * kk[2] + a3.y * kk[3])) * fir_gain;
+                v.z = ((a0.z * kk[0] + a1.z * kk[1]) + (a2.z * kk[2] + a3.z * kk[3])) * fir_gain;
+                v.w = ((a0.w * kk[0] + a1.w * kk[1]) + (a2.w * kk[2] + a3.w * kk[3])) * fir_gain;
+                const float nz = nzc[k] * strength;
+                v.x = act1<true>(v.x * dv.x + nz + bv.x, 0, slope, gain, clamp); v.y = act1<true>(v.y * dv.y + nz + bv.y, 0, slope, gain, clamp);
+                v.z = act1<true>(v.z * dv.z + nz + bv.z, 0, slope, gain, clamp); v.w = act1<true>(v.w * dv.w + nz + bv.w, 0, slope, gain, clamp);
+                if (y < ye && xo < W) am = amax4(am, v);
+                vv[k] = v;
+                if (SPLIT) *reinterpret_cast<float4*>(O + (k * UE_TW + col) * UE_OPITCH + c4 * 4) = v;
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < US_TH; ++k)
+            us_put16(vv[k], ors, worker && yb + k < ye && xo < W ? (unsigned)((((yb + k) * W + xo) * C + c) * 4) : US_OOB - 16u * k);
+        if (SPLIT) {
+            lds_barrier();
+            // ---- phase 3: item = (octet, pixel), lanes along the pixels of a band row (16 x 16 bytes contiguous in a plane's row)
+            f16x8_t ph[P3_ITEMS], pl[P3_ITEMS];
+            unsigned poff[P3_ITEMS];
+#pragma unroll
+            for (int k = 0; k < P3_ITEMS; ++k) {
+                poff[k] = US_OOB;
+#pragma unroll
+                for (int q = 0; q < 8; ++q) { ph[k][q] = (_Float16)0.f; pl[k][q] = (_Float16)0.f; }
+            }
+            if (worker) {
+#pragma unroll
+                for (int k = 0; k < P3_ITEMS; ++k) {
+                    const int item = tid + k * 256;
+                    const int pix = item & (US_TH * UE_TW - 1), kl = item / (US_TH * UE_TW);
+                    const int oy = pix / UE_TW, ox = pix - oy * UE_TW;
+                    const int y = yb + oy, x = x0 + ox;
+                    if (y >= ye || x >= W) continue;
+                    const float4 lo = *reinterpret_cast<const float4*>(O + pix * UE_OPITCH + kl * 8), hi = *reinterpret_cast<const float4*>(O + pix * UE_OPITCH + kl * 8 + 4);
+                    const float* sr = S + kl * 8;
+                    const float v[8] = {lo.x * sr[0], lo.y * sr[1], lo.z * sr[2], lo.w * sr[3], hi.x * sr[4], hi.y * sr[5], hi.z * sr[6], hi.w * sr[7]};
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) {
+                        const float a = v[2 * q] * sp_mul, b = v[2 * q + 1] * sp_mul;
+                        const ue_fp16x2 hh = __builtin_amdgcn_cvt_pkrtz(a, b);
+                        const float ra = __builtin_amdgcn_fmed3f((a - (float)hh[0]) * 2048.f, -65504.f, 65504.f);
+                        const float rb = __builtin_amdgcn_fmed3f((b - (float)hh[1]) * 2048.f, -65504.f, 65504.f);
+                        ph[k][2 * q] = (_Float16)hh[0]; ph[k][2 * q + 1] = (_Float16)hh[1];
+                        pl[k][2 * q] = (_Float16)ra; pl[k][2 * q + 1] = (_Float16)rb;
+                    }
+                    poff[k] = (unsigned)(((c0 / 8 + kl) * HW + y * W + x) * 16);          // piece 0; piece 1 lies noct planes further
+                }
+            }
+#pragma unroll
+            for (int k = 0; k < P3_ITEMS; ++k) {
+                us_put16(ph[k], irs, poff[k] == US_OOB ? US_OOB - 32u * k : poff[k]);
+                us_put16(pl[k], irs, poff[k] == US_OOB ? US_OOB - 32u * k - 16u : poff[k] + (unsigned)(noct * HW * 16));
+            }
+        }
+        // this band's reads of V are over before the next band's vertical sums land (SPLIT: the barrier in front of phase 3 already says so, and O is not V)
+        if (!SPLIT && yb + US_TH < ye) lds_barrier();
     }
+    if (SPLIT && blockIdx.x == 0 && blockIdx.y == 0 && tid == 0) *sp_scale_out = sp_mul;
     commit_amax(am, out_amax);
 }
 
@@ -365,9 +427,6 @@ struct FinArgs { const float* z; const float* s; const float* addend; float* ds;
 // pieces are floating point, a scale that is a few octaves too cautious costs range at the bottom, not precision: |dz| <= gain * (max|dy| *
 // max_{n,c}(sum_o |wa[c][o]|) |s[n,c]| |d[n,c]|) + max|addend| * max |d|) since |act'| <= 1.  Every block derives it from the same few
 // hundred numbers.  512^2 x 128: 85 + 52 us (this pass + split pass) -> 61 us, and no fp32 dz at all when nobody else reads it.
-// barrier that orders LDS traffic only (__syncthreads also drains the vector-memory counter: it would wait for prefetched global loads)
-__device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-
 template <bool PWL, bool FIN, bool SPLIT = false>
 __global__ void __launch_bounds__(EPI_BWD_THREADS) epilogue_bwd_kernel(const FinArgs fin, const float* __restrict__ dout, const float* __restrict__ outv, float* __restrict__ dz,
                                                            int H, int W, int C4, const float* __restrict__ d, const float* __restrict__ noise,
@@ -1156,15 +1215,22 @@ extern "C" int eg3d_upconv_epilogue_fwd(const float* z, float* out, int N, int H
     const bool split = split_image != nullptr;
     if (split && (!split_in_scale || !split_scale_out || !(clamp >= 0.f))) return EG3D_ERR_INVALID;
     if ((reinterpret_cast<uintptr_t>(z) & 15) || (reinterpret_cast<uintptr_t>(out) & 15) || (split && (reinterpret_cast<uintptr_t>(split_image) & 15))) return EG3D_ERR_UNSUPPORTED;
-    const dim3 grid(N * eg3d_cdiv(H, UE_TH) * eg3d_cdiv(W, UE_TW), C / UE_CH);
     const float slope = eg3d_act_pwl_slope(act, alpha);
     hipStream_t st = (hipStream_t)stream;
+    if ((int64_t)H * W * C * 4 > 0x7fffffe0ll) return EG3D_ERR_UNSUPPORTED;        // 32-bit offsets into one image's buffer descriptor (an image of 2 GiB)
+    // A strip (image, 16 columns, 64 channels) is cut into as many row segments as it takes to give every CU its us_blocks_per_cu() resident
+    // blocks in ONE round (256 CUs: a constant, as epi_bwd_cap() -- no device query inside a captured step); each segment re-reads three input rows.
+    const int strips = N * eg3d_cdiv(W, UE_TW) * (C / UE_CH);
+    const int want = std::max(1, 256 * us_blocks_per_cu(split) / strips);
+    const int seg_rows = eg3d_cdiv(eg3d_cdiv(H, std::min(want, eg3d_cdiv(H, US_TH))), US_TH) * US_TH;
+    const dim3 sgrid(N * eg3d_cdiv(H, seg_rows) * eg3d_cdiv(W, UE_TW), C / UE_CH);
     if (split)
-        hipLaunchKernelGGL(upconv_epilogue_kernel<true>, grid, dim3(256), 0, st, z, out, N, H, W, C, Hz, Wz, k4[0], k4[1], k4[2], k4[3], pad0, fir_gain, d, noise,
-                           noise_nstride, noise_strength, bias, slope, gain, clamp, out_amax, split_in_scale, reinterpret_cast<_Float16*>(split_image), split_scale_out);
+        hipLaunchKernelGGL(upconv_epilogue_strip_kernel<true>, sgrid, dim3(US_THREADS), 0, st, z, out, N, H, W, C, Hz, Wz, k4[0], k4[1], k4[2], k4[3], pad0, fir_gain, d,
+                           noise, noise_nstride, noise_strength, bias, slope, gain, clamp, out_amax, split_in_scale, reinterpret_cast<_Float16*>(split_image),
+                           split_scale_out, seg_rows);
     else
-        hipLaunchKernelGGL(upconv_epilogue_kernel<false>, grid, dim3(256), 0, st, z, out, N, H, W, C, Hz, Wz, k4[0], k4[1], k4[2], k4[3], pad0, fir_gain, d, noise,
-                           noise_nstride, noise_strength, bias, slope, gain, clamp, out_amax, nullptr, nullptr, nullptr);
+        hipLaunchKernelGGL(upconv_epilogue_strip_kernel<false>, sgrid, dim3(US_THREADS), 0, st, z, out, N, H, W, C, Hz, Wz, k4[0], k4[1], k4[2], k4[3], pad0, fir_gain, d,
+                           noise, noise_nstride, noise_strength, bias, slope, gain, clamp, out_amax, nullptr, nullptr, nullptr, seg_rows);
     EG3D_LAUNCH_CHECK();
     return EG3D_OK;
 }

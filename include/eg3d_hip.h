@@ -305,7 +305,8 @@ int eg3d_conv2d_v3_s2adj(const eg3d_conv_v2_params* p, void* stream);
  * dz [N, 2 Hi, 2 Wi, ldz] NHWC fp32 (C used channels, C % 8 == 0) -- the (2 Hi + 1) x (2 Wi + 1) input of the data gradient above
  * (torch_utils/ops/upfirdn2d.py:258-268 applied to conv2d_resample.py:129) -- written as the four parity images [.][Hi + 1][Wi + 1] in the
  * split layout, range-normalised by the bound max|G| <= gain * max|dz| (dz_amax: device scalar max|dz|).  image:
- * eg3d_fir44_adjoint_split_bytes() bytes; scale_out: device scalar (the image's power-of-two scale). */
+ * eg3d_fir44_adjoint_split_bytes() bytes; scale_out: device scalar (the image's power-of-two scale).  C % 64 == 0 and
+ * eg3d_fir44_adjoint_split_bytes(1, Hi, Wi, C) <= 0x7fffffe0 (EG3D_ERR_UNSUPPORTED otherwise). */
 int64_t eg3d_fir44_adjoint_split_bytes(int N, int Hi, int Wi, int C);
 int eg3d_fir44_adjoint_split(const float* dz, const float* dz_amax, void* image, float* scale_out, int N, int Hi, int Wi, int C, int ldz, float gain,
                              void* stream);
@@ -489,7 +490,8 @@ int eg3d_modconv_epilogue_fwd(const float* z, float* out, int N, int H, int W, i
                               const float* noise, int64_t noise_nstride, const float* noise_strength,
                               const float* bias, int act, float alpha, float gain, float clamp, float* out_amax, void* stream);
 /* The same epilogue for a SEPARABLE 4-tap FIR given by its host-side taps k4 (2-D filter = outer(k4, k4); the [1,3,3,1] / 8 filter of every
- * up-sampling layer), C % 64 == 0, act in {linear, relu, lrelu}: staged through LDS (csrc/epilogue.hip: upconv_epilogue_kernel).  With
+ * up-sampling layer), C % 64 == 0, act in {linear, relu, lrelu}: staged through LDS (csrc/epilogue.hip: upconv_epilogue_strip_kernel;
+ * one image H * W * C * 4 <= 0x7fffffe0 bytes, EG3D_ERR_UNSUPPORTED beyond: 32-bit offsets into a buffer descriptor per image).  With
  * split_image (+ split_in_scale [N,C] = the CONSUMER layer's styles, split_scale_out = device scalar; clamp >= 0 required, it is the range
  * bound) the launch also writes that layer's operand image split(out * split_in_scale) exactly as eg3d_split_activation would
  * (eg3d_split_activation_bytes(N, H, W, C) bytes), so the consumer needs no split pass of its own. */

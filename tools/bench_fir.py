@@ -22,3 +22,10 @@ for (c, h) in ((128, 512), (256, 256), (256, 128), (512, 64)):
     tb = timeit(lambda: H.upfirdn2d_nhwc(dz, f, pad=(2, 2, 2, 2), flip=True, gain=4.0))
     mb = 2 * c * h * h * 4 / 1e6
     print(f'C={c} {h}^2: epilogue_fwd {tf*1e3:6.1f} us ({mb/tf/1e3:4.2f} TB/s)   FIR adjoint {tb*1e3:6.1f} us ({mb/tb/1e3:4.2f} TB/s)')
+    # the forms the step runs: epilogue + fused operand split of the consumer (SR head, clamp 256); FIR adjoint + parity split (eg3d_fir44_adjoint_split)
+    sty = 1 + 0.5 * torch.randn(1, c, device=dev)
+    ts = timeit(lambda: H.upconv_epilogue_fwd(z, out, pad0=1, fir_gain=4.0, d=d, noise=nz, noise_nstride=0, noise_strength=ns, bias=b, act='lrelu', alpha=0.2, gain=1.414, clamp=256.0, split_in_scale=sty)) if c % 128 == 0 else float('nan')
+    am = H.absmax(dz)
+    ta = timeit(lambda: H.fir44_adjoint_split(dz, am, gain=4.0))
+    mbs, mba = 3 * c * h * h * 4 / 1e6, (c * h * h * 4 + c * (h // 2 + 1) ** 2 * 16) / 1e6
+    print(f'            epilogue + split {ts*1e3:6.1f} us ({mbs/ts/1e3:4.2f} TB/s)   adjoint + parity split {ta*1e3:6.1f} us ({mba/ta/1e3:4.2f} TB/s)')

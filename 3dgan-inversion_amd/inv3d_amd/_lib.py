@@ -257,6 +257,27 @@ class JpegParams(C.Structure):
 JPEG_F32, JPEG_U8 = 0, 1
 JPEG_444, JPEG_420 = 0, 1
 
+
+class Resample8Params(C.Structure):
+    """eg3d_resample8_params: Pillow's 8-bit separable resize (eg3d_resample8_query_workspace / eg3d_resample8)."""
+    _fields_ = [('src', C.c_void_p), ('dst', C.c_void_p), ('hbounds', C.c_void_p), ('hcoef', C.c_void_p), ('vbounds', C.c_void_p),
+                ('vcoef', C.c_void_p), ('workspace', C.c_void_p), ('workspace_bytes', C.c_int64), ('N', C.c_int32), ('Hi', C.c_int32),
+                ('Wi', C.c_int32), ('C', C.c_int32), ('Ho', C.c_int32), ('Wo', C.c_int32), ('hksize', C.c_int32), ('vksize', C.c_int32),
+                ('hseg', C.c_int32)]
+
+
+class QuadWarp8Params(C.Structure):
+    """eg3d_quad_warp8_params: Pillow's QUAD bilinear transform (eg3d_quad_warp8)."""
+    _fields_ = [('src', C.c_void_p), ('dst', C.c_void_p), ('a', C.c_double * 8), ('N', C.c_int32), ('Hi', C.c_int32), ('Wi', C.c_int32),
+                ('C', C.c_int32), ('Ho', C.c_int32), ('Wo', C.c_int32)]
+
+
+class FeatherPadParams(C.Structure):
+    """eg3d_feather_pad_params: align_face's reflect pad with feathered, median-filled border (eg3d_feather_pad_query_workspace / eg3d_feather_pad)."""
+    _fields_ = [('src', C.c_void_p), ('dst', C.c_void_p), ('gauss', C.c_void_p), ('workspace', C.c_void_p), ('workspace_bytes', C.c_int64),
+                ('N', C.c_int32), ('H', C.c_int32), ('W', C.c_int32), ('C', C.c_int32), ('left', C.c_int32), ('top', C.c_int32),
+                ('right', C.c_int32), ('bottom', C.c_int32), ('radius', C.c_int32)]
+
 _SIGS = {
     'eg3d_abi_version': (C.c_int, []),
     'eg3d_status_string': (C.c_char_p, [C.c_int]),
@@ -400,6 +421,12 @@ _SIGS = {
     'eg3d_jpeg_query_workspace': (C.c_int, [C.POINTER(JpegParams), C.POINTER(C.c_int64)]),
     'eg3d_jpeg_encode': (C.c_int, [C.POINTER(JpegParams), C.c_void_p]),
     'eg3d_jpeg_pack': (C.c_int, [C.POINTER(JpegParams), C.c_void_p]),
+    'eg3d_resample8_query_workspace': (C.c_int, [C.POINTER(Resample8Params), C.POINTER(C.c_int64)]),
+    'eg3d_resample8': (C.c_int, [C.POINTER(Resample8Params), C.c_void_p]),
+    'eg3d_quad_warp8': (C.c_int, [C.POINTER(QuadWarp8Params), C.c_void_p]),
+    'eg3d_feather_pad_query_workspace': (C.c_int, [C.POINTER(FeatherPadParams), C.POINTER(C.c_int64)]),
+    'eg3d_feather_pad': (C.c_int, [C.POINTER(FeatherPadParams), C.c_void_p]),
+    'eg3d_u8_to_target': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGS)

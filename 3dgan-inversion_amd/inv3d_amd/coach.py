@@ -18,8 +18,9 @@ write_ply).  Evaluation is here too: with `do_evaluation` the tuned reconstructi
 MS-SSIM, the ArcFace IR-SE-50 identity distance) go to {eval_dir}/{name}metrics.txt, and `save_pivot` writes {name}_ws.npy /
 {name}_cam.npy (single_id_coach.py:87-117).  Media export is here as well: with `save_grid` / `gen_video` the pivot grid PNG and the orbit video
 are written before Phase B to {media_dir}/pivot/ and again after it to {media_dir}/ (single_id_coach.py:57-62,80-85; video.py: the GPU JPEG
-encoder in a Motion-JPEG AVI, since there is no H.264 encoder to call).  Image loading, face alignment and wandb logging of the reference loop
-are outside this package; the e4e encoder, the pose head and ArcFace are in e4e.py, pose_net.py and metrics.py.
+encoder in a Motion-JPEG AVI, since there is no H.264 encoder to call).  Image loading and face alignment are images.py (load_targets gives
+the tuples `run` takes); wandb logging of the reference loop is outside this package; the e4e encoder, the pose head and ArcFace are in
+e4e.py, pose_net.py and metrics.py.
 """
 from dataclasses import dataclass, field
 from typing import Callable, Dict, List, Optional, Sequence, Tuple

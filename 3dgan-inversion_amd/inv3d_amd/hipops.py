@@ -12,6 +12,7 @@ import weakref
 import ctypes as C
 from typing import List, Optional, Sequence
 
+import numpy as np
 import torch
 
 from . import _lib as L
@@ -2062,3 +2063,189 @@ def jpeg_encode(img: torch.Tensor, quality: int = 90, subsampling: str = '420', 
     p.out, p.out_capacity = out.data_ptr(), total
     L.check(lib.eg3d_jpeg_pack(C.byref(p), L.stream_ptr()), 'jpeg_pack')
     return out, offsets
+
+
+# ---- image ingestion (csrc/imgprep.hip; include/eg3d_hip.h "Image ingestion"): Pillow's resize and QUAD warp, align_face's pad, ToTensor ------
+PIL_FILTER_SUPPORT = dict(bilinear=1.0, lanczos=3.0)
+RESAMPLE_TILE = 64                       # EG3D_RESAMPLE_TILE: output pixels of a row one workgroup of the horizontal pass produces
+
+
+def _pil_filter(name: str, t: float) -> float:
+    if name == 'bilinear':
+        t = -t if t < 0.0 else t
+        return 1.0 - t if t < 1.0 else 0.0
+    if -3.0 <= t < 3.0:                  # lanczos: sinc(t) sinc(t / 3), truncated
+        sinc = lambda v: 1.0 if v == 0.0 else math.sin(v * math.pi) / (v * math.pi)
+        return sinc(t) * sinc(t / 3)
+    return 0.0
+
+
+def pil_resize_coeffs(in_size: int, out_size: int, filter: str):
+    """(bounds int32 [out,2] = (xmin, count), coef int32 [out,ksize]) of Pillow's 8-bit resize along one axis (Resample.c precompute_coeffs +
+    normalize_coeffs_8bpc): float64 weights of the `filter` ('bilinear' | 'lanczos') scaled to the reduction, normalised by their left-to-right
+    sum, quantised to 22 fractional bits with the rounding offset following the weight's sign.  Plain numpy / host code."""
+    if filter not in PIL_FILTER_SUPPORT:
+        raise ValueError(f"pil_resize_coeffs: filter 'bilinear' | 'lanczos', got {filter!r}")
+    if in_size < 1 or out_size < 1:
+        raise ValueError(f'pil_resize_coeffs: sizes >= 1, got {in_size} -> {out_size}')
+    scale = in_size / out_size
+    fs = max(scale, 1.0)
+    support = PIL_FILTER_SUPPORT[filter] * fs
+    ksize = int(math.ceil(support)) * 2 + 1
+    ss = 1.0 / fs
+    bounds = np.zeros((out_size, 2), np.int32)
+    coef = np.zeros((out_size, ksize), np.int32)
+    for xx in range(out_size):
+        c = (xx + 0.5) * scale
+        xmin = max(int(c - support + 0.5), 0)
+        count = min(int(c + support + 0.5), in_size) - xmin
+        w = [_pil_filter(filter, (x + xmin - c + 0.5) * ss) for x in range(count)]
+        ww = 0.0
+        for v in w:
+            ww += v
+        if ww != 0.0:
+            w = [v / ww for v in w]
+        bounds[xx] = (xmin, count)
+        coef[xx, :count] = [int(-0.5 + v * (1 << 22)) if v < 0 else int(0.5 + v * (1 << 22)) for v in w]
+    return bounds, coef
+
+
+def pil_quad_coeffs(size, quad) -> np.ndarray:
+    """The eight float64 coefficients Pillow's Image.transform derives from QUAD data (NW, SW, SE, NE corners as x, y pairs) for an output of
+    size = (w, h): xin = a0 + a1 xi + a2 yi + a3 xi yi, yin = a4 + ... with xi = x + 0.5, yi = y + 0.5."""
+    w, h = int(size[0]), int(size[1])
+    q = [float(v) for v in np.asarray(quad, dtype=np.float64).reshape(8)]
+    nw, sw, se, ne = q[0:2], q[2:4], q[4:6], q[6:8]
+    x0, y0 = nw
+    As, At = 1.0 / w, 1.0 / h
+    return np.array([x0, (ne[0] - x0) * As, (sw[0] - x0) * At, (se[0] - sw[0] - ne[0] + x0) * As * At,
+                     y0, (ne[1] - y0) * As, (sw[1] - y0) * At, (se[1] - sw[1] - ne[1] + y0) * As * At], np.float64)
+
+
+def gauss_weights(sigma: float) -> np.ndarray:
+    """g[0..radius] float64: one half of scipy.ndimage's normalised Gaussian kernel (radius int(4 sigma + 0.5))."""
+    sigma = float(sigma)
+    radius = int(4.0 * sigma + 0.5)
+    x = np.arange(-radius, radius + 1)
+    phi = np.exp(-0.5 / (sigma * sigma) * x ** 2) if radius > 0 else np.ones(1)
+    phi = phi / phi.sum()
+    return phi[radius:].copy()
+
+
+def _u8_images(img: torch.Tensor, what: str):
+    L.require_cuda(img)
+    if img.dtype != torch.uint8 or img.dim() not in (3, 4) or img.shape[-1] not in (1, 3) or min(img.shape) < 1:
+        raise L.Eg3dHipError(f'{what}: uint8 [N,H,W,C] or [H,W,C] with C = 1 | 3, got {tuple(img.shape)} {img.dtype}')
+    x = img.contiguous()
+    return (x[None] if img.dim() == 3 else x), img.dim() == 3
+
+
+_resample_tables = {}
+
+
+def _resample_axis(in_size: int, out_size: int, filter: str, dev, horizontal: bool):
+    """Device tables of one pass (cached per configuration): bounds [out,2], coef ([ksize,out] tap-major for the horizontal pass, [out,ksize]
+    for the vertical), ksize, and the longest input span a tile of RESAMPLE_TILE outputs reads."""
+    key = (in_size, out_size, filter, str(dev), horizontal)
+    hit = _resample_tables.get(key)
+    if hit is None:
+        if len(_resample_tables) >= 64:
+            _resample_tables.clear()
+        bounds, coef = pil_resize_coeffs(in_size, out_size, filter)
+        seg = 0
+        for t0 in range(0, out_size, RESAMPLE_TILE):
+            t1 = min(t0 + RESAMPLE_TILE, out_size)
+            seg = max(seg, int((bounds[t0:t1, 0] + bounds[t0:t1, 1]).max() - bounds[t0:t1, 0].min()))
+        c = np.ascontiguousarray(coef.T) if horizontal else coef
+        hit = _resample_tables[key] = (torch.from_numpy(bounds).to(dev), torch.from_numpy(c).to(dev), coef.shape[1], seg)
+    return hit
+
+
+def pil_resize(img: torch.Tensor, size, filter: str = 'bilinear') -> torch.Tensor:
+    """PIL.Image.resize(size, filter) of uint8 images [N,H,W,C] (or [H,W,C]), C = 1 | 3, on the device, byte for byte (eg3d_resample8): size =
+    (width, height) as Pillow takes it, filter 'bilinear' | 'lanczos' (ANTIALIAS).  The integer coefficient tables are built on the host
+    (pil_resize_coeffs) and cached per configuration; one launch per axis that changes."""
+    x, squeeze = _u8_images(img, 'pil_resize')
+    if filter not in PIL_FILTER_SUPPORT:
+        raise L.Eg3dHipError(f"pil_resize: filter 'bilinear' | 'lanczos', got {filter!r}")
+    Wo, Ho = int(size[0]), int(size[1])
+    N, Hi, Wi, Ch = x.shape
+    if Wo < 1 or Ho < 1:
+        raise L.Eg3dHipError(f'pil_resize: size >= 1, got {size}')
+    dev = x.device
+    out = torch.empty((N, Ho, Wo, Ch), dtype=torch.uint8, device=dev)
+    p = L.Resample8Params(src=x.data_ptr(), dst=out.data_ptr(), N=N, Hi=Hi, Wi=Wi, C=Ch, Ho=Ho, Wo=Wo)
+    keep = []
+    if Wo != Wi:
+        hb, hc, p.hksize, p.hseg = _resample_axis(Wi, Wo, filter, dev, True)
+        p.hbounds, p.hcoef = hb.data_ptr(), hc.data_ptr()
+        keep += [hb, hc]
+    if Ho != Hi:
+        vb, vc, p.vksize, _ = _resample_axis(Hi, Ho, filter, dev, False)
+        p.vbounds, p.vcoef = vb.data_ptr(), vc.data_ptr()
+        keep += [vb, vc]
+    lib = L.lib()
+    nbytes = C.c_int64(0)
+    L.check(lib.eg3d_resample8_query_workspace(C.byref(p), C.byref(nbytes)), 'resample8_query_workspace')
+    ws = torch.empty(max(nbytes.value, 16), dtype=torch.uint8, device=dev)
+    p.workspace, p.workspace_bytes = ws.data_ptr(), nbytes.value
+    L.check(lib.eg3d_resample8(C.byref(p), L.stream_ptr()), 'resample8')
+    return out[0] if squeeze else out
+
+
+def pil_quad_warp(img: torch.Tensor, size, quad) -> torch.Tensor:
+    """PIL.Image.transform(size, QUAD, quad, BILINEAR) of uint8 images [N,H,W,C] (or [H,W,C]) on the device, byte for byte, pixels whose source
+    falls outside the image 0 (eg3d_quad_warp8): size = (width, height), quad = the NW, SW, SE, NE corners as eight numbers (x, y pairs)."""
+    x, squeeze = _u8_images(img, 'pil_quad_warp')
+    Wo, Ho = int(size[0]), int(size[1])
+    if Wo < 1 or Ho < 1:
+        raise L.Eg3dHipError(f'pil_quad_warp: size >= 1, got {size}')
+    N, Hi, Wi, Ch = x.shape
+    out = torch.empty((N, Ho, Wo, Ch), dtype=torch.uint8, device=x.device)
+    p = L.QuadWarp8Params(src=x.data_ptr(), dst=out.data_ptr(), N=N, Hi=Hi, Wi=Wi, C=Ch, Ho=Ho, Wo=Wo)
+    p.a[:] = [float(v) for v in pil_quad_coeffs((Wo, Ho), quad)]
+    L.check(L.lib().eg3d_quad_warp8(C.byref(p), L.stream_ptr()), 'quad_warp8')
+    return out[0] if squeeze else out
+
+
+_gauss_tables = {}
+
+
+def feather_pad(img: torch.Tensor, pads, qsize: float) -> torch.Tensor:
+    """The pad branch of the reference's align_face (utils/alignment.py:95-105) on the device (eg3d_feather_pad): uint8 [N,H,W,C] (or [H,W,C])
+    reflect-padded by pads = (left, top, right, bottom) >= 1, blended towards its Gaussian blur (sigma 0.02 qsize) and then towards the
+    per-channel median of the blended image by the reference's border mask, rounded to uint8.  fp32 with a pixel-fixed summation order."""
+    x, squeeze = _u8_images(img, 'feather_pad')
+    left, top, right, bottom = (int(v) for v in pads)
+    if min(left, top, right, bottom) < 1:
+        raise L.Eg3dHipError(f'feather_pad: pads >= 1 (the mask divides by them), got {tuple(pads)}')
+    N, Hi, Wi, Ch = x.shape
+    dev = x.device
+    key = (float(qsize), str(dev))
+    gd = _gauss_tables.get(key)
+    if gd is None:
+        if len(_gauss_tables) >= 64:
+            _gauss_tables.clear()
+        gd = _gauss_tables[key] = torch.from_numpy(gauss_weights(float(qsize) * 0.02).astype(np.float32)).to(dev)
+    out = torch.empty((N, Hi + top + bottom, Wi + left + right, Ch), dtype=torch.uint8, device=dev)
+    p = L.FeatherPadParams(src=x.data_ptr(), dst=out.data_ptr(), gauss=gd.data_ptr(), N=N, H=Hi, W=Wi, C=Ch, left=left, top=top, right=right,
+                           bottom=bottom, radius=gd.numel() - 1)
+    lib = L.lib()
+    nbytes = C.c_int64(0)
+    L.check(lib.eg3d_feather_pad_query_workspace(C.byref(p), C.byref(nbytes)), 'feather_pad_query_workspace')
+    ws = torch.empty(nbytes.value, dtype=torch.uint8, device=dev)
+    p.workspace, p.workspace_bytes = ws.data_ptr(), nbytes.value
+    L.check(lib.eg3d_feather_pad(C.byref(p), L.stream_ptr()), 'feather_pad')
+    return out[0] if squeeze else out
+
+
+def u8_to_target(img: torch.Tensor) -> torch.Tensor:
+    """ToTensor + Normalize([0.5] * 3, [0.5] * 3) of uint8 [N,H,W,3] (or [H,W,3]): fp32 [N,3,H,W] = (v / 255 - 0.5) / 0.5, every step a
+    correctly rounded fp32 operation as torchvision's host pipeline computes it (eg3d_u8_to_target)."""
+    x, _ = _u8_images(img, 'u8_to_target')
+    if x.shape[-1] != 3:
+        raise L.Eg3dHipError(f'u8_to_target: C = 3, got {tuple(img.shape)}')
+    N, Hi, Wi, _ = x.shape
+    out = torch.empty((N, 3, Hi, Wi), dtype=torch.float32, device=x.device)
+    L.check(L.lib().eg3d_u8_to_target(L.ptr(x), N, Hi, Wi, L.ptr(out), L.stream_ptr()), 'u8_to_target')
+    return out

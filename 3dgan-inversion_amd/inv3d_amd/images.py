@@ -1,0 +1,174 @@
+"""Target-image ingestion (utils/alignment.py, utils/align_data.py, utils/ImagesDataset.py, scripts/run_pti.py:28-30).
+
+  align_plan, align_face   <- utils/alignment.py::align_face, lines 37-114: the geometry (quad, qsize, shrink, border, crop and pad boxes) in host
+                              float64, statement by statement; every pixel step one of the kernels of csrc/imgprep.hip (hipops.pil_resize,
+                              feather_pad, pil_quad_warp), the crop a slice.  Landmarks (68 x 2) come from a file, as in EG3D's preprocessing:
+                              there is no landmark detector here
+  e4e_image_transform      <- training/coaches/base_coach.py:41-45: ToPILImage, Resize((256, 256)), ToTensor, Normalize
+  load_landmarks           <- a .json ({name: 68 x 2}) or .npz (one array per name) mapping
+  load_targets             <- ImagesDataset / make_dataset + ToTensor / Normalize: the (name, target, None) tuples InversionCoach.run takes
+
+PIL decodes the files on the host (imported lazily, and only in load_targets); everything after the decode runs on the device."""
+import json
+import os
+from typing import NamedTuple, Optional, Tuple
+
+import numpy as np
+import torch
+
+IMG_EXTENSIONS = ('.jpg', '.JPG', '.jpeg', '.JPEG', '.png', '.PNG', '.ppm', '.PPM', '.bmp', '.BMP', '.tiff')      # utils/data_utils.py
+
+
+class AlignPlan(NamedTuple):
+    shrink_size: Optional[Tuple[int, int]]         # (width, height) of the LANCZOS shrink, or None
+    crop: Optional[Tuple[int, int, int, int]]      # (x0, y0, x1, y1) in the (shrunk) image, or None
+    pad: Optional[Tuple[int, int, int, int]]       # (left, top, right, bottom), or None
+    qsize: float                                   # at the pad step (after the shrink)
+    quad: Tuple[float, ...]                        # the QUAD transform's data: NW, SW, SE, NE corners + 0.5, in the padded image
+
+
+def align_plan(height: int, width: int, landmarks, output_size: int) -> AlignPlan:
+    """The host geometry of align_face for an image of height x width (alignment.py:37-109, statement by statement, float64)."""
+    lm = np.asarray(landmarks)
+    if lm.shape != (68, 2):
+        raise ValueError(f'align_plan: landmarks 68 x 2, got {lm.shape}')
+    lm_eye_left = lm[36: 42]  # left-clockwise
+    lm_eye_right = lm[42: 48]  # left-clockwise
+    lm_mouth_outer = lm[48: 60]  # left-clockwise
+
+    # Calculate auxiliary vectors.
+    eye_left = np.mean(lm_eye_left, axis=0)
+    eye_right = np.mean(lm_eye_right, axis=0)
+    eye_avg = (eye_left + eye_right) * 0.5
+    eye_to_eye = eye_right - eye_left
+    mouth_left = lm_mouth_outer[0]
+    mouth_right = lm_mouth_outer[6]
+    mouth_avg = (mouth_left + mouth_right) * 0.5
+    eye_to_mouth = mouth_avg - eye_avg
+
+    # Choose oriented crop rectangle.
+    x = eye_to_eye - np.flipud(eye_to_mouth) * [-1, 1]
+    x /= np.hypot(*x)
+    x *= max(np.hypot(*eye_to_eye) * 2.0, np.hypot(*eye_to_mouth) * 1.8)
+    y = np.flipud(x) * [-1, 1]
+    c = eye_avg + eye_to_mouth * 0.1
+    quad = np.stack([c - x - y, c - x + y, c + x + y, c + x - y])
+    qsize = np.hypot(*x) * 2
+
+    size = [int(width), int(height)]                 # img.size
+
+    # Shrink.
+    shrink_size = None
+    shrink = int(np.floor(qsize / output_size * 0.5))
+    if shrink > 1:
+        shrink_size = (int(np.rint(float(size[0]) / shrink)), int(np.rint(float(size[1]) / shrink)))
+        size = list(shrink_size)
+        quad /= shrink
+        qsize /= shrink
+
+    # Crop.
+    crop_box = None
+    border = max(int(np.rint(qsize * 0.1)), 3)
+    crop = (int(np.floor(min(quad[:, 0]))), int(np.floor(min(quad[:, 1]))), int(np.ceil(max(quad[:, 0]))), int(np.ceil(max(quad[:, 1]))))
+    crop = (max(crop[0] - border, 0), max(crop[1] - border, 0), min(crop[2] + border, size[0]), min(crop[3] + border, size[1]))
+    if crop[2] - crop[0] < size[0] or crop[3] - crop[1] < size[1]:
+        crop_box = crop
+        size = [crop[2] - crop[0], crop[3] - crop[1]]
+        quad -= crop[0:2]
+
+    # Pad.
+    pad_box = None
+    pad = (int(np.floor(min(quad[:, 0]))), int(np.floor(min(quad[:, 1]))), int(np.ceil(max(quad[:, 0]))), int(np.ceil(max(quad[:, 1]))))
+    pad = (max(-pad[0] + border, 0), max(-pad[1] + border, 0), max(pad[2] - size[0] + border, 0), max(pad[3] - size[1] + border, 0))
+    if max(pad) > border - 4:                        # enable_padding is True in the reference
+        pad = np.maximum(pad, int(np.rint(qsize * 0.3)))
+        pad_box = tuple(int(v) for v in pad)
+        quad += pad[:2]
+
+    return AlignPlan(shrink_size, crop_box, pad_box, float(qsize), tuple(float(v) for v in (quad + 0.5).flatten()))
+
+
+def align_face(img_u8: torch.Tensor, landmarks, output_size: int) -> torch.Tensor:
+    """utils/alignment.py::align_face on the device: uint8 [H,W,3] (the decoded photograph) and its 68 x 2 landmarks -> the aligned uint8
+    [output_size, output_size, 3] image.  Byte-equal to the reference's Pillow calls unless the pad branch runs (fp32 there)."""
+    from . import hipops
+    if img_u8.dim() != 3:
+        raise ValueError(f'align_face: one uint8 [H,W,C] image, got {tuple(img_u8.shape)}')
+    plan = align_plan(img_u8.shape[0], img_u8.shape[1], landmarks, output_size)
+    img = img_u8
+    if plan.shrink_size is not None:
+        img = hipops.pil_resize(img, plan.shrink_size, 'lanczos')                 # PIL.Image.ANTIALIAS is LANCZOS
+    if plan.crop is not None:
+        x0, y0, x1, y1 = plan.crop
+        img = img[y0:y1, x0:x1]
+    if plan.pad is not None:
+        img = hipops.feather_pad(img, plan.pad, plan.qsize)
+    # transform_size = output_size in the reference, so its closing `if output_size < transform_size: img.resize(...)` (alignment.py:110-111)
+    # is dead code: the warp writes the output size directly, and it stays dead here
+    return hipops.pil_quad_warp(img, (output_size, output_size), plan.quad)
+
+
+def e4e_image_transform(target: torch.Tensor) -> torch.Tensor:
+    """base_coach.py:41-45 applied to (target + 1) / 2 as the coach applies it: fp32 [N,3,H,W] in [0,1] -> ToPILImage (mul(255).byte()),
+    PIL Resize((256, 256)) (bilinear, on uint8), ToTensor, Normalize(0.5, 0.5) -> fp32 [N,3,256,256].  Offered as a function: the coach's own
+    start-latent path is unchanged."""
+    from . import hipops
+    if target.dim() != 4 or target.shape[1] != 3 or not target.dtype.is_floating_point:
+        raise ValueError(f'e4e_image_transform: floating-point [N,3,H,W] in [0,1], got {tuple(target.shape)} {target.dtype}')
+    u8 = target.mul(255).byte().permute(0, 2, 3, 1).contiguous()
+    return hipops.u8_to_target(hipops.pil_resize(u8, (256, 256), 'bilinear'))
+
+
+def load_landmarks(path: str) -> dict:
+    """{name: float64 [68,2]} from a .json ({name: [[x, y], ...]}) or an .npz (one array per name).  Names are file names up to their first dot."""
+    if path.endswith('.npz'):
+        with np.load(path, allow_pickle=False) as z:
+            out = {k: np.asarray(z[k], dtype=np.float64) for k in z.files}
+    else:
+        with open(path) as f:
+            out = {k: np.asarray(v, dtype=np.float64) for k, v in json.load(f).items()}
+    for k, v in out.items():
+        if v.shape != (68, 2):
+            raise ValueError(f'load_landmarks: {k}: 68 x 2 expected, got {v.shape}')
+    return out
+
+
+def image_files(directory: str):
+    """[(name, path)] of the image files under a directory, sorted: ImagesDataset's `sorted(make_dataset(root))` -- the tree is walked, the
+    name is the file name up to its first dot (utils/data_utils.py:25-34)."""
+    if not os.path.isdir(directory):
+        raise ValueError(f'{directory} is not a valid directory')
+    out = []
+    for root, _, fnames in sorted(os.walk(directory)):
+        for fname in fnames:
+            if fname.endswith(IMG_EXTENSIONS):
+                out.append((fname.split('.')[0], os.path.join(root, fname)))
+    return sorted(out)
+
+
+def decode_rgb(path: str, device) -> torch.Tensor:
+    """uint8 [H,W,3] on the device: PIL.Image.open(path).convert('RGB') -- the decode is host work."""
+    from PIL import Image
+    with Image.open(path) as im:
+        arr = np.array(im.convert('RGB'), dtype=np.uint8)
+    return torch.from_numpy(arr).to(device)
+
+
+def load_targets(directory: str, landmarks=None, output_size: int = 512, device='cuda'):
+    """[(name, target fp32 [1,3,S,S] in [-1,1] on the device, None)] for InversionCoach.run, S = output_size: every image file of `directory` in
+    sorted order, decoded to RGB; aligned by align_face where `landmarks` (a {name: 68 x 2} mapping, or the path of a .json / .npz holding
+    one) has its name, otherwise required to be S x S already; then ToTensor + Normalize(0.5, 0.5) (hipops.u8_to_target)."""
+    from . import hipops
+    if isinstance(landmarks, str):
+        landmarks = load_landmarks(landmarks)
+    landmarks = landmarks or {}
+    out = []
+    for name, path in image_files(directory):
+        img = decode_rgb(path, device)
+        if name in landmarks:
+            img = align_face(img, landmarks[name], output_size)
+        elif tuple(img.shape[:2]) != (output_size, output_size):
+            raise ValueError(f'load_targets: {path} is {img.shape[1]} x {img.shape[0]} and has no landmarks: give landmarks for it or a '
+                             f'{output_size} x {output_size} image')
+        out.append((name, hipops.u8_to_target(img), None))
+    return out

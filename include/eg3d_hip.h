@@ -1195,6 +1195,82 @@ int eg3d_jpeg_query_workspace(const eg3d_jpeg_params* p, int64_t* workspace_byte
 int eg3d_jpeg_encode(const eg3d_jpeg_params* p, void* stream);
 int eg3d_jpeg_pack(const eg3d_jpeg_params* p, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Image ingestion (the pixel work of utils/alignment.py::align_face and of ToTensor / Normalize, scripts/run_pti.py:28-30; csrc/imgprep.hip).
+ *   Images are contiguous uint8 [N,H,W,C], C = 1 or 3, sides 1..65535, on the device.  No atomics on floats, no floating-point sum whose order
+ *   depends on the launch: bit-identical between runs, batch sizes and the two builds.
+ *
+ * eg3d_resample8: PIL.Image.resize of an 8-bit image, byte for byte (Pillow's Resample.c, 8bpc path).  The caller builds the integer tables on
+ *   the host in float64 (inv3d_amd/hipops.py pil_resize_coeffs: filter support scaled by max(in / out, 1), ksize = 2 ceil(support) + 1, weights
+ *   normalised by their left-to-right sum and quantised to 22 fractional bits) and passes them on the device:
+ *     hbounds [Wo][2] = (xmin, count) per output column, hcoef [hksize][Wo] (tap-major), hseg = the longest input span
+ *     max(xmin + count) - min(xmin) over any tile of EG3D_RESAMPLE_TILE consecutive output columns (tiles start at multiples of it);
+ *     vbounds [Ho][2], vcoef [Ho][vksize] (row-major).  A pass runs only when its tables are given: h* must be NULL exactly when Wo == Wi,
+ *     v* exactly when Ho == Hi (neither: a copy).
+ *   Horizontal pass first (a workgroup stages the row segments it needs in LDS), uint8 intermediate [N,Hi,Wo,C] in the workspace when both
+ *   passes run, then the vertical pass (lanes along the row's bytes).  Per sample acc = 2^21 + sum pixel * k in int32, clip(acc >> 22, 0, 255).
+ *   A table whose span does not fit hseg yields 0 for that output, never an out-of-range read; hseg * C beyond the LDS budget (48 KB per row)
+ *   is EG3D_ERR_UNSUPPORTED.  eg3d_resample8_query_workspace is host only. */
+#define EG3D_RESAMPLE_TILE 64
+typedef struct eg3d_resample8_params {
+    const uint8_t* src;                /* [N,Hi,Wi,C] */
+    uint8_t* dst;                      /* [N,Ho,Wo,C] */
+    const int32_t* hbounds;            /* device; NULL when Wo == Wi */
+    const int32_t* hcoef;
+    const int32_t* vbounds;            /* device; NULL when Ho == Hi */
+    const int32_t* vcoef;
+    void* workspace;                   /* eg3d_resample8_query_workspace's bytes (may be 0: then unused) */
+    int64_t workspace_bytes;
+    int32_t N, Hi, Wi, C, Ho, Wo;
+    int32_t hksize, vksize;
+    int32_t hseg;
+} eg3d_resample8_params;
+int eg3d_resample8_query_workspace(const eg3d_resample8_params* p, int64_t* workspace_bytes);
+int eg3d_resample8(const eg3d_resample8_params* p, void* stream);
+
+/* eg3d_quad_warp8: PIL.Image.transform((Wo, Ho), QUAD, data, BILINEAR) with fill 0, byte for byte (Pillow's Geometry.c).  a[0..7] are the
+ *   coefficients Pillow derives from the quad (hipops.pil_quad_coeffs); for output (x, y), xi = x + 0.5, yi = y + 0.5:
+ *     xin = a0 + a1 xi + a2 yi + a3 xi yi,  yin = a4 + a5 xi + a6 yi + a7 xi yi;  xin < 0 | xin >= Wi | yin < 0 | yin >= Hi: the pixel is 0;
+ *     else xin -= 0.5, yin -= 0.5, fx = floor(xin), dx = xin - fx (likewise y), neighbours index-clamped,
+ *     r0 = p00 + (p01 - p00) dx, r1 = p10 + (p11 - p10) dx, v = r0 + (r1 - r0) dy, stored as (uint8)v (truncated).
+ *   fp64, exactly this operation order, no contraction into FMA.  The same quad for the N images.  One launch. */
+typedef struct eg3d_quad_warp8_params {
+    const uint8_t* src;                /* [N,Hi,Wi,C] */
+    uint8_t* dst;                      /* [N,Ho,Wo,C] */
+    double a[8];
+    int32_t N, Hi, Wi, C, Ho, Wo;
+} eg3d_quad_warp8_params;
+int eg3d_quad_warp8(const eg3d_quad_warp8_params* p, void* stream);
+
+/* eg3d_feather_pad: the pad branch of align_face (alignment.py:95-105) in fp32.  With Hp = H + top + bottom, Wp = W + left + right (pads >= 1):
+ *     P = float(np.pad(src, 'reflect'))                                    (no edge repeat; any pad width)
+ *     B = separable Gaussian of P along y, then x: weights gauss[0..radius] (device fp32, one half of the symmetric normalised kernel, built
+ *         on the host in float64), boundary scipy 'reflect' (numpy 'symmetric'), fp32 intermediate; every sum is
+ *         g[0] p[0] + g[1] (p[-1] + p[+1]) + ... + g[radius] (p[-radius] + p[+radius]) in this order -- a function of the pixel alone
+ *     mask = max(1 - min(x / left, (Wp-1-x) / right), 1 - min(y / top, (Hp-1-y) / bottom))
+ *     V = P + (B - P) clip(3 mask + 1, 0, 1)
+ *     m[n][c] = median of V[n,:,:,c]: exact, by a radix select over the ordered float bits (integer histograms); an even count takes
+ *         (a + b) / 2 of the two middle values in fp32, as np.median
+ *     dst = uint8(clip(rint(V + (m - V) clip(mask, 0, 1)), 0, 255)), ties to even
+ *   Where both blend weights are 0 the result is src's own byte.  Workspace: two fp32 images [N,Hp,Wp,C] + the select's state; Hp Wp < 2^31.
+ *   eg3d_feather_pad_query_workspace is host only. */
+typedef struct eg3d_feather_pad_params {
+    const uint8_t* src;                /* [N,H,W,C] */
+    uint8_t* dst;                      /* [N,Hp,Wp,C] */
+    const float* gauss;                /* device [radius + 1] */
+    void* workspace;                   /* eg3d_feather_pad_query_workspace's bytes, 16-byte aligned */
+    int64_t workspace_bytes;
+    int32_t N, H, W, C;
+    int32_t left, top, right, bottom;
+    int32_t radius;
+} eg3d_feather_pad_params;
+int eg3d_feather_pad_query_workspace(const eg3d_feather_pad_params* p, int64_t* workspace_bytes);
+int eg3d_feather_pad(const eg3d_feather_pad_params* p, void* stream);
+
+/* img uint8 [N,H,W,3] -> out fp32 [N,3,H,W] = (float(v) / 255 - 0.5) / 0.5: torchvision's ToTensor + Normalize(0.5, 0.5), each step one
+ *   correctly rounded fp32 operation (a true division by 255, not a multiplication by its reciprocal). */
+int eg3d_u8_to_target(const uint8_t* img, int N, int H, int W, float* out, void* stream);
+
 /* Measurement aid (bench.py): a register-only v_mfma_f32_32x32x16_f16 loop on caller-supplied fp16 data -- what the matrix pipe sustains on
  * this chip at its current power / clock state, timed inside the benchmark run.  in: 4096 x 8 fp16 (64 KiB); out: blocks x 256 floats;
  * executes blocks x 4 waves x iters x 24 MFMAs of 32 x 32 x 16.  No reference counterpart. */

@@ -1,0 +1,87 @@
+"""Invert a directory of photographs (the reference's scripts/run_pti.py: ImagesDataset + SingleIDCoach.train): decode, align on the GPU where
+landmarks are given (inv3d_amd/images.py), then InversionCoach.run -- Phase A, Phase B and the per-image outputs that were asked for.
+
+  python tools/run_inversion.py --in-dir photos --out-dir out [--landmarks landmarks.json] [--weights G.safetensors | --synthetic small|full]
+                                [--steps-a 400] [--steps-b 400] [--optimize-pose] [--graph] [--save-grid] [--gen-video] [--gen-mesh]
+                                [--mesh-format .mrc|.ply] [--mesh-res 512] [--do-evaluation] [--save-pivot]
+
+Images with an entry in --landmarks (a .json {name: 68 x 2} or an .npz) are aligned to the generator's resolution; the others must have it
+already.  --weights: a generator archive (inv3d_amd.weights, tools/convert_eg3d_pickle.py); otherwise a synthetic generator.  Outputs go to
+{out-dir}/media (grids, videos), /mesh, /eval, /pivot; a summary line per image and the totals are printed."""
+import argparse
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+for _p in (ROOT, os.path.join(ROOT, '3dgan-inversion_amd')):
+    if _p not in sys.path:
+        sys.path.insert(0, _p)
+
+import torch  # noqa: E402
+
+
+def _generator(a, dev):
+    if a.weights:
+        from inv3d_amd.weights import load_generator
+        return load_generator(a.weights, device=dev)
+    from inv3d_amd import synthetic as S
+    if a.synthetic == 'small':
+        from oracle import eg3d_oracle as O
+        G = S.make_generator(w_dim=32, z_dim=32, plane_res=32, channel_base=256, channel_max=16, nrr=16, sr_in_res=16, sr_widths=(16, 8),
+                             rendering_kwargs=O.small_config().rendering, device=dev)
+    else:
+        G = S.make_generator(device=dev)
+    S.load_synthetic_weights(G, seed=a.seed)
+    for p in G.parameters():
+        p.requires_grad_(False)
+    return G
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(description=__doc__.splitlines()[0])
+    ap.add_argument('--in-dir', required=True)
+    ap.add_argument('--out-dir', required=True)
+    ap.add_argument('--landmarks', default=None)
+    ap.add_argument('--weights', default=None, help='generator archive; default: a synthetic generator')
+    ap.add_argument('--synthetic', choices=('full', 'small'), default='full')
+    ap.add_argument('--seed', type=int, default=0, help='synthetic generator weights seed')
+    ap.add_argument('--output-size', type=int, default=None, help="default: the generator's img_resolution")
+    ap.add_argument('--steps-a', type=int, default=400)
+    ap.add_argument('--steps-b', type=int, default=400)
+    ap.add_argument('--lpips-threshold', type=float, default=0.06)
+    ap.add_argument('--w-avg-samples', type=int, default=None, help='default: 10000 with --weights, 0 with a synthetic generator')
+    ap.add_argument('--optimize-pose', action='store_true')
+    ap.add_argument('--graph', action='store_true', help='capture the steps into HIP graphs')
+    ap.add_argument('--save-grid', action='store_true')
+    ap.add_argument('--gen-video', action='store_true')
+    ap.add_argument('--gen-mesh', action='store_true')
+    ap.add_argument('--mesh-format', choices=('.mrc', '.ply'), default='.mrc')
+    ap.add_argument('--mesh-res', type=int, default=512)
+    ap.add_argument('--do-evaluation', action='store_true')
+    ap.add_argument('--save-pivot', action='store_true')
+    a = ap.parse_args(argv)
+    from inv3d_amd import images
+    from inv3d_amd.coach import InversionCoach
+    dev = torch.device('cuda')
+    G = _generator(a, dev)
+    size = a.output_size or int(G.img_resolution)
+    targets = images.load_targets(a.in_dir, a.landmarks, output_size=size, device=dev)
+    if not targets:
+        raise SystemExit(f'no image files in {a.in_dir}')
+    sub = lambda d: os.path.join(a.out_dir, d)
+    samples = a.w_avg_samples if a.w_avg_samples is not None else (10000 if a.weights else 0)
+    coach = InversionCoach(G, first_inv_steps=a.steps_a, max_pti_steps=a.steps_b, lpips_threshold=a.lpips_threshold, optimize_pose=a.optimize_pose,
+                           use_graph=a.graph, w_avg_samples=samples, save_grid=a.save_grid, gen_video=a.gen_video,
+                           media_dir=sub('media') if (a.save_grid or a.gen_video) else None, gen_mesh=a.gen_mesh,
+                           mesh_dir=sub('mesh') if a.gen_mesh else None, mesh_format=a.mesh_format, mesh_res=a.mesh_res,
+                           do_evaluation=a.do_evaluation, eval_dir=sub('eval') if a.do_evaluation else None, save_pivot=a.save_pivot,
+                           pivot_dir=sub('pivot') if a.save_pivot else None)
+    results, stats = coach.run(targets)
+    for r in results:
+        print(f'{r.name}: {r.steps_a} + {r.steps_b} steps, PSNR {r.psnr_pivot:.2f} dB at the pivot, {r.psnr_tuned:.2f} dB tuned')
+    print(' '.join(f'{k}={v:.6g}' for k, v in sorted(stats.items())))
+    return results, stats
+
+
+if __name__ == '__main__':
+    main()

@@ -947,7 +947,6 @@ __global__ void __launch_bounds__(ACCP_WAVES * 64) scatter_accum16p_kernel(const
     const int pj = lane >> 2, half = (lane >> 1) & 1, dx = lane & 1;          // this lane's (pair, corner) of a 16-pair group
     const int a_slot = (pj >> 1) * 64 + (pj & 1) * 32 + half * 16;          // + column
     const __amdgpu_buffer_rsrc_t drs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(df), 0, (int)(S * FC * 4), 0x00020000);
-    const float4 zero4 = make_float4(0.f, 0.f, 0.f, 0.f);
     const int nwave = gridDim.x * ACCP_WAVES;
     for (int ui = blockIdx.x * ACCP_WAVES + wave; ui < nlist * split; ui += nwave) {
         const int li = ui / split, part = ui - li * split;
@@ -957,7 +956,12 @@ __global__ void __launch_bounds__(ACCP_WAVES * 64) scatter_accum16p_kernel(const
         acc16_t acc;
 #pragma unroll
         for (int i = 0; i < 16; ++i) acc[i] = 0.f;
-        auto load_recs = [&](int p0) { return p0 + lane < end ? recs[p0 + lane] : zero4; };      // an all-zero record has coefficient 0 everywhere
+        // a list's last super-step is padded with records of coefficient 0 (column bits 0, zero weights) that carry the row id of the list's FIRST
+        // record: the padded lanes' row loads feed the matrix cores like any other, and 0 x NaN = NaN -- an all-zero record would read gradient row 0
+        // of the image, which may belong to an absent sample (not part of the data: include/eg3d_hip.h)
+        // (lane 0 of the first super-step always holds the first record: beg < end)
+        float4 pad4 = make_float4(0.f, 0.f, 0.f, 0.f);
+        auto load_recs = [&](int p0) { return p0 + lane < end ? recs[p0 + lane] : pad4; };
         // records of a super-step live in LDS (wave-private, two parities): lane (pair, corner) re-reads its pair's record as one
         // broadcast ds_read_b128, and the row ids are stored de-interleaved so that the eight ids a lane needs for a group of MFMAs
         // are two ds_read_b128 -- the cross-lane reads were 11 ds_bpermute per group before
@@ -967,7 +971,10 @@ __global__ void __launch_bounds__(ACCP_WAVES * 64) scatter_accum16p_kernel(const
         };
         unsigned g[32];
         {
-            const float4 R0 = load_recs(beg), R1 = load_recs(beg + 64);
+            float4 R0 = load_recs(beg);
+            pad4.x = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(R0.x)) & 0x7ffffff);
+            if (beg + lane >= end) R0 = pad4;
+            const float4 R1 = load_recs(beg + 64);
             stash(R0, 0); stash(R1, 1);
         }
 #pragma unroll
@@ -1047,7 +1054,6 @@ __global__ void __launch_bounds__(ACCP_WAVES * 64) scatter_accum16h_kernel(const
     const int pj = lane >> 2, half = (lane >> 1) & 1, dx = lane & 1;          // this lane's (pair, corner) of a 16-pair group
     const int a_slot = half * 16 * 16 + pj;                                  // + 16 * column   (element [row = half * 16 + column][pair])
     const __amdgpu_buffer_rsrc_t drs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(df), 0, (int)(S * FC * 4), 0x00020000);
-    const float4 zero4 = make_float4(0.f, 0.f, 0.f, 0.f);
     // operand scale: max|g| -> [2^13, 2^14) (1 for a zero / non-finite maximum)
     float sc = 1.f;
     {
@@ -1066,7 +1072,12 @@ __global__ void __launch_bounds__(ACCP_WAVES * 64) scatter_accum16h_kernel(const
         acc16_t acc;
 #pragma unroll
         for (int i = 0; i < 16; ++i) acc[i] = 0.f;
-        auto load_recs = [&](int p0) { return p0 + lane < end ? recs[p0 + lane] : zero4; };      // an all-zero record has coefficient 0 everywhere
+        // a list's last super-step is padded with records of coefficient 0 (column bits 0, zero weights) that carry the row id of the list's FIRST
+        // record: the padded lanes' row loads feed the matrix cores like any other, and 0 x NaN = NaN -- an all-zero record would read gradient row 0
+        // of the image, which may belong to an absent sample (not part of the data: include/eg3d_hip.h)
+        // (lane 0 of the first super-step always holds the first record: beg < end)
+        float4 pad4 = make_float4(0.f, 0.f, 0.f, 0.f);
+        auto load_recs = [&](int p0) { return p0 + lane < end ? recs[p0 + lane] : pad4; };
         auto stash = [&](const float4& R, int par) { recl[par * 64 + lane] = R; keyl[par * 64 + lane] = __float_as_int(R.x); };
         // the lane's gradient value of pair 8 kk + j of group gq of the super-step whose records sit in parity `par`
         auto issue_rows = [&](unsigned (&gr)[32], int gq, int par) {
@@ -1078,7 +1089,10 @@ __global__ void __launch_bounds__(ACCP_WAVES * 64) scatter_accum16h_kernel(const
         };
         unsigned g[32];
         {
-            const float4 R0 = load_recs(beg), R1 = load_recs(beg + 64);
+            float4 R0 = load_recs(beg);
+            pad4.x = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(R0.x)) & 0x7ffffff);
+            if (beg + lane >= end) R0 = pad4;
+            const float4 R1 = load_recs(beg + 64);
             stash(R0, 0); stash(R1, 1);
         }
 #pragma unroll

@@ -1511,12 +1511,24 @@ def render_bwd(p, d_rgb, d_depth, d_wsum, d_planes, d_origins, d_dirs, dumps=Non
         bp.df_amax = amax.data_ptr()
     L.check(L.lib().eg3d_render_bwd(C.byref(bp), L.stream_ptr()), 'render_bwd')
     if d_planes is not None:
-        nints = L.lib().eg3d_triplane_scatter_workspace_ints(S, p.N, p.Hp, p.Wp)
-        ws = torch.empty(nints, dtype=torch.int32, device=d_planes.device)
         rw = math.isqrt(p.R)            # rays are generated row by row over a square image (ray_sampler.py:41-50): a hint for the binning order only
-        L.check(L.lib().eg3d_triplane_scatter(L.ptr(rows), L.ptr(pos), S, p.R * 2 * D, L.ptr(d_planes), p.N, p.Hp, p.Wp, p.ldp,
-                                              p.box_warp, L.ptr(ws), rw if rw * rw == p.R else 0, 2 * D, L.ptr(amax) if amax is not None else None,
-                                              L.stream_ptr()), 'triplane_scatter')
+        triplane_scatter(rows, pos, d_planes, p.box_warp, ray_w=rw if rw * rw == p.R else 0, rows_per_ray=2 * D, amax=amax)
+
+
+def triplane_scatter(rows, pos, d_planes, box_warp, ray_w=0, rows_per_ray=0, amax=None):
+    """d_planes (channels_last [N,3C,Hp,Wp], i.e. [N,Hp,Wp,ldp] in memory) += the bilinear-adjoint scatter of the gradient rows [S,32] at the positions
+    pos [S,4] (x, y, z, -; x = NaN marks an absent row, whose gradient row is never read); image n owns rows n S/N .. (n+1) S/N - 1.
+    ray_w, rows_per_ray: the optional brick-walk hint of the binning passes.  amax: [1] tensor holding max|rows| selects the accumulation
+    on the 16-bit matrix cores, None the exact fp32 products (eg3d_triplane_scatter, include/eg3d_hip.h)."""
+    assert is_cl(d_planes) and d_planes.dtype == torch.float32
+    n, ldp, hp, wp = d_planes.shape
+    S = pos.numel() // 4
+    assert rows.numel() == S * 32 and S % n == 0
+    nints = L.lib().eg3d_triplane_scatter_workspace_ints(S, n, hp, wp)
+    ws = torch.empty(nints, dtype=torch.int32, device=d_planes.device)
+    L.check(L.lib().eg3d_triplane_scatter(L.ptr(rows), L.ptr(pos), S, S // n, L.ptr(d_planes), n, hp, wp, ldp, float(box_warp), L.ptr(ws),
+                                          int(ray_w), int(rows_per_ray), L.ptr(amax) if amax is not None else None, L.stream_ptr()),
+            'triplane_scatter')
 
 
 def sample_decode(p, coords, M):

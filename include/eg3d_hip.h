@@ -847,6 +847,8 @@ int eg3d_render_bwd(const eg3d_render_bwd_params* p, void* stream);
  *
  * d_planes[N,Hp,Wp,ldp] (pre-zeroed) += bilinear-adjoint scatter of the S dumped rows (grid_sample backward w.r.t. the
  * planes, renderer.py:64 under autograd).  rows_per_image = R*2*D.  workspace: eg3d_triplane_scatter_workspace_ints() int32.
+ * Rows of absent samples (df_pos x = NaN) are never read: their df_rows rows may hold anything, NaN and Inf included (eg3d_render_bwd leaves
+ * them unwritten).  The rows of present samples must be finite.
  *
  * Supported range (both builds; EG3D_ERR_UNSUPPORTED outside it, decided from the arguments before any GPU work):
  *   - planes up to 270 x 270: 3 * ceil(Hp / 15) * ceil(Wp / 15) * 16 <= 16384 (tile, texel row) lists per image;

@@ -1,19 +1,22 @@
-"""HIP-graph replay behind the plain `G.synthesis(ws, c, **kw)` call (the reference's drop-in callers never see a graph object).
+"""HIP-graph capture and replay.  Everything that is measured runs as a replayed graph: one forward + backward of the full-size
+generator is ~190 kernel launches of ~20 us of host time each through Python / ctypes, ~16 ms per optimisation step for ~6 ms of GPU work.
 
-Why: one forward + backward of the full-size generator is ~190 kernel launches.  Launched one by one through Python / ctypes they cost
-~20 us of host time each, i.e. ~16 ms per optimisation step for ~6 ms of GPU work -- the loops of the reference
-(training/projectors/w_projector.py:189-261, training/coaches/base_coach.py:162-164 + single_id_coach.py:64-77) call `G.synthesis` exactly
-like that.  `inversion.LatentProjector(use_graph=True)` removes the cost by capturing its whole step, but a caller bound through
-`reference_binding.install_as_reference_modules()` runs the reference's own loop.  So the generator does it itself:
+  * `capture(fn, arena=, pool=)` is the one place that captures: collector held, thread-local error mode, zero arena routed inside, and the
+    derived weight images that the captured launches hold raw pointers to returned as `refs`, to be kept as long as the graph.
+  * `StepGraph` is "one optimisation step" of `inversion.LatentProjector` / `PivotalTuner(use_graph=True)`: warm-up on a side stream,
+    capture, first replay, replays; after a refused capture a warning and eager launches on the current stream from then on.
+  * `synthesis` replays behind the plain `G.synthesis(ws, c, **kw)` call.  The loops of the reference (w_projector.py:189-261,
+    base_coach.py:162-164 + single_id_coach.py:64-77), bound through `reference_binding.install_as_reference_modules()`, call it once per
+    step and never see a graph object.  So the generator captures by itself:
 
-  * a call signature (shapes, keyword arguments, grad mode, which leaves require grad, versions of the frozen weights) that has been seen
-    `HOT_AFTER` times is captured once -- forward into one `hipGraph`, `torch.autograd.grad` of its outputs into a second one sharing the
-    memory pool -- and every later call with that signature is: copy (ws, c) into the static inputs, replay, hand back copies of the
-    outputs, wrapped in ONE autograd node whose backward copies the output gradients in, replays the second graph and returns the static
-    input / parameter gradients;
-  * anything the capture cannot express falls back to the per-launch path, silently and correctly: a call made while the previous
-    forward's graph is still waiting for its backward (two live graphs of one generator), `noise_inject`, cached-backbone calls, a
-    launch profiler, a call that is itself being captured (LatentProjector / PivotalTuner graphs), CPU tensors.
+    - a call signature (shapes, keyword arguments, grad mode, which leaves require grad, versions of the frozen weights) that has been seen
+      `HOT_AFTER` times is captured once -- forward into one `hipGraph`, `torch.autograd.grad` of its outputs into a second one sharing the
+      memory pool -- and every later call with that signature is: copy (ws, c) into the static inputs, replay, hand back copies of the
+      outputs, wrapped in ONE autograd node whose backward copies the output gradients in, replays the second graph and returns the static
+      input / parameter gradients;
+    - anything the capture cannot express falls back to the per-launch path, silently and correctly: a call made while the previous
+      forward's graph is still waiting for its backward (two live graphs of one generator), `noise_inject`, cached-backbone calls, a
+      launch profiler, a call that is itself being captured (LatentProjector / PivotalTuner graphs), CPU tensors.
 
 Semantics kept: outputs are fresh tensors (copies of the static buffers); gradients of `ws` / `c` flow on into the caller's graph; parameter
 gradients reach `.grad` through autograd's own AccumulateGrad (they alias static buffers when `.grad` was None, which is what
@@ -22,11 +25,15 @@ False)` -- gets a private copy first).  Trainable weights are re-packed inside t
 seen; frozen weights are part of the signature (pointer + version), so `load_state_dict` / in-place edits re-capture.
 Set `EG3D_GRAPH_EAGER=0` (or `inv3d_amd.graphed.ENABLED = False`, or `G.graph_eager = False`) to switch it off.
 """
+import contextlib
 import os
+import types
+import warnings
 import weakref
 
 import torch
 
+from . import dist as D
 from . import hipops as H
 
 ENABLED = os.environ.get('EG3D_GRAPH_EAGER', '1') != '0'
@@ -37,13 +44,80 @@ _STATE = weakref.WeakKeyDictionary()        # generator -> _PerG   (not an attri
 STATS = dict(captured=0, replayed=0, eager=0, fallback_pending=0, capture_failed=0)
 
 
+def _routed(arena):
+    return H.zero_arena(arena) if arena is not None else contextlib.nullcontext()
+
+
+def capture(fn, *, arena=None, pool=None):
+    """Capture the launches of `fn()` into a new HIP graph: (graph, fn's result, refs).  No garbage collection inside (hipops.capture_guard),
+    thread-local error mode (other threads -- the RCCL watchdog -- may touch the runtime), the zero arena's fill launch part of the graph.
+    `refs`: every derived tensor that hipops.memo / fused.WeightCache handed to a captured launch; the launches hold raw pointers to them, so
+    whoever keeps the graph keeps `refs`.  Capture records without executing; nothing is replayed, warned about or swallowed here."""
+    prev, H.CAPTURE_REFS = H.CAPTURE_REFS, []
+    try:
+        with H.capture_guard():
+            graph = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(graph, pool=pool, capture_error_mode='thread_local'), _routed(arena):
+                return graph, fn(), H.CAPTURE_REFS
+    finally:
+        H.CAPTURE_REFS = prev
+
+
+def _synchronize():
+    torch.cuda.synchronize()
+
+
+def _on_side_stream(fn, device):
+    side = torch.cuda.Stream(device=device)
+    side.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(side):
+        res = fn()
+    torch.cuda.current_stream().wait_stream(side)
+    return res
+
+
+class StepGraph:
+    """One optimisation step as a replayed graph.  Each call is exactly one of: a replay (once a graph exists); an eager run of `fn` on a
+    side stream (the first `warmup` calls: allocator / autograd state, lazy kernel attributes); the capture followed by its first replay;
+    or, from a refused capture on, an eager run on the current stream (same kernels), announced once by a warning.  Eager runs and the
+    capture route `arena` when one is given.  `result` is what `fn` returned last: under replay, the capture's static tensors."""
+
+    def __init__(self, name, fn, before_capture, *, arena=None, warmup=2, device=None):
+        self.name, self.fn, self.before_capture, self.arena, self.warmup, self.device = name, fn, before_capture, arena, warmup, device
+        self.graph, self.error, self.refs, self.result, self.warmed = None, None, None, None, 0
+
+    def _eager(self):
+        with _routed(self.arena):
+            return self.fn()
+
+    def __call__(self):
+        if self.graph is not None:
+            self.graph.replay()
+        elif self.error is not None:
+            self.result = self._eager()
+        elif self.warmed < self.warmup:
+            self.result = _on_side_stream(self._eager, self.device)
+            self.warmed += 1
+        else:
+            _synchronize()
+            self.before_capture()
+            D.assert_comm_ready()                 # multi-rank: RCCL's communicator must exist before anything is captured
+            try:
+                self.graph, self.result, self.refs = capture(self.fn, arena=self.arena)
+            except RuntimeError as e:             # the runtime refused the capture: keep going eagerly, say so
+                self.error = e
+                warnings.warn(f'{self.name}: HIP graph capture failed ({e}); continuing with eager launches')
+                _synchronize()
+                self.before_capture()
+                self.result = self._eager()
+            else:
+                self.graph.replay()               # capture records without executing
+        return self.result
+
+
 class _PerG:
     def __init__(self):
         self.counts, self.entries, self.failed = {}, {}, set()
-
-
-class _Entry:
-    pass
 
 
 def _leaves(G):
@@ -185,7 +259,7 @@ def _capture(G, impl, ws, c, uni, kw, leaves, need_grad, pack_inside):
     """Capture forward (and backward) for this signature; returns the entry.  Two passes: the first sizes the zero arenas (every
     zero-initialised accumulator of the step comes out of one buffer cleared by one launch, hipops.ZeroArena), the second is kept."""
     dev = ws.device
-    e = _Entry()
+    e = types.SimpleNamespace()
     e.ws_req, e.c_req = bool(need_grad and ws.requires_grad), bool(need_grad and c.requires_grad)
     e.s_ws = ws.detach().clone().requires_grad_(e.ws_req)
     e.s_c = c.detach().clone().requires_grad_(e.c_req)
@@ -197,16 +271,10 @@ def _capture(G, impl, ws, c, uni, kw, leaves, need_grad, pack_inside):
     # image must be rebuilt INSIDE the captured forward -- a new optimiser epoch makes the caches of trainable weights miss (frozen ones keep
     # their images: fused.WeightCache.key_of, hipops.memo)
     s_uni = (e.s_u1, e.s_u2) if e.s_u1 is not None else None
-    for attempt in range(2):
-        keep = attempt == 1
+    for keep in (False, True):
         if pack_inside:
             H.weights_changed()
-        refs = H.CAPTURE_REFS = []     # every derived tensor the launches of this capture were handed (they hold raw pointers to them)
-        try:
-            e_fwd_bwd = _capture_once(G, impl, e, kw, leaves, need_grad, s_uni)
-        finally:
-            H.CAPTURE_REFS = None
-        fwd, bwd, outs, req, gouts, gins, padded = e_fwd_bwd
+        fwd, bwd, outs, req, gouts, gins, padded, refs = _capture_once(G, impl, e, kw, leaves, need_grad, s_uni)
         if keep:
             e.fwd, e.bwd = fwd, bwd
             e.s_out = [o.detach() for o in outs]
@@ -215,17 +283,18 @@ def _capture(G, impl, ws, c, uni, kw, leaves, need_grad, pack_inside):
             e.s_gin = list(gins) if gins is not None else []
             e.grad_targets = ([ws] if e.ws_req else []) + ([c] if e.c_req else []) + list(leaves)      # .grad holders (the user's tensors)
             e.refs = refs
-        del e_fwd_bwd, fwd, bwd, outs, gouts, gins
+        del fwd, bwd, outs, gouts, gins
     STATS['captured'] += 1
     return e
 
 
 def _capture_once(G, impl, e, kw, leaves, need_grad, s_uni):
-    fwd = torch.cuda.CUDAGraph()
+    def forward():
+        with torch.set_grad_enabled(need_grad):
+            return impl(e.s_ws, e.s_c, render_uniforms=s_uni, **kw)
+
     with _aliased_leaves(G, leaves) as aliases:
-        with H.capture_guard(), torch.cuda.graph(fwd, capture_error_mode='thread_local'), H.zero_arena(e.arena_f):
-            with torch.set_grad_enabled(need_grad):
-                out = impl(e.s_ws, e.s_c, render_uniforms=s_uni, **kw)
+        fwd, out, refs = capture(forward, arena=e.arena_f)
     img, raw = out['image'], out['image_raw']
     img4, raw4 = getattr(img, '_eg3d_padded4', None), getattr(raw, '_eg3d_padded4', None)
     outs = [img4 if img4 is not None else img, raw4 if raw4 is not None else raw, out['image_depth']]
@@ -234,11 +303,11 @@ def _capture_once(G, impl, e, kw, leaves, need_grad, s_uni):
     targets = ([e.s_ws] if e.ws_req else []) + ([e.s_c] if e.c_req else []) + list(aliases)
     if any(req):
         gouts = [torch.zeros_like(o) for o, r in zip(outs, req) if r]
-        bwd = torch.cuda.CUDAGraph()
-        with H.capture_guard(), torch.cuda.graph(bwd, pool=fwd.pool(), capture_error_mode='thread_local'), H.zero_arena(e.arena_b):
-            gins = torch.autograd.grad([o for o, r in zip(outs, req) if r], targets, gouts, allow_unused=True)
+        bwd, gins, refs_b = capture(lambda: torch.autograd.grad([o for o, r in zip(outs, req) if r], targets, gouts, allow_unused=True),
+                                    arena=e.arena_b, pool=fwd.pool())
+        refs = refs + refs_b
     del aliases, targets
-    return fwd, bwd, outs, req, gouts, gins, (img4 is not None, raw4 is not None)
+    return fwd, bwd, outs, req, gouts, gins, (img4 is not None, raw4 is not None), refs
 
 
 def _wrap(e, outs):
@@ -291,7 +360,6 @@ def synthesis(G, impl, ws, c, render_uniforms=None, **kw):
         try:
             e = _capture(G, impl, ws, c, render_uniforms, kw, leaves, need_grad, pack_inside)
         except RuntimeError as err:          # the runtime refused the capture: keep launching kernel by kernel (same kernels), say so once
-            import warnings
             st.failed.add(key)
             STATS['capture_failed'] += 1
             warnings.warn(f'G.synthesis: HIP graph capture failed ({err}); continuing with per-kernel launches')

@@ -330,8 +330,8 @@ def weights_changed():
 
 
 
-CAPTURE_REFS = None           # a list while graphed._capture runs: every derived tensor handed out (memo / WeightCache) is appended, so that the
-                              # captured graph's entry can keep alive what its kernels hold raw pointers to
+CAPTURE_REFS = None           # a list while graphed.capture runs: every derived tensor handed out (memo / WeightCache) is appended, so that the
+                              # captured graph's owner can keep alive what its kernels hold raw pointers to
 
 
 def keep_for_capture(*objs):

@@ -22,6 +22,7 @@ import torch.nn.functional as F
 
 from . import hipops
 from . import fused as _fused
+from . import graphed as _graphed
 from .torch_utils.ops import bias_act, conv2d_gradfix
 
 
@@ -358,10 +359,16 @@ def _area_resize(img: torch.Tensor, size: int) -> torch.Tensor:
 # replayed G.synthesis (graphed.py) copies ws into a dense static buffer and sums d w per row and then over the rows, the eager call sums all layers into
 # one row -- two roundings of the same exact sums, and which steps replay depends on what ran before (two runs would differ by ~4e-7 in w)
 BROADCAST_WS = not hipops.L.DETERMINISTIC
-REG_BRANCH = False          # the noise regulariser on a second stream (a branch of the captured graph): measured -1.5 %
 
 
-class LatentProjector:
+class _StepGraphState:
+    """What the benchmark, the coach, the tests and the tools read of a loop's `_step_graph` (graphed.StepGraph), under the names they know."""
+    _graph = property(lambda self: self._step_graph.graph)
+    _graph_warmup = property(lambda self: self._step_graph.warmup)
+    graph_capture_error = property(lambda self: self._step_graph.error)
+
+
+class LatentProjector(_StepGraphState):
     """Phase A.  One `step()` = pose chain (optional) -> G.synthesis with grad -> [canonical no-grad forward + warping loss] ->
     feature distance + 1e5 * noise regulariser -> backward -> Adam steps -> noise renormalisation.
 
@@ -395,7 +402,9 @@ class LatentProjector:
         N = self.N = int(target.shape[0])
         if N > 1 and optimize_pose:
             raise NotImplementedError('batched projection optimises latents and noise maps; the pose chain / warping loss are per image (N = 1)')
-        self.use_graph, self._graph, self._graph_warmup, self.graph_capture_error = use_graph, None, graph_warmup, None
+        self.use_graph = use_graph
+        self._step_graph = _graphed.StepGraph('LatentProjector', lambda: self._step_body(self._scale_t, self._wn, self.synth_kwargs, True),
+                                              self._zero_grads, warmup=graph_warmup, device=dev)
         self.G = G.eval().requires_grad_(False)
         self.dev = dev
         self.pose_net = None
@@ -510,9 +519,8 @@ class LatentProjector:
                 self.translation_optimizer = torch.optim.Adam([self.translation_opt], lr=translation_lr, capturable=use_graph)
         self.step_idx = 0
         self.last = {}
-        self._reg_stream = None
         self._one = None
-        self._arena = None
+        self._arena = hipops.ZeroArena(torch.device(dev))
 
     @property
     def quat(self):
@@ -541,10 +549,8 @@ class LatentProjector:
         deterministic runs; otherwise they are drawn on the device.
 
         With `use_graph=True` the whole step (~640 kernel launches: synthesis forward and backward, loss, fused Adam, noise
-        renormalisation) is captured once into a HIP graph after `graph_warmup` eager steps and replayed afterwards; the per-step
-        schedule values (latent-noise scale, learning rate) and the latent noise are device tensors refreshed before each replay.
-        The host then issues one graph launch per step instead of ~640 launches (~20 us of Python/ctypes each, which is about the
-        GPU time of the step itself)."""
+        renormalisation) is warmed up, captured and replayed by `graphed.StepGraph`: one graph launch per step; the per-step schedule
+        values (latent-noise scale, learning rate) and the latent noise are device tensors refreshed before each replay."""
         step = self.step_idx
         w_noise_scale, lr = self._schedule(step)
         if self.use_graph:
@@ -566,40 +572,12 @@ class LatentProjector:
                 self._wn.normal_(generator=self.gen)
             if self._uni is not None:         # every step, the eager camera-preheat ones included: they render from the same buffer
                 self._uni.uniform_(generator=self.gen)
-            if self._graph is not None:
-                self._graph.replay()
-            elif step < self.preheat:
+            if self._graph is None and step < self.preheat:
                 # camera preheat (pose chain): the latent is frozen and un-noised for these steps (w_projector.py:249-253) -- different
-                # control flow, run eagerly; the steady-state step is captured afterwards
+                # control flow, run eagerly, no warm-up call.  Once a graph exists no step runs eagerly: _step_body's arena is the graph's alone
                 self.last = self._step_body(self._scale_t, None, self.synth_kwargs, False)
-            elif step < self.preheat + self._graph_warmup or self.graph_capture_error is not None:
-                # eager: warm-up on a side stream (allocator / autograd state, lazy kernel attributes), or capture was refused
-                side = torch.cuda.Stream(device=self.dev)
-                side.wait_stream(torch.cuda.current_stream())
-                with torch.cuda.stream(side):
-                    self.last = self._step_body(self._scale_t, self._wn, self.synth_kwargs, True)
-                torch.cuda.current_stream().wait_stream(side)
             else:
-                torch.cuda.synchronize()
-                self.optimizer.zero_grad(set_to_none=True)
-                if self.optimize_pose:
-                    self.cam_optimizer.zero_grad(set_to_none=True)
-                    self.translation_optimizer.zero_grad(set_to_none=True)
-                from . import dist as _D
-                _D.assert_comm_ready()                # multi-rank: RCCL's communicator must exist before anything is captured
-                graph = torch.cuda.CUDAGraph()
-                try:
-                    with hipops.capture_guard(), torch.cuda.graph(graph, capture_error_mode='thread_local'):   # other threads (RCCL watchdog) may touch the runtime
-                        self.last = self._step_body(self._scale_t, self._wn, self.synth_kwargs, True)
-                    self._graph = graph
-                    graph.replay()                    # capture records without executing
-                except RuntimeError as e:             # the runtime refused the capture: keep optimising eagerly (same kernels), say so
-                    import warnings
-                    self.graph_capture_error = e
-                    warnings.warn(f'LatentProjector: HIP graph capture failed ({e}); continuing with eager launches')
-                    torch.cuda.synchronize()
-                    self.optimizer.zero_grad(set_to_none=True)
-                    self.last = self._step_body(self._scale_t, self._wn, self.synth_kwargs, True)
+                self.last = self._step_graph()
             self.step_idx += 1
             return self.last
         for g in self.optimizer.param_groups:
@@ -611,9 +589,13 @@ class LatentProjector:
         self.step_idx += 1
         return self.last
 
+    def _zero_grads(self):
+        self.optimizer.zero_grad(set_to_none=True)
+        if self.optimize_pose:
+            self.cam_optimizer.zero_grad(set_to_none=True)
+            self.translation_optimizer.zero_grad(set_to_none=True)
+
     def _step_body(self, w_noise_scale, wn, kw, do_step):
-        if self._arena is None:
-            self._arena = hipops.ZeroArena(torch.device(self.dev))
         with hipops.zero_arena(self._arena):
             return self._step_body_inner(w_noise_scale, wn, kw, do_step)
 
@@ -624,28 +606,16 @@ class LatentProjector:
             pred_ext, pred_cam = pose_chain(pred, self.translation_opt, self.intrinsic, self.radius, self.pose_mode)
         else:
             pred_ext, pred_cam = None, self.cam
-        # The noise regulariser only reads the noise buffers.  While its kernel occupied 17 CUs for ~0.4 ms (rounds 1-2) it ran on a second
-        # stream -- a parallel branch of the captured graph, joined where the loss is formed.  Since it is three multi-block passes of
-        # ~50 us together the fork / join of the replayed graph costs more than it hides: in line by default (+1.5 % per step), the branch
-        # stays available as the module attribute REG_BRANCH.
-        cur = torch.cuda.current_stream()
-        reg_branch = REG_BRANCH
-        if reg_branch and self._reg_stream is None:
-            self._reg_stream = torch.cuda.Stream(device=self.dev)
-            _quiet = getattr(torch.autograd.graph, 'set_warn_on_accumulate_grad_stream_mismatch', None)
-            if _quiet is not None:      # the noise buffers' gradients are accumulated from two streams on purpose
-                _quiet(False)
-        if reg_branch:
-            self._reg_stream.wait_stream(cur)
-        with torch.cuda.stream(self._reg_stream if reg_branch else cur):
-            # value AND gradient of the regulariser for all 17 buffers from one launch; the gradient is added to the buffers' .grad
-            # after backward with one fused multi-tensor add (through autograd it would be 17 AccumulateGrad add launches)
-            if self._buf_views is None:
-                reg, reg_grads = hipops.noise_regularizer([b.detach() for b in self._all_bufs], scale=float(self.reg_w), want_grad=True)
-            else:       # batched: the same kernel over the N x 17 per-image maps, gradients assembled per map tensor
-                reg_grads = [torch.empty_like(t) for t in self._all_bufs]
-                reg, _ = hipops.noise_regularizer(self._buf_views, scale=float(self.reg_w), want_grad=True,
-                                                  grads=[g[i, 0] for g in reg_grads for i in range(self.N)])
+        # The noise regulariser only reads the noise buffers: value AND gradient for all 17 buffers from one launch, in line (on a second
+        # stream it was a parallel branch of the captured graph, whose fork / join cost more than it hid: -1.5 % per step; DESIGN.md 3.3: no
+        # forked branches in a captured step).  The gradient is added to the buffers' .grad after backward with one fused multi-tensor add
+        # (through autograd it would be 17 AccumulateGrad add launches)
+        if self._buf_views is None:
+            reg, reg_grads = hipops.noise_regularizer([b.detach() for b in self._all_bufs], scale=float(self.reg_w), want_grad=True)
+        else:       # batched: the same kernel over the N x 17 per-image maps, gradients assembled per map tensor
+            reg_grads = [torch.empty_like(t) for t in self._all_bufs]
+            reg, _ = hipops.noise_regularizer(self._buf_views, scale=float(self.reg_w), want_grad=True,
+                                              grads=[g[i, 0] for g in reg_grads for i in range(self.N)])
         w = self.w_opt
         if wn is not None:          # w + wn * scale in one launch (scale: a device scalar under graph replay)
             w = torch.addcmul(w, wn, w_noise_scale) if torch.is_tensor(w_noise_scale) else torch.add(w, wn, alpha=float(w_noise_scale))
@@ -672,8 +642,6 @@ class LatentProjector:
                 img = _area_resize(img, 256)
         dist_i = LN.sqdist(self.feature_net(img), self.target_features)              # per image; independent trajectories: the sum's
         dist = dist_i.sum() if dist_i.numel() > 1 else dist_i.reshape(())            # gradient is each image's own gradient (one image: a view)
-        if reg_branch:
-            cur.wait_stream(self._reg_stream)
         loss = dist + reg                         # reported value; only `dist` (and the warping term) goes through autograd
         warp = None
         if self.use_warp and self.optimize_pose:
@@ -684,10 +652,7 @@ class LatentProjector:
             if share:
                 G._last_planes = None          # (nothing outside this step may render stale planes)
             loss = loss + warp
-        self.optimizer.zero_grad(set_to_none=True)
-        if self.optimize_pose:
-            self.cam_optimizer.zero_grad(set_to_none=True)
-            self.translation_optimizer.zero_grad(set_to_none=True)
+        self._zero_grads()
         if self._one is None:
             self._one = torch.ones((), device=dist.device)          # the seed gradient, allocated once (backward() would fill a new one per step)
         (dist if warp is None else dist + warp).backward(gradient=self._one)
@@ -721,7 +686,7 @@ class LatentProjector:
         return last
 
 
-class PivotalTuner:
+class PivotalTuner(_StepGraphState):
     """Phase B.  One `step()` = G.synthesis(w_pivot, cam) with default kwargs (noise_mode='random') -> L2 + LPIPS at 512^2 and
     128^2 + depth TV -> backward into all generator weights -> Adam."""
 
@@ -752,7 +717,12 @@ class PivotalTuner:
             # the targets with 4-float pixels (channel 3 = 0), the layout the SR head and the renderer hand their images over in
             self.target4 = _pad_cl4(target)
             self.target4_128 = _pad_cl4(self.target_128)
-        self.use_graph, self._graph, self._graph_warmup, self.graph_capture_error, self._eager_steps = bool(use_graph), None, int(graph_warmup), None, 0
+        self.use_graph = bool(use_graph)
+        # every zero-initialised accumulator of the step (split-K outputs, gradient sums) comes out of one arena cleared by one launch;
+        # nothing allocated from it outlives the step (gradients are consumed by optimizer.step() below)
+        self._step_graph = _graphed.StepGraph('PivotalTuner', lambda: self._step(False), lambda: self.optimizer.zero_grad(set_to_none=True),
+                                              arena=hipops.ZeroArena(target.device), warmup=int(graph_warmup), device=target.device)
+        self._arena_eager = hipops.ZeroArena(target.device)
         # Adam over the 30.7 M parameters.  The library's own kernel (eg3d_adam_step, hipops.HipAdam; EG3D_HIP_ADAM=0 -> torch's fused
         # multi-tensor Adam): device-side learning rate / step count AND a device-side skip flag -- the early stop of the reference's loop
         # (`if loss_lpips <= threshold: break` BEFORE the update, single_id_coach.py:68-71) then needs no host sync: the captured step
@@ -770,7 +740,8 @@ class PivotalTuner:
         self.synth_kwargs = dict(synth_kwargs or {})
         self.synth_kwargs.setdefault('sr_fp16', bool(sr_fp16))
         self.last = {}
-        self._arena = self._arena_eager = None
+
+    _arena = property(lambda self: self._step_graph.arena)
 
     def _fused_objective(self, out):
         """The same objective as the ATen composition in `_step` from five reduction launches per direction (loss_nets.weighted_objective):
@@ -798,55 +769,16 @@ class PivotalTuner:
         return total, parts.unbind(0)
 
     def step(self, early_stop: bool = False, **step_kwargs) -> Dict[str, torch.Tensor]:
-        # every zero-initialised accumulator of the step (split-K outputs, gradient sums) comes out of one arena cleared by one launch;
-        # nothing allocated from it outlives the step (gradients are consumed by optimizer.step() below)
-        if self._arena is None:
-            self._arena = hipops.ZeroArena(self.target.device)
         if not self.use_graph or early_stop or self.graph_capture_error is not None:
             # the captured graph holds raw pointers into self._arena.buf, which begin() re-allocates when the demand grows (an eager step
             # with other shapes or a fallback path): once a graph exists, eager steps take their accumulators from an arena of their own
-            if self._graph is not None:
-                if self._arena_eager is None:
-                    self._arena_eager = hipops.ZeroArena(self.target.device)
-                arena = self._arena_eager
-            else:
-                arena = self._arena
-            with hipops.zero_arena(arena):
+            with hipops.zero_arena(self._arena if self._graph is None else self._arena_eager):
                 return self._step(early_stop, **step_kwargs)
         if step_kwargs:
             raise ValueError('use_graph: per-step synthesis kwargs cannot change between replays; pass them as synth_kwargs')
+        self.last = self._step_graph()
         if self._graph is not None:
-            self._graph.replay()
-            hipops.weights_changed()              # the optimizer's post-step hook does not run under replay
-            self.last = self._graph_last
-            return self.last
-        if self._eager_steps < self._graph_warmup:             # warm-up on a side stream (allocator / autograd state, lazy kernel attributes)
-            side = torch.cuda.Stream(device=self.target.device)
-            side.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(side), hipops.zero_arena(self._arena):
-                res = self._step(False)
-            torch.cuda.current_stream().wait_stream(side)
-            self._eager_steps += 1
-            return res
-        torch.cuda.synchronize()
-        self.optimizer.zero_grad(set_to_none=True)
-        from . import dist as _D
-        _D.assert_comm_ready()
-        graph = torch.cuda.CUDAGraph()
-        try:
-            with hipops.capture_guard(), torch.cuda.graph(graph, capture_error_mode='thread_local'), hipops.zero_arena(self._arena):
-                self._step(False)
-            self._graph, self._graph_last = graph, self.last
-            graph.replay()                        # capture records without executing
-            hipops.weights_changed()
-        except RuntimeError as e:                 # the runtime refused the capture: keep tuning eagerly (same kernels), say so
-            import warnings
-            self.graph_capture_error = e
-            warnings.warn(f'PivotalTuner: HIP graph capture failed ({e}); continuing with eager launches')
-            torch.cuda.synchronize()
-            self.optimizer.zero_grad(set_to_none=True)
-            with hipops.zero_arena(self._arena):
-                return self._step(False)
+            hipops.weights_changed()              # after the capture's first replay and every later one: the optimizer's post-step hook does not run under replay
         return self.last
 
     def _step(self, early_stop: bool = False, **step_kwargs) -> Dict[str, torch.Tensor]:

@@ -558,7 +558,13 @@ def amax_of(t):
 
 
 class SplitImage:
-    """Two-piece fp16 image of an operand + the power-of-two scale it was written with (device scalar)."""
+    """Two-piece fp16 image of an operand + the power-of-two scale it was written with (device scalar).
+
+    An element v leaves as a = fl32(v * scale), hi = fp16(a) rounded toward zero, lo = fp16((a - hi) * lo_mul) rounded to nearest, and reads back as
+    (hi + lo / lo_mul) / scale; scale brings the operand's range to [2^13, 2^14).
+      activations   [N][2 piece][C/8][H*W][8],              lo_mul = 2048  (shape = (N, C, H, W); v = x * in_scale[n, c])
+      weights       [T][I/16][2 piece][2 koct][O][8],       lo_mul = 1     (shape = (O, I, T); element w[o, tap * I + (2 chunk + koct) * 8 + lane])
+    tests/support/split_ref.py restates both bit for bit (and decodes them); tests/test_gpu_split.py holds the kernels to it."""
     __slots__ = ('data', 'scale', 'shape')
 
     def __init__(self, data, scale, shape):
@@ -579,8 +585,11 @@ def split_activation(x, x_amax, in_scale=None, s_amax=None, C=None):
 
 
 def split_weight(wp, O, I, T):
-    """Packed fp32 weights [O, T*I] (forward or adjoint image) -> SplitImage [T][I/16][2][2][O][8] fp16 (unscaled low piece)."""
-    amax = absmax(wp)
+    """Packed fp32 weights [O, T*I] (forward or adjoint image; rows may be a view of a wider matrix: the kernel takes the row pitch) -> SplitImage
+    [T][I/16][2][2][O][8] fp16 (unscaled low piece)."""
+    assert wp.dtype == torch.float32 and tuple(wp.shape) == (O, T * I) and wp.stride(1) == 1 and wp.stride(0) >= T * I
+    # eg3d_absmax reads a dense array: of a row view it would reduce the first O*T*I floats of the wider matrix (columns that are not weights, rows missing)
+    amax = absmax(wp if wp.is_contiguous() else wp.contiguous())
     img = torch.empty((O * T * I * 2,), dtype=torch.float16, device=wp.device)
     scale = torch.empty((1,), dtype=torch.float32, device=wp.device)
     L.check(L.lib().eg3d_split_weight(L.ptr(wp), L.ptr(amax), L.ptr(img), L.ptr(scale), O, I, T, wp.stride(0), L.stream_ptr()), 'split_weight')

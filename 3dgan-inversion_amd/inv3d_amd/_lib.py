@@ -226,6 +226,18 @@ class McParams(C.Structure):
                 ('verts', C.c_void_p), ('vert_capacity', C.c_int64), ('faces', C.c_void_p), ('face_capacity', C.c_int64)]
 
 
+class IsoParams(C.Structure):
+    """eg3d_iso_params: iso-surface ray marcher over a regular grid (eg3d_iso_bricks / eg3d_iso_render)."""
+    _fields_ = [('vol', C.c_void_p), ('bricks', C.c_void_p), ('cams', C.c_void_p), ('depth', C.c_void_p), ('normal', C.c_void_p),
+                ('mask', C.c_void_p), ('hit_k', C.c_void_p), ('shade', C.c_void_p), ('D0', C.c_int32), ('D1', C.c_int32), ('D2', C.c_int32),
+                ('F', C.c_int32), ('res', C.c_int32), ('axes', C.c_int32 * 3), ('origin', C.c_float * 3), ('spacing', C.c_float * 3),
+                ('level', C.c_float), ('step', C.c_float), ('refine', C.c_int32), ('skip', C.c_int32), ('shade_mode', C.c_int32),
+                ('ambient', C.c_float), ('background', C.c_float)]
+
+
+ISO_LAMBERT, ISO_NORMAL = 0, 1
+ISO_BRICK = 8
+
 SSIM_MAX_LEVELS = 8
 
 
@@ -402,6 +414,8 @@ _SIGS = {
     'eg3d_mc_query_workspace': (C.c_int, [C.POINTER(McParams), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     'eg3d_mc_count': (C.c_int, [C.POINTER(McParams), C.c_void_p]),
     'eg3d_mc_emit': (C.c_int, [C.POINTER(McParams), C.c_void_p]),
+    'eg3d_iso_bricks': (C.c_int, [C.POINTER(IsoParams), C.c_void_p]),
+    'eg3d_iso_render': (C.c_int, [C.POINTER(IsoParams), C.c_void_p]),
     'eg3d_ssim_query_workspace': (C.c_int, [C.POINTER(SsimParams), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64),
                                             C.POINTER(C.c_int64)]),
     'eg3d_ssim_forward': (C.c_int, [C.POINTER(SsimParams), C.c_void_p]),

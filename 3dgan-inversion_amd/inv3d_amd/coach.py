@@ -64,8 +64,8 @@ class InversionCoach:
                  start_w_fn: Optional[Callable[[torch.Tensor], torch.Tensor]] = None, sr_fp16: bool = True, gen_mesh: bool = False,
                  mesh_dir: Optional[str] = None, mesh_res: int = 512, mesh_level: float = 10.0, mesh_format: str = '.mrc',
                  do_evaluation: bool = False, eval_dir: Optional[str] = None, lpips_eval_net: Optional[Callable] = None,
-                 id_net: Optional[Callable] = None, save_pivot: bool = False, pivot_dir: Optional[str] = None, save_grid: bool = False,
-                 gen_video: bool = False, media_dir: Optional[str] = None, video_quality: int = 90):
+                 id_net: Optional[Callable] = None, save_pivot: bool = False, pivot_dir: Optional[str] = None, shape_views: bool = False,
+                 save_grid: bool = False, gen_video: bool = False, media_dir: Optional[str] = None, video_quality: int = 90):
         """Hyper-parameter names and defaults follow configs/hyperparameters.py.  `early_stop_interval` = how often Phase B reads the
         early-stop state back to the host (1 = every step like the reference).  With the library's Adam the TEST itself runs on the device
         in every step whatever the interval (PivotalTuner.device_stop): the interval then only bounds how many masked no-op steps are
@@ -81,10 +81,13 @@ class InversionCoach:
         under do_evaluation, here it is independent of it (like gen_mesh).
         `save_grid`: video.pivot_grid (target, the render at the pivot camera, three look_at views; noise_mode='const') as
         {media_dir}/pivot/{name}.png before Phase B and {media_dir}/{name}.png after it.  `gen_video` (global_config.gen_video):
-        video.write_orbit_video (240 frames, 60 fps, JPEG quality `video_quality`) as {media_dir}/pivot/{name}_pivot.avi and {media_dir}/{name}.avi."""
+        video.write_orbit_video (240 frames, 60 fps, JPEG quality `video_quality`) as {media_dir}/pivot/{name}_pivot.avi and {media_dir}/{name}.avi.
+        `shape_views` (no reference counterpart): both get shaded views of the density surface beside the renders (shape=True of
+        video.pivot_grid: a second row; of video.write_orbit_video: image | shape, twice the width)."""
         if (save_grid or gen_video) and not media_dir:
             raise ValueError('save_grid / gen_video need a media_dir')
         self.save_grid, self.gen_video, self.media_dir, self.video_quality = save_grid, gen_video, media_dir, int(video_quality)
+        self.shape_views = bool(shape_views)
         if do_evaluation and not eval_dir:
             raise ValueError('do_evaluation needs an eval_dir')
         if save_pivot and not pivot_dir:
@@ -222,10 +225,10 @@ class InversionCoach:
         grid_path = video_path = None
         if self.save_grid:
             grid_path = os.path.join(d, f'{name}.png')
-            write_png(grid_path, pivot_grid(self.G, w_pivot, cam, target, **self.synth_kwargs))
+            write_png(grid_path, pivot_grid(self.G, w_pivot, cam, target, shape=self.shape_views, **self.synth_kwargs))
         if self.gen_video:
             video_path = os.path.join(d, f'{name}_pivot.avi' if pivot else f'{name}.avi')
-            write_orbit_video(self.G, w_pivot, video_path, quality=self.video_quality, **self.synth_kwargs)
+            write_orbit_video(self.G, w_pivot, video_path, quality=self.video_quality, shape=self.shape_views, **self.synth_kwargs)
         return grid_path, video_path
 
     def write_mesh(self, name: str, w_pivot: torch.Tensor) -> str:

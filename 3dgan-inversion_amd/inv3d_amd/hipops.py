@@ -1798,6 +1798,87 @@ def marching_cubes(vol: torch.Tensor, level: float, origin=None, spacing=None):
     return verts, faces
 
 
+def _iso_grid_params(vol: torch.Tensor, what: str):
+    L.require_cuda(vol)
+    if vol.dim() != 3 or vol.dtype != torch.float32:
+        raise L.Eg3dHipError(f'{what}: a 3-D fp32 grid, got {tuple(vol.shape)} {vol.dtype}')
+    vol = vol.contiguous()
+    return vol, L.IsoParams(vol=vol.data_ptr(), D0=vol.shape[0], D1=vol.shape[1], D2=vol.shape[2])
+
+
+def iso_bricks_shape(shape):
+    """Bricks per axis of a grid of `shape`: ceil((D - 1) / 8)."""
+    return tuple((int(d) + L.ISO_BRICK - 2) // L.ISO_BRICK for d in shape)
+
+
+def iso_bricks(vol: torch.Tensor) -> torch.Tensor:
+    """fp32 [B0,B1,B2], B = ceil((D - 1) / 8): per 8x8x8-cell brick of the fp32 grid vol [D0,D1,D2] the maximum over the brick's corner range
+    dilated by one voxel on every side (NaN ignored) -- what iso_render's empty-space skipping reads.  It does not depend on the level: one
+    pass per grid serves every level and every frame (eg3d_iso_bricks; include/eg3d_hip.h "Shape views").  One launch."""
+    vol, p = _iso_grid_params(vol, 'iso_bricks')
+    out = torch.empty(iso_bricks_shape(vol.shape), dtype=torch.float32, device=vol.device)
+    p.bricks = out.data_ptr()
+    L.check(L.lib().eg3d_iso_bricks(C.byref(p), L.stream_ptr()), 'iso_bricks')
+    return out
+
+
+ISO_SHADE_MODES = dict(lambert=L.ISO_LAMBERT, normal=L.ISO_NORMAL)
+
+
+def iso_render(vol: torch.Tensor, cams: torch.Tensor, res: int, level: float, origin, spacing, axes=(0, 1, 2), step: float = 0.5, refine: int = 4,
+               bricks: Optional[torch.Tensor] = None, skip: bool = True, shade: str = 'lambert', ambient: float = 0.15, background: float = 1.0,
+               want_hit_k: bool = False) -> dict:
+    """First-hit views of the surface {vol = level} of the fp32 grid vol [D0,D1,D2] from the cameras cams [F,25] (cam2world 16 + intrinsics 9,
+    the generator's conditioning vectors) at res x res pixels; the rays are RaySampler's, so the frames register with G.synthesis's images
+    (eg3d_iso_render; the algorithm is specified operation by operation in include/eg3d_hip.h "Shape views").  Grid index i of grid axis a sits
+    at world coordinate origin[a] + i * spacing[a] of world axis axes[a]; spacing may be negative.  Inside = v > level; NaN never hits.
+    Samples every step * min|spacing| along the ray, trilinear field, `refine` bisections and one secant step at the first crossing.
+    Returns a dict:
+      depth  fp32 [F,res,res]     distance along the unit ray in world units (what image_depth measures), 0 on a miss
+      normal fp32 [F,res,res,3]   world-space unit normal toward lower values, 0 on a miss or where the gradient vanishes
+      mask   uint8 [F,res,res]
+      shade  fp32 [F,3,res,res]   in [-1,1], ready for jpeg_encode / image_grid_u8 (which show x * 127.5 + 128):
+                                  'lambert': grey v * 2 - 1 with v = ambient + (1 - ambient) * max(0, n . -d) in [0,1] (a headlight);
+                                  'normal':  colour * 2 - 1 with colour = camera-space normal * 0.5 + 0.5 in [0,1];
+                                  a miss takes `background`, which is already in [-1,1] (1.0 = white)
+      hit_k  int32 [F,res,res]    with want_hit_k: index of the hit sample, -1 on a miss
+      bricks                      the brick maxima used (pass them back in for the next call on the same grid)
+    skip=True jumps over bricks whose maximum is <= level; the outputs are bit-identical either way.  One launch (two when it has to build the
+    bricks), no host synchronise."""
+    vol, p = _iso_grid_params(vol, 'iso_render')
+    L.require_cuda(cams)
+    if cams.dim() != 2 or cams.shape[1] != 25 or cams.shape[0] < 1:
+        raise L.Eg3dHipError(f'iso_render: cameras [F >= 1, 25], got {tuple(cams.shape)}')
+    if shade not in ISO_SHADE_MODES:
+        raise L.Eg3dHipError(f'iso_render: shade {sorted(ISO_SHADE_MODES)}, got {shade!r}')
+    cams = cams.to(device=vol.device, dtype=torch.float32).contiguous()
+    dev, F, res = vol.device, cams.shape[0], int(res)
+    if skip:
+        if bricks is None:
+            bricks = iso_bricks(vol)
+        L.require_cuda(bricks)
+        if tuple(bricks.shape) != iso_bricks_shape(vol.shape) or bricks.dtype != torch.float32 or not bricks.is_contiguous():
+            raise L.Eg3dHipError(f'iso_render: bricks must be contiguous fp32 {iso_bricks_shape(vol.shape)}, got {tuple(bricks.shape)} {bricks.dtype}')
+    if res < 1:
+        raise L.Eg3dHipError(f'iso_render: res >= 1, got {res}')
+    out = dict(depth=torch.empty((F, res, res), dtype=torch.float32, device=dev), normal=torch.empty((F, res, res, 3), dtype=torch.float32, device=dev),
+               mask=torch.empty((F, res, res), dtype=torch.uint8, device=dev), shade=torch.empty((F, 3, res, res), dtype=torch.float32, device=dev))
+    if want_hit_k:
+        out['hit_k'] = torch.empty((F, res, res), dtype=torch.int32, device=dev)
+        p.hit_k = out['hit_k'].data_ptr()
+    p.cams, p.bricks = cams.data_ptr(), (bricks.data_ptr() if skip else None)
+    p.depth, p.normal, p.mask, p.shade = out['depth'].data_ptr(), out['normal'].data_ptr(), out['mask'].data_ptr(), out['shade'].data_ptr()
+    p.F, p.res = F, res
+    p.axes[:] = [int(v) for v in axes]
+    p.origin[:] = [float(v) for v in origin]
+    p.spacing[:] = [float(v) for v in spacing]
+    p.level, p.step, p.refine, p.skip = float(level), float(step), int(refine), int(bool(skip))
+    p.shade_mode, p.ambient, p.background = ISO_SHADE_MODES[shade], float(ambient), float(background)
+    L.check(L.lib().eg3d_iso_render(C.byref(p), L.stream_ptr()), 'iso_render')
+    out['bricks'] = bricks
+    return out
+
+
 def _ssim_params(x, y, mode, weights, nonnegative, size_average, win_size, win_sigma, C1, C2):
     N, Ch, Hh, Ww = x.shape
     p = L.SsimParams(x=x.data_ptr(), y=y.data_ptr(), N=N, C=Ch, H=Hh, W=Ww, mode=mode, levels=len(weights), nonnegative=int(bool(nonnegative)),

@@ -9,6 +9,8 @@ G.mapping / ImportanceRenderer.run_model on the gfx950 kernels.
   extract_mesh, write_ply      <- create_geometry's '.ply' branch (single_id_coach.py:155-157) and convert_sdf_samples_to_ply /
                                   convert_mrc, shape_utils.py:40-100: marching cubes on the device (hipops.marching_cubes), no skimage / plyfile
   write_mrc                    <- create_geometry's '.mrc' branch (single_id_coach.py:158-160, mrcfile.new_mmap mode 2), no mrcfile
+  grid_frame, render_shape,    no reference counterpart: shaded first-hit views of the density surface from the generator's own cameras
+  render_shape_orbit              (hipops.iso_render over density_grid's grid), to look at the recovered shape without an external viewer
 
 Differences from the reference that do not change results: the tri-planes of a fixed latent are synthesised once per orbit / per grid
 instead of once per frame / per chunk (the reference re-runs the backbone every time), and grid coordinates are generated per chunk on
@@ -134,6 +136,50 @@ def extract_mesh(G, ws: torch.Tensor, res: int = 512, level: float = 10.0, max_b
     from .hipops import marching_cubes
     grid = density_grid(G, ws, res=res, max_batch=max_batch, **synthesis_kwargs)
     return marching_cubes(grid, level)
+
+
+def grid_frame(G, res: int):
+    """(origin, spacing, axes) of density_grid(G, ws, res)'s layout for hipops.iso_render: grid index i of grid axis a sits at world coordinate
+    origin[a] + i * spacing[a] of world axis axes[a].  Grid axes 0, 1, 2 run along world x, y, z over [-L/2, L/2] (L = box_warp) with
+    res points each, and axis 0 is flipped (create_geometry's flip): its index 0 is x = +L/2 and its spacing is negative.
+    The reference's float-division skew (_grid_points: the two slow coordinates carry the faster indices' fractions, less than one voxel) is
+    ignored: the frame is the regular grid those points were meant to be."""
+    box = float(G.rendering_kwargs['box_warp'])
+    vs = box / (int(res) - 1)
+    return (box / 2, -box / 2, -box / 2), (-vs, vs, vs), (0, 1, 2)
+
+
+@torch.no_grad()
+def render_shape(G, ws: torch.Tensor, cameras: torch.Tensor, res: Optional[int] = None, grid_res: int = 512, level: float = 10.0,
+                 grid: Optional[torch.Tensor] = None, **kw) -> dict:
+    """Shaded first-hit views of the sigma = level surface of one latent from `cameras` [F,25]: hipops.iso_render's dict (depth, normal, mask,
+    shade [F,3,res,res] in [-1,1], bricks) plus 'grid'.  res defaults to the generator's image resolution, so a frame registers pixel for pixel
+    with G.synthesis(ws, camera)['image'].  The density grid (density_grid at grid_res, laid out as grid_frame says) is built here unless one is
+    passed; pass the returned 'grid' and 'bricks' back in (grid=..., bricks=...) to render more views of the same latent.  Further keywords go to
+    hipops.iso_render (step, refine, skip, shade, ambient, background, bricks)."""
+    from .hipops import iso_render
+    if grid is None:
+        grid = density_grid(G, ws, res=grid_res)
+    if grid.dim() != 3 or len(set(grid.shape)) != 1:
+        raise ValueError(f'render_shape: a cubic density grid, got {tuple(grid.shape)}')
+    origin, spacing, axes = grid_frame(G, grid.shape[0])
+    out = iso_render(grid, cameras.to(grid.device), int(G.img_resolution if res is None else res), level, origin, spacing, axes=axes, **kw)
+    out['grid'] = grid
+    return out
+
+
+@torch.no_grad()
+def render_shape_orbit(G, ws: torch.Tensor, num_frames: int = 240, cameras: Optional[torch.Tensor] = None, res: Optional[int] = None,
+                       grid_res: int = 512, level: float = 10.0, grid: Optional[torch.Tensor] = None, **kw) -> Iterator[torch.Tensor]:
+    """Yields one shaded [3,res,res] frame per camera of orbit_cameras (or `cameras`), the companion of render_orbit: one density grid and one
+    brick pass for the whole orbit, one launch per frame."""
+    dev = ws.device
+    cams = orbit_cameras(num_frames, device=dev) if cameras is None else cameras.to(dev)
+    state = dict(grid=grid, bricks=kw.pop('bricks', None))
+    for i in range(cams.shape[0]):
+        out = render_shape(G, ws, cams[i:i + 1], res=res, grid_res=grid_res, level=level, grid=state['grid'], bricks=state['bricks'], **kw)
+        state = dict(grid=out['grid'], bricks=out['bricks'])
+        yield out['shade'][0]
 
 
 def _host(a, dtype):

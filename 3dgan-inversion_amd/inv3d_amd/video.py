@@ -188,14 +188,29 @@ def write_png(path: str, u8_hwc) -> None:
 # ---- the per-image outputs -----------------------------------------------------------------------------------------------------------------------
 @torch.no_grad()
 def write_orbit_video(G, ws: torch.Tensor, path: str, num_frames: int = 240, image_mode: str = 'image', fps: int = 60, quality: int = 90,
-                      batch: int = 16, **synthesis_kwargs) -> int:
+                      batch: int = 16, shape: bool = False, shape_kwargs: Optional[dict] = None, **synthesis_kwargs) -> int:
     """gen_interp_video for one latent: inference.render_orbit's frames, `batch` at a time through hipops.jpeg_encode (4:2:0; grey for
-    image_depth), one device-to-host copy per batch, into a Motion-JPEG AVI at `path`.  Returns the number of frames written."""
+    image_depth), one device-to-host copy per batch, into a Motion-JPEG AVI at `path`.  Returns the number of frames written.
+    shape=True (no reference counterpart): every frame is image | shape side by side, twice the width -- the shaded first-hit view of the
+    density surface from the same camera at the frame's resolution (inference.render_shape; shape_kwargs: grid_res, level, shade, ...).  The
+    density grid and its brick maxima are built once per video.  With shape=False the file is what it was before the option existed."""
     from .hipops import jpeg_encode
-    from .inference import render_orbit
+    from .inference import density_grid, orbit_cameras, render_orbit, render_shape
     if batch < 1:
         raise ValueError('write_orbit_video: batch >= 1')
     writer, pending, n = None, [], 0
+    if shape:
+        skw = dict(shape_kwargs or {})
+        cams = synthesis_kwargs.get('cameras')
+        cams = orbit_cameras(num_frames, device=ws.device) if cams is None else cams.to(ws.device)
+        # before the first frame: the grid runs the backbone, and render_orbit keeps the planes of its first frame for the later ones
+        grid = skw.pop('grid', None)
+        state = dict(grid=density_grid(G, ws, res=skw.get('grid_res', 512)) if grid is None else grid, bricks=skw.pop('bricks', None))
+
+    def beside(i, frame):
+        out = render_shape(G, ws, cams[i:i + 1], res=frame.shape[-1], grid=state['grid'], bricks=state['bricks'], **skw)
+        state['bricks'] = out['bricks']
+        return torch.cat([frame, out['shade'][0, :frame.shape[0]]], dim=-1)
 
     def flush():
         nonlocal writer, n
@@ -208,8 +223,8 @@ def write_orbit_video(G, ws: torch.Tensor, path: str, num_frames: int = 240, ima
         n += len(pending)
         pending.clear()
     try:
-        for frame in render_orbit(G, ws, num_frames=num_frames, image_mode=image_mode, **synthesis_kwargs):
-            pending.append(frame.float().clone())                          # (the frame may be a view of a buffer the next render reuses)
+        for i, frame in enumerate(render_orbit(G, ws, num_frames=num_frames, image_mode=image_mode, **synthesis_kwargs)):
+            pending.append(beside(i, frame.float()) if shape else frame.float().clone())      # (the frame may be a view of a buffer the next render reuses)
             if len(pending) == batch:
                 flush()
         if pending:
@@ -246,14 +261,19 @@ def look_at_small(radius: float = 2.7) -> torch.Tensor:
 
 
 @torch.no_grad()
-def pivot_grid(G, ws: torch.Tensor, cam: torch.Tensor, target: torch.Tensor, **synthesis_kwargs) -> torch.Tensor:
+def pivot_grid(G, ws: torch.Tensor, cam: torch.Tensor, target: torch.Tensor, shape: bool = False, shape_kwargs: Optional[dict] = None,
+               **synthesis_kwargs) -> torch.Tensor:
     """uint8 [H',W',3] on the device: the reference's forward(ws, needs_img_grid='small', grid_num=5, need_gt_ingrid=(target, cam)) after its
     (grid * 127.5 + 128).clamp(0, 255).to(uint8): target, the render at `cam`, and the right / centre / left look_at views, one row of five
     tiled as make_grid(nrow=5, padding=2) (hipops.image_grid_u8; make_grid's float padding 0 is the grey 128 here).
     Rendered with noise_mode='const': the reference calls G.synthesis with its default 'random', which would make the file differ from run
     to run; everything else (full ws, intrinsics 4.2647 / 0.5) is the reference's.  The renderer's stratified-sampling draws are still random
-    unless render_uniforms=(u1, u2) is among the synthesis kwargs."""
+    unless render_uniforms=(u1, u2) is among the synthesis kwargs.
+    shape=True (no reference counterpart) adds a second row: under each of the four renders the shaded first-hit view of the density surface
+    from the same camera (inference.render_shape at the render's resolution; shape_kwargs: grid_res, level, shade, background, ...), under the
+    target a cell of the background value.  The first row is the shape=False grid."""
     from .hipops import image_grid_u8
+    from .inference import render_shape
     dev = ws.device
     K = torch.tensor([4.2647, 0, 0.5, 0, 4.2647, 0.5, 0, 0, 1.])
     cams = [cam[:1].to(dev).float()] + [torch.cat([m, K]).unsqueeze(0).to(dev) for m in look_at_small()]
@@ -261,4 +281,8 @@ def pivot_grid(G, ws: torch.Tensor, cam: torch.Tensor, target: torch.Tensor, **s
     images = [target[:1].to(dev).float()]
     for i, c in enumerate(cams):
         images.append(G.synthesis(ws[:1], c, cache_backbone=(i == 0), use_cached_backbone=(i > 0), **kw)['image'].float())
+    if shape:
+        skw = dict(shape_kwargs or {})
+        views = render_shape(G, ws, torch.cat(cams, 0), res=images[1].shape[-1], **skw)['shade']
+        images += [torch.full_like(views[:1], float(skw.get('background', 1.0))), views]
     return image_grid_u8(torch.cat(images, 0), nrow=5, padding=2, pad_value=128)

@@ -1015,6 +1015,74 @@ int eg3d_mc_count(const eg3d_mc_params* p, void* stream);
 int eg3d_mc_emit(const eg3d_mc_params* p, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Shape views: first-hit iso-surface ray marcher over a regular fp32 grid (csrc/iso_render.hip).  No reference counterpart (the reference
+ *   only writes .mrc / .ply for an external viewer).
+ *   vol: contiguous fp32 [D0][D1][D2] as for marching cubes, D >= 2, D0*D1*D2 < 2^31.  Grid index i on grid axis a sits at world coordinate
+ *   origin[a] + i * spacing[a] of WORLD axis axes[a] (axes: a permutation of 0,1,2; spacing != 0, may be negative).  Inside iff v > level;
+ *   NaN never hits.
+ *
+ * eg3d_iso_bricks (one launch): bricks [B0][B1][B2], B_a = (D_a + 6) / 8; entry b = max of vol over i_a in [8 b_a - 1, 8 b_a + 9] clamped to
+ *   the grid (the brick's corner range dilated by one voxel), NaN ignored (-inf when all are NaN), + 0.0f.  Independent of the level.
+ *
+ * eg3d_iso_render (one launch, one wave per 8 x 8 pixel tile): exactly these fp32 operations in this order, no contraction (the library is
+ *   built with -ffp-contract=off); tests/support/iso_ref.py restates them in numpy and the outputs are compared bit for bit.
+ *   Ray of pixel (y, x) of camera c[25] (m = c[0..15] row-major cam2world, fx = c[16], sk = c[17], cx = c[18], fy = c[20], cy = c[21]):
+ *     xc = (x + 0.5) / res, yc = (y + 0.5) / res;  xl = (((xc - cx) + (cy * sk) / fy) - (sk * yc) / fy) / fx;  yl = (yc - cy) / fy
+ *     w_i = ((m_i0 * xl + m_i1 * yl) + m_i2) + m_i3;  o_i = m_i3;  e_i = w_i - o_i;  d_i = e_i / sqrt((e_0^2 + e_1^2) + e_2^2)
+ *   Index coordinates, per grid axis a (w = axes[a]):  oi_a = (o_w - origin_a) / spacing_a,  di_a = d_w / spacing_a,  h_a = D_a - 1.
+ *   Slabs, tn = 0, tf = +inf:  di_a == 0: the ray is empty unless 0 <= oi_a <= h_a;  else t0 = (0 - oi_a) / di_a, t1 = (h_a - oi_a) / di_a,
+ *     tn = max(tn, min(t0, t1)), tf = min(tf, max(t0, t1)), all by explicit comparisons.  Empty or not (tf >= tn): a miss.
+ *   dt = step * min |spacing_a|;  K = min(floor((tf - tn) / dt), 2^24);  t_k = tn + float(k) * dt, k = 0..K.
+ *   Field at t: p_a = clamp(oi_a + t * di_a, 0, h_a) (p > 0 ? p : 0, then p < h ? p : h);  i_a = min(int(floor(p_a)), D_a - 2);
+ *     f_a = p_a - float(i_a);  lerp(a, b, f) = a + f * (b - a) clamped to [min(a, b), max(a, b)] (so the interpolant never leaves the range of
+ *     its corners, in fp32 too);  lerps along axis 2, then axis 1, then axis 0.
+ *   Hit: the first k with field(t_k) > level.  k = 0: t = tn.  Otherwise ta = t_{k-1}, fa = field(ta), tb = t_k, fb = field(tb); `refine` times
+ *     tm = ta + (tb - ta) * 0.5, (fm > level ? (tb, fb) : (ta, fa)) = (tm, fm);  t = ta + (tb - ta) * ((level - fa) / (fb - fa)), replaced by tb
+ *     unless ta <= t <= tb.
+ *   Skipping (skip != 0): a sample whose cell (i_0 >> 3, i_1 >> 3, i_2 >> 3) has bricks[...] <= level is not evaluated; with
+ *     te = min over axes with di_a != 0 of ((di_a > 0 ? 8 b_a + 8 : 8 b_a) - oi_a) / di_a and q = floor((te - tn) / dt), the next k is
+ *     q > k + 1 ? min(q, K + 1) : k + 1.  Every skipped sample lies in the brick up to rounding (far less than the one-voxel dilation) and
+ *     the interpolant is bounded by its corners: no skipped sample exceeds the level, so every output is bit-identical with skip = 0.
+ *   Normal at the hit: per grid axis g_a = (field(p with p_a + 1 clamped) - field(p with p_a - 1 clamped)) / ((p_a^+ - p_a^-) * spacing_a);
+ *     n_w = -g_a for w = axes[a];  n / sqrt((n_0^2 + n_1^2) + n_2^2) when that length is > 0, else 0.
+ *   Outputs (each may be NULL): depth [F][res][res] = t (world units along the unit ray), 0 on a miss;  normal [F][res][res][3] world space, 0
+ *     on a miss;  mask uint8 [F][res][res];  hit_k int32 [F][res][res], -1 on a miss;  shade [F][3][res][res] in [-1, 1]:
+ *     EG3D_ISO_LAMBERT  v = ambient + (1 - ambient) * max(0, -((n_0 d_0 + n_1 d_1) + n_2 d_2)), the three channels = v * 2 - 1
+ *     EG3D_ISO_NORMAL   channel j = ((m_0j n_0 + m_1j n_1) + m_2j n_2) * 0.5 + 0.5, then * 2 - 1
+ *     a miss takes `background` (already in [-1, 1]).
+ *   No atomics, no floating-point sum whose order depends on the launch: bit-identical between runs and between the two builds.
+ *   Errors, before any launch: EG3D_ERR_INVALID (null vol / cams, no bricks with skip, D < 2, F or res < 1, axes no permutation, spacing 0 or
+ *   not finite, level / origin not finite, step outside [1/64, 64], refine outside 0..32, ambient outside [0, 1], unknown shade mode),
+ *   EG3D_ERR_TOO_LARGE (grid of 2^31 points or more), EG3D_ERR_UNSUPPORTED (res > 16384 or F > 65535).
+ */
+#define EG3D_ISO_LAMBERT 0
+#define EG3D_ISO_NORMAL 1
+typedef struct eg3d_iso_params {
+    const float* vol;                  /* [D0][D1][D2] */
+    float* bricks;                     /* [B0][B1][B2]: written by eg3d_iso_bricks, read by eg3d_iso_render when skip != 0 */
+    const float* cams;                 /* [F][25] */
+    float* depth;                      /* [F][res][res] or NULL */
+    float* normal;                     /* [F][res][res][3] or NULL */
+    uint8_t* mask;                     /* [F][res][res] or NULL */
+    int32_t* hit_k;                    /* [F][res][res] or NULL */
+    float* shade;                      /* [F][3][res][res] or NULL */
+    int32_t D0, D1, D2;
+    int32_t F, res;
+    int32_t axes[3];                   /* world axis of each grid axis */
+    float origin[3];                   /* per grid axis */
+    float spacing[3];                  /* per grid axis, signed */
+    float level;
+    float step;                        /* sample distance in units of min |spacing| */
+    int32_t refine;                    /* bisection halvings before the secant step */
+    int32_t skip;                      /* 0 = march every sample */
+    int32_t shade_mode;                /* EG3D_ISO_LAMBERT | EG3D_ISO_NORMAL */
+    float ambient;
+    float background;
+} eg3d_iso_params;
+int eg3d_iso_bricks(const eg3d_iso_params* p, void* stream);
+int eg3d_iso_render(const eg3d_iso_params* p, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * SSIM / MS-SSIM (reconstruction metrics) -- pytorch_msssim 1.0's ssim / ms_ssim with win=None, as the reference's evaluation calls it
  *   (training/coaches/single_id_coach.py:87-99; csrc/ssim.hip).  x, y: contiguous fp32 [N,C,H,W], any value range.
  *   Gaussian window win[k] = exp(-(k - win_size/2)^2 / (2 sigma^2)) / sum, applied separably (H then W) per channel, valid (no padding).

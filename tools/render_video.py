@@ -5,7 +5,8 @@ single_id_coach.py:61-62,84-85 calls it), frames encoded by the GPU JPEG encoder
 
 --weights: a generator archive (inv3d_amd.weights, tools/convert_eg3d_pickle.py); without it, the full-size synthetic generator
 (inv3d_amd.synthetic, seed --seed).  --ws: a [1, num_ws, w_dim] (or [num_ws, w_dim]) .npy latent, e.g. the coach's {image}_ws.npy.
---depth renders image_depth (grey frames) instead of the colour image."""
+--depth renders image_depth (grey frames) instead of the colour image.  --shape puts the shaded first-hit view of the density surface
+(--shape-level, --shape-grid, --shape-shade lambert | normal) beside every frame: twice the width, one density grid per video."""
 import argparse
 import os
 import sys
@@ -29,6 +30,10 @@ def main():
     ap.add_argument('--fps', type=int, default=60)
     ap.add_argument('--quality', type=int, default=90)
     ap.add_argument('--batch', type=int, default=16, help='frames per encoder call')
+    ap.add_argument('--shape', action='store_true', help='image | shaded density surface side by side (twice the width)')
+    ap.add_argument('--shape-level', type=float, default=10.0, help='density level of the surface')
+    ap.add_argument('--shape-grid', type=int, default=512, help='side of the density grid')
+    ap.add_argument('--shape-shade', default='lambert', choices=['lambert', 'normal'])
     a = ap.parse_args()
     from inv3d_amd import video as V
     dev = torch.device('cuda')
@@ -44,7 +49,7 @@ def main():
         ws = ws.unsqueeze(0)
     t0 = time.perf_counter()
     n = V.write_orbit_video(G, ws, a.out, num_frames=a.frames, image_mode='image_depth' if a.depth else 'image', fps=a.fps, quality=a.quality,
-                            batch=a.batch)
+                            batch=a.batch, shape=a.shape, shape_kwargs=dict(level=a.shape_level, grid_res=a.shape_grid, shade=a.shape_shade))
     dt = time.perf_counter() - t0
     print(f'{a.out}: {n} frames, {os.path.getsize(a.out)} bytes ({dt * 1e3:.1f} ms, {n / dt:.1f} frames/s)')
 

@@ -238,6 +238,20 @@ class IsoParams(C.Structure):
 ISO_LAMBERT, ISO_NORMAL = 0, 1
 ISO_BRICK = 8
 
+
+class MeshNormalsParams(C.Structure):
+    """eg3d_mesh_normals_params: unit normals of the density field at points (eg3d_mesh_normals)."""
+    _fields_ = [('vol', C.c_void_p), ('points', C.c_void_p), ('normals', C.c_void_p), ('V', C.c_int64), ('D0', C.c_int32), ('D1', C.c_int32),
+                ('D2', C.c_int32), ('axes', C.c_int32 * 3), ('origin', C.c_float * 3), ('spacing', C.c_float * 3)]
+
+
+class MeshBakeParams(C.Structure):
+    """eg3d_mesh_bake_params: vertex colours blended from rendered views (eg3d_mesh_bake)."""
+    _fields_ = [('points', C.c_void_p), ('normals', C.c_void_p), ('cams', C.c_void_p), ('images', C.c_void_p), ('depth', C.c_void_p),
+                ('mask', C.c_void_p), ('fallback', C.c_void_p), ('color', C.c_void_p), ('rgb', C.c_void_p), ('weight', C.c_void_p),
+                ('views', C.c_void_p), ('V', C.c_int64), ('F', C.c_int32), ('H', C.c_int32), ('R', C.c_int32), ('depth_tol', C.c_float),
+                ('cos_min', C.c_float), ('power', C.c_int32)]
+
 SSIM_MAX_LEVELS = 8
 
 
@@ -416,6 +430,8 @@ _SIGS = {
     'eg3d_mc_emit': (C.c_int, [C.POINTER(McParams), C.c_void_p]),
     'eg3d_iso_bricks': (C.c_int, [C.POINTER(IsoParams), C.c_void_p]),
     'eg3d_iso_render': (C.c_int, [C.POINTER(IsoParams), C.c_void_p]),
+    'eg3d_mesh_normals': (C.c_int, [C.POINTER(MeshNormalsParams), C.c_void_p]),
+    'eg3d_mesh_bake': (C.c_int, [C.POINTER(MeshBakeParams), C.c_void_p]),
     'eg3d_ssim_query_workspace': (C.c_int, [C.POINTER(SsimParams), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64),
                                             C.POINTER(C.c_int64)]),
     'eg3d_ssim_forward': (C.c_int, [C.POINTER(SsimParams), C.c_void_p]),

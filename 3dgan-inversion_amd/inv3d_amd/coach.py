@@ -31,7 +31,7 @@ import numpy as np
 import torch
 
 from . import dist as D
-from .inference import density_grid, estimate_w_stats, extract_mesh, write_mrc, write_ply
+from .inference import bake_cameras, color_mesh, density_grid, estimate_w_stats, extract_mesh, write_mrc, write_ply
 from .inversion import LatentProjector, PivotalTuner, psnr_01
 from .metrics import IDLoss, format_metrics_txt, reconstruction_metrics
 from .video import pivot_grid, write_orbit_video, write_png
@@ -62,7 +62,7 @@ class InversionCoach:
                  synth_kwargs: Optional[dict] = None, seed: int = 0, pose_net_factory: Optional[Callable] = None, pose_mode: str = 'quat',
                  w_avg_samples: int = 10000, w_stats: Optional[Tuple[torch.Tensor, float]] = None,
                  start_w_fn: Optional[Callable[[torch.Tensor], torch.Tensor]] = None, sr_fp16: bool = True, gen_mesh: bool = False,
-                 mesh_dir: Optional[str] = None, mesh_res: int = 512, mesh_level: float = 10.0, mesh_format: str = '.mrc',
+                 mesh_dir: Optional[str] = None, mesh_res: int = 512, mesh_level: float = 10.0, mesh_format: str = '.mrc', mesh_colors: bool = False,
                  do_evaluation: bool = False, eval_dir: Optional[str] = None, lpips_eval_net: Optional[Callable] = None,
                  id_net: Optional[Callable] = None, save_pivot: bool = False, pivot_dir: Optional[str] = None, shape_views: bool = False,
                  save_grid: bool = False, gen_video: bool = False, media_dir: Optional[str] = None, video_quality: int = 90):
@@ -74,7 +74,9 @@ class InversionCoach:
         tied to their standard deviation; `w_stats=(w_avg, w_std)` overrides the estimate, `w_avg_samples=0` starts at w = 0, std 1.
         `gen_mesh` (global_config.gen_mesh): after Phase B write the tuned generator's shape at the pivot latent to
         {mesh_dir}/{name}_pti{mesh_format} like create_geometry(shape_res=mesh_res, shape_format=mesh_format): '.mrc' = the raw density grid,
-        '.ply' = its marching-cubes mesh at `mesh_level` (the reference's level 10).
+        '.ply' = its marching-cubes mesh at `mesh_level` (the reference's level 10).  `mesh_colors` (no reference counterpart; '.ply' only):
+        the PLY also carries per-vertex normals and colours (inference.color_mesh with the pivot camera first among the bake views: the view
+        the photograph constrains); x y z and the faces are those of the plain file.
         `do_evaluation` (global_config.do_evaluation): after Phase B render G.synthesis(w_pivot[:, :14], cam[:, :25]) with the tuned generator and
         write metrics.reconstruction_metrics to {eval_dir}/{name}metrics.txt; `lpips_eval_net` (LPIPSAlex) and `id_net` (IDLoss) are built
         once per coach when None.  `save_pivot` writes {pivot_dir}/{name}_ws.npy and {name}_cam.npy; in the reference it only takes effect
@@ -96,6 +98,9 @@ class InversionCoach:
             raise ValueError(f"mesh_format must be '.mrc' or '.ply', got {mesh_format!r}")
         if gen_mesh and not mesh_dir:
             raise ValueError('gen_mesh needs a mesh_dir')
+        if mesh_colors and mesh_format != '.ply':
+            raise ValueError("mesh_colors needs mesh_format='.ply': an '.mrc' file is the density grid")
+        self.mesh_colors = bool(mesh_colors)
         self.gen_mesh, self.mesh_dir, self.mesh_res, self.mesh_level, self.mesh_format = gen_mesh, mesh_dir, int(mesh_res), float(mesh_level), mesh_format
         self.do_evaluation, self.eval_dir, self.save_pivot, self.pivot_dir = do_evaluation, eval_dir, save_pivot, pivot_dir
         self.lpips_eval_net, self.id_net = lpips_eval_net, id_net
@@ -193,7 +198,7 @@ class InversionCoach:
             mse = float(((img.clamp(-1, 1) - target) ** 2).mean() / 4.0)
         state = {k: v.detach().clone() for k, v in G.state_dict().items()} if self.keep else None
         G.requires_grad_(False)
-        mesh_path = self.write_mesh(name, w_pivot) if self.gen_mesh else None
+        mesh_path = self.write_mesh(name, w_pivot, cam_pivot) if self.gen_mesh else None
         metrics = self.evaluate(name, w_pivot, cam_pivot, target) if self.do_evaluation else None
         grid_tuned, video_tuned = self.write_media(name, w_pivot, cam_pivot, target, pivot=False)
         if self.save_pivot:
@@ -231,16 +236,31 @@ class InversionCoach:
             write_orbit_video(self.G, w_pivot, video_path, quality=self.video_quality, shape=self.shape_views, **self.synth_kwargs)
         return grid_path, video_path
 
-    def write_mesh(self, name: str, w_pivot: torch.Tensor) -> str:
-        """create_geometry(G, w_pivot, outdir=mesh_dir, fname=name + '_pti') with the generator as it is now (the tuned one)."""
+    def write_mesh(self, name: str, w_pivot: torch.Tensor, cam: Optional[torch.Tensor] = None) -> str:
+        """create_geometry(G, w_pivot, outdir=mesh_dir, fname=name + '_pti') with the generator as it is now (the tuned one); with
+        mesh_colors the PLY carries normals and colours baked from `cam` (the pivot camera) and inference.bake_cameras()."""
         os.makedirs(self.mesh_dir, exist_ok=True)
         path = os.path.join(self.mesh_dir, f'{name}_pti{self.mesh_format}')
         if self.mesh_format == '.ply':
-            verts, faces = extract_mesh(self.G, w_pivot, res=self.mesh_res, level=self.mesh_level)
-            write_ply(path, verts, faces)
+            if self.mesh_colors:
+                from .hipops import marching_cubes
+                grid = density_grid(self.G, w_pivot, res=self.mesh_res)                  # extract_mesh's two steps, keeping the grid for the bake
+                verts, faces = marching_cubes(grid, self.mesh_level)
+                att = color_mesh(self.G, w_pivot, verts, self.mesh_res, level=self.mesh_level, grid=grid, cameras=self.mesh_cameras(cam),
+                                 **self.synth_kwargs)
+                write_ply(path, verts, faces, normals=att['normals'], colors=att['colors'])
+            else:
+                verts, faces = extract_mesh(self.G, w_pivot, res=self.mesh_res, level=self.mesh_level)
+                write_ply(path, verts, faces)
         else:
             write_mrc(path, density_grid(self.G, w_pivot, res=self.mesh_res))
         return path
+
+    @staticmethod
+    def mesh_cameras(cam: Optional[torch.Tensor]) -> torch.Tensor:
+        """The bake views of a coloured mesh: the pivot camera (when there is one) in front of inference.bake_cameras()."""
+        views = bake_cameras()
+        return views if cam is None else torch.cat([cam.detach()[:1, :25].float().cpu(), views])
 
     def run(self, images: Sequence[Tuple[str, torch.Tensor, Optional[torch.Tensor]]]) -> Tuple[List[InversionResult], Dict[str, float]]:
         """Invert this rank's shard of `images` = [(name, target [1,3,H,W] in [-1,1], cam [1,25] | None), ...] (every rank passes the

@@ -1879,6 +1879,79 @@ def iso_render(vol: torch.Tensor, cams: torch.Tensor, res: int, level: float, or
     return out
 
 
+def _mesh_rows(t: torch.Tensor, what: str, dev=None, rows=None) -> torch.Tensor:
+    L.require_cuda(t)
+    if t.dim() != 2 or t.shape[1] != 3 or t.dtype != torch.float32 or not t.is_contiguous() or (rows is not None and t.shape[0] != rows):
+        raise L.Eg3dHipError(f'{what} must be contiguous fp32 [{"V" if rows is None else rows}, 3], got {tuple(t.shape)} {t.dtype}')
+    if dev is not None and t.device != dev:
+        raise L.Eg3dHipError(f'{what} is on {t.device}, expected {dev}')
+    return t
+
+
+def mesh_normals(vol: torch.Tensor, points: torch.Tensor, origin, spacing, axes=(0, 1, 2)) -> torch.Tensor:
+    """fp32 [V,3]: the unit normal of the trilinear field of the fp32 grid vol [D0,D1,D2] at the world points [V,3], toward lower values (out of
+    the dense region): clamped +-1 voxel differences of iso_render's field, its 'normal at the hit' at arbitrary points (eg3d_mesh_normals;
+    include/eg3d_hip.h "Mesh attributes").  The frame (origin, spacing, axes) is iso_render's.  0 where the gradient vanishes or is not finite
+    and for a NaN point.  One launch, no host synchronise."""
+    L.require_cuda(vol)
+    if vol.dim() != 3 or vol.dtype != torch.float32:
+        raise L.Eg3dHipError(f'mesh_normals: a 3-D fp32 grid, got {tuple(vol.shape)} {vol.dtype}')
+    vol = vol.contiguous()
+    points = _mesh_rows(points, 'mesh_normals: points', vol.device)
+    out = torch.empty_like(points)
+    p = L.MeshNormalsParams(vol=vol.data_ptr(), points=points.data_ptr(), normals=out.data_ptr(), V=points.shape[0], D0=vol.shape[0], D1=vol.shape[1],
+                            D2=vol.shape[2])
+    p.axes[:] = [int(v) for v in axes]
+    p.origin[:] = [float(v) for v in origin]
+    p.spacing[:] = [float(v) for v in spacing]
+    L.check(L.lib().eg3d_mesh_normals(C.byref(p), L.stream_ptr()), 'mesh_normals')
+    return out
+
+
+def mesh_bake(points: torch.Tensor, normals: torch.Tensor, images: torch.Tensor, depth: torch.Tensor, mask: torch.Tensor, cams: torch.Tensor,
+              fallback: Optional[torch.Tensor] = None, depth_tol: float = 0.0, cos_min: float = 0.1, power: int = 2) -> dict:
+    """Vertex colours from rendered views (eg3d_mesh_bake; specified operation by operation in include/eg3d_hip.h "Mesh attributes").
+    points, normals fp32 [V,3] in world coordinates; images fp32 [F,3,H,H] in [-1,1], the renders of cams [F,25]; depth fp32 [F,R,R] and mask
+    uint8 [F,R,R] as iso_render gives them for the same cameras.  A vertex takes colour from a view when it projects inside the frame, lies no
+    further than depth + depth_tol (world units) behind the first hit of one of the four depth pixels around it, and faces the camera with
+    cosine c > cos_min; the views' bilinear samples are blended with weights c ** power (power 1..8).  A vertex no view sees takes
+    `fallback` [V,3] (0 without one).  Returns a dict:
+      color  fp32 [V,3]   in [-1,1]
+      rgb    uint8 [V,3]  color * 127.5 + 128, clamped and truncated as image_grid_u8 does
+      weight fp32 [V]     the sum of the weights
+      views  uint8 [V]    how many views contributed
+    One launch, no host synchronise."""
+    points = _mesh_rows(points, 'mesh_bake: points')
+    dev, V = points.device, points.shape[0]
+    normals = _mesh_rows(normals, 'mesh_bake: normals', dev, V)
+    L.require_cuda(images, depth, mask, cams)
+    if cams.dim() != 2 or cams.shape[1] != 25 or cams.shape[0] < 1:
+        raise L.Eg3dHipError(f'mesh_bake: cameras [F >= 1, 25], got {tuple(cams.shape)}')
+    F = cams.shape[0]
+    if images.dim() != 4 or images.shape[0] != F or images.shape[1] != 3 or images.shape[2] != images.shape[3] or images.shape[2] < 1 \
+            or images.dtype != torch.float32 or not images.is_contiguous():
+        raise L.Eg3dHipError(f'mesh_bake: images must be contiguous fp32 [{F}, 3, H, H], got {tuple(images.shape)} {images.dtype}')
+    if depth.dim() != 3 or depth.shape[0] != F or depth.shape[1] != depth.shape[2] or depth.shape[1] < 1 or depth.dtype != torch.float32 \
+            or not depth.is_contiguous():
+        raise L.Eg3dHipError(f'mesh_bake: depth must be contiguous fp32 [{F}, R, R], got {tuple(depth.shape)} {depth.dtype}')
+    if tuple(mask.shape) != tuple(depth.shape) or mask.dtype != torch.uint8 or not mask.is_contiguous():
+        raise L.Eg3dHipError(f'mesh_bake: mask must be contiguous uint8 {tuple(depth.shape)}, got {tuple(mask.shape)} {mask.dtype}')
+    if fallback is not None:
+        fallback = _mesh_rows(fallback, 'mesh_bake: fallback', dev, V)
+    for name, t in (('images', images), ('depth', depth), ('mask', mask), ('cams', cams)):
+        if t.device != dev:
+            raise L.Eg3dHipError(f'mesh_bake: {name} is on {t.device}, expected {dev}')
+    cams = cams.to(dtype=torch.float32).contiguous()
+    out = dict(color=torch.empty((V, 3), dtype=torch.float32, device=dev), rgb=torch.empty((V, 3), dtype=torch.uint8, device=dev),
+               weight=torch.empty((V,), dtype=torch.float32, device=dev), views=torch.empty((V,), dtype=torch.uint8, device=dev))
+    p = L.MeshBakeParams(points=points.data_ptr(), normals=normals.data_ptr(), cams=cams.data_ptr(), images=images.data_ptr(), depth=depth.data_ptr(),
+                         mask=mask.data_ptr(), fallback=None if fallback is None else fallback.data_ptr(), color=out['color'].data_ptr(),
+                         rgb=out['rgb'].data_ptr(), weight=out['weight'].data_ptr(), views=out['views'].data_ptr(), V=V, F=F, H=images.shape[2],
+                         R=depth.shape[1], depth_tol=float(depth_tol), cos_min=float(cos_min), power=int(power))
+    L.check(L.lib().eg3d_mesh_bake(C.byref(p), L.stream_ptr()), 'mesh_bake')
+    return out
+
+
 def _ssim_params(x, y, mode, weights, nonnegative, size_average, win_size, win_sigma, C1, C2):
     N, Ch, Hh, Ww = x.shape
     p = L.SsimParams(x=x.data_ptr(), y=y.data_ptr(), N=N, C=Ch, H=Hh, W=Ww, mode=mode, levels=len(weights), nonnegative=int(bool(nonnegative)),

@@ -11,6 +11,9 @@ G.mapping / ImportanceRenderer.run_model on the gfx950 kernels.
   write_mrc                    <- create_geometry's '.mrc' branch (single_id_coach.py:158-160, mrcfile.new_mmap mode 2), no mrcfile
   grid_frame, render_shape,    no reference counterpart: shaded first-hit views of the density surface from the generator's own cameras
   render_shape_orbit              (hipops.iso_render over density_grid's grid), to look at the recovered shape without an external viewer
+  mesh_to_world, bake_cameras, no reference counterpart (its meshes are bare x y z): per-vertex normals of the density field and vertex colours
+  color_mesh, normals_to_mesh     blended from rendered views that see the vertex (hipops.mesh_normals / mesh_bake), for write_ply's optional
+                                  nx ny nz / red green blue properties
 
 Differences from the reference that do not change results: the tri-planes of a fixed latent are synthesised once per orbit / per grid
 instead of once per frame / per chunk (the reference re-runs the backbone every time), and grid coordinates are generated per chunk on
@@ -129,13 +132,19 @@ def density_grid(G, ws: torch.Tensor, res: int = 512, max_batch: int = 1 << 22, 
 
 
 @torch.no_grad()
-def extract_mesh(G, ws: torch.Tensor, res: int = 512, level: float = 10.0, max_batch: int = 1 << 22, **synthesis_kwargs):
+def extract_mesh(G, ws: torch.Tensor, res: int = 512, level: float = 10.0, max_batch: int = 1 << 22, attributes: bool = False, **synthesis_kwargs):
     """(verts fp32 [V,3], faces int32 [F,3]) on the device: density_grid, then marching cubes at `level` in the coordinates of the reference's
     PLY (marching_cubes(np.transpose(grid, (2,1,0)), level, spacing=[1]*3), origin [0,0,0]: voxel units).  Faces are wound so that their
-    right-hand normals point out of the dense region.  Triangles may differ from skimage's Lewiner method in ambiguous cubes; vertices do not."""
+    right-hand normals point out of the dense region.  Triangles may differ from skimage's Lewiner method in ambiguous cubes; vertices do not.
+    attributes=True: (verts, faces, normals fp32 [V,3], colors uint8 [V,3]) with color_mesh's defaults on the same grid; verts and faces are
+    those of the plain call."""
     from .hipops import marching_cubes
     grid = density_grid(G, ws, res=res, max_batch=max_batch, **synthesis_kwargs)
-    return marching_cubes(grid, level)
+    verts, faces = marching_cubes(grid, level)
+    if not attributes:
+        return verts, faces
+    att = color_mesh(G, ws, verts, res, level=level, grid=grid, **synthesis_kwargs)
+    return verts, faces, att['normals'], att['colors']
 
 
 def grid_frame(G, res: int):
@@ -182,25 +191,150 @@ def render_shape_orbit(G, ws: torch.Tensor, num_frames: int = 240, cameras: Opti
         yield out['shade'][0]
 
 
+def _mesh_axes(G, res: int):
+    """Per vertex column k of marching_cubes' frame (grid point (i0, i1, i2) -> vertex (i2, i1, i0)): (world axis, origin, spacing), and the
+    determinant's sign of the voxel -> world map (a signed permutation: -1 means it mirrors)."""
+    origin, spacing, axes = grid_frame(G, res)
+    cols = [(axes[2 - k], origin[2 - k], spacing[2 - k]) for k in range(3)]
+    perm = [c[0] for c in cols]
+    sign = 1 if perm in ([0, 1, 2], [1, 2, 0], [2, 0, 1]) else -1
+    for c in cols:
+        sign = -sign if c[2] < 0 else sign
+    return cols, sign
+
+
+def mesh_to_world(G, verts: torch.Tensor, faces: Optional[torch.Tensor], res: int):
+    """(world fp32 [V,3], faces): the vertices marching_cubes / extract_mesh return (voxel units, the (i2, i1, i0) frame of the reference's PLY)
+    in world coordinates through grid_frame(G, res): column k is grid axis 2 - k, so world[axes[2-k]] = verts[k] * spacing[2-k] + origin[2-k]
+    (a product, then a sum, in fp32).  That is a reversal of the axes plus the flipped grid axis 0; where the map mirrors, the faces come back
+    re-wound (columns 1 and 2 swapped) so that right-hand face normals still point out of the dense region.  faces may be None."""
+    cols, sign = _mesh_axes(G, res)
+    world = torch.empty_like(verts, dtype=torch.float32)
+    for k, (w, o, s) in enumerate(cols):
+        world[:, w] = verts[:, k].float() * s + o
+    if faces is not None and sign < 0:
+        faces = faces[:, [0, 2, 1]].contiguous()
+    return world, faces
+
+
+def normals_to_mesh(G, normals: torch.Tensor, res: int) -> torch.Tensor:
+    """World-space normals [V,3] in the frame of the mesh vertices (what a PLY carries beside x y z): the inverse of mesh_to_world applied to
+    directions.  The grid is cubic with one |spacing|, so it is a permutation with sign changes, exact in fp32."""
+    cols, _ = _mesh_axes(G, res)
+    return torch.stack([-normals[:, w] if s < 0 else normals[:, w] for (w, _, s) in cols], 1).contiguous()
+
+
+def bake_cameras(n_yaw: int = 5, n_pitch: int = 3, yaw_range: float = 0.6, pitch_range: float = 0.25, radius: float = 2.7, focal: float = 4.2647,
+                 device='cpu') -> torch.Tensor:
+    """[n_yaw * n_pitch, 25] lookat_pose views around the frontal camera (yaw pi/2, pitch pi/2) for color_mesh: yaw offsets evenly over
+    [-yaw_range, yaw_range], pitch offsets over [-pitch_range, pitch_range] (a single value is offset 0), pitch-major.  Callers may prepend the
+    inversion's own camera, the view the photograph constrains best."""
+    K = torch.tensor([focal, 0, 0.5, 0, focal, 0.5, 0, 0, 1.])
+    span = lambda n, r: [0.0] if n <= 1 else [-r + 2 * r * i / (n - 1) for i in range(n)]     # noqa: E731
+    cams = [torch.cat([lookat_pose(math.pi / 2 + dy, math.pi / 2 + dp, (0., 0., 0.), radius).reshape(16), K])
+            for dp in span(int(n_pitch), pitch_range) for dy in span(int(n_yaw), yaw_range)]
+    return torch.stack(cams).to(device)
+
+
+def _to_u8(color: torch.Tensor) -> torch.Tensor:
+    """x * 127.5 + 128 clamped to [0, 255] and truncated: image_grid_u8's conversion."""
+    return (color * 127.5 + 128).clamp(0, 255).to(torch.uint8)
+
+
+@torch.no_grad()
+def color_mesh(G, ws: torch.Tensor, verts: torch.Tensor, res: int, level: float = 10.0, grid: Optional[torch.Tensor] = None,
+               cameras: Optional[torch.Tensor] = None, source: str = 'views', depth_tol: Optional[float] = None, cos_min: float = 0.1,
+               power: int = 2, **synthesis_kwargs) -> dict:
+    """Normals and colours for the vertices `verts` [V,3] of marching_cubes / extract_mesh at grid resolution `res` and `level`.  Returns a dict:
+      world   fp32 [V,3]   the vertices in world coordinates (mesh_to_world)
+      normals fp32 [V,3]   unit normals of the density field (hipops.mesh_normals on density_grid's grid, built here unless `grid` is passed)
+                           in the frame of `verts` (normals_to_mesh: what a PLY carries); 'world_normals' has them in world coordinates
+      color   fp32 [V,3]   in [-1,1];  colors uint8 [V,3] = color * 127.5 + 128 clamped and truncated
+      views   uint8 [V]    how many views coloured the vertex (0: it carries the fallback)
+    source='views': every camera of `cameras` [F,25] (default bake_cameras()) renders one G.synthesis image (noise_mode='const', one backbone
+    pass) and one first-hit depth map of the same surface from the same rays (hipops.iso_render at the image resolution, one brick pass);
+    hipops.mesh_bake blends the views' samples where the vertex is visible and faces the camera (cos_min, power).  A vertex no view sees takes the
+    fallback: the generator's own radiance at the vertex, the first three colour channels of G.renderer.run_model on the planes of ws, * 2 - 1
+    as the renderer forms image_raw.  source='radiance': the fallback is the colour and nothing is rendered.
+    depth_tol=None means two voxels of the grid in world units: a default chosen from geometry (at 512 pixels over the frame a depth pixel is
+    about as wide as a voxel of a 512^3 grid, and the mesh vertex and the marcher's hit differ by interpolation, less than a voxel), not
+    tuned on real heads.  Further keywords go to G.synthesis."""
+    from .hipops import iso_bricks, iso_render, mesh_bake, mesh_normals
+    if source not in ('views', 'radiance'):
+        raise ValueError(f"color_mesh: source 'views' or 'radiance', got {source!r}")
+    res = int(res)
+    if grid is None:
+        grid = density_grid(G, ws, res=res)
+    if tuple(grid.shape) != (res, res, res):
+        raise ValueError(f'color_mesh: a {res}^3 density grid, got {tuple(grid.shape)}')
+    dev = grid.device
+    verts = verts.to(dev)
+    origin, spacing, axes = grid_frame(G, res)
+    world, _ = mesh_to_world(G, verts, None, res)
+    V = world.shape[0]
+    world_normals = mesh_normals(grid, world, origin, spacing, axes)
+    out = dict(world=world, world_normals=world_normals, normals=normals_to_mesh(G, world_normals, res))
+    fallback = torch.empty((V, 3), dtype=torch.float32, device=dev)
+    if V:
+        bkw = {k: v for k, v in synthesis_kwargs.items() if k not in ('force_fp32', 'render_uniforms', 'sr_fp16', 'neural_rendering_resolution')}
+        planes = G.backbone.synthesis(ws[:1], noise_mode='const', **bkw)
+        planes = planes.view(1, 3, -1, planes.shape[-2], planes.shape[-1])
+        for head in range(0, V, 1 << 22):
+            rgb = G.renderer.run_model(planes, G.decoder, world[head:head + (1 << 22)].unsqueeze(0), None, G.rendering_kwargs)['rgb']
+            fallback[head:head + (1 << 22)] = rgb.reshape(-1, rgb.shape[-1])[:, :3].float() * 2 - 1
+    if source == 'radiance' or V == 0:
+        out.update(color=fallback, colors=_to_u8(fallback), views=torch.zeros(V, dtype=torch.uint8, device=dev))
+        return out
+    cams = (bake_cameras(device=dev) if cameras is None else cameras.to(dev)).float().contiguous()
+    kw = dict(noise_mode='const', **synthesis_kwargs)
+    images = None
+    for i in range(cams.shape[0]):
+        img = G.synthesis(ws[:1], cams[i:i + 1], cache_backbone=(i == 0), use_cached_backbone=(i > 0), **kw)['image']
+        if images is None:
+            images = torch.empty((cams.shape[0], *img.shape[1:]), dtype=torch.float32, device=dev)
+        images[i] = img[0]
+    iso = iso_render(grid, cams, images.shape[-1], level, origin, spacing, axes=axes, bricks=iso_bricks(grid))
+    tol = 2.0 * abs(spacing[0]) if depth_tol is None else float(depth_tol)
+    baked = mesh_bake(world, world_normals, images, iso['depth'], iso['mask'], cams, fallback=fallback, depth_tol=tol, cos_min=cos_min, power=power)
+    out.update(color=baked['color'], colors=baked['rgb'], views=baked['views'])
+    return out
+
+
 def _host(a, dtype):
     if isinstance(a, torch.Tensor):
         a = a.detach().cpu().numpy()
     return np.ascontiguousarray(a, dtype=dtype)
 
 
-def write_ply(path: str, verts, faces) -> None:
+def write_ply(path: str, verts, faces, normals=None, colors=None) -> None:
     """Binary little-endian PLY with the header plyfile writes for the reference's dtypes (shape_utils.py:84-97: vertex x, y, z 'f4'; face
-    vertex_indices 'i4' x 3 as a list with a uchar count)."""
+    vertex_indices 'i4' x 3 as a list with a uchar count).  normals fp32 [V,3] add 'property float nx / ny / nz', colors uint8 [V,3] add
+    'property uchar red / green / blue', in that order after z (the names MeshLab and Blender read); with neither, the file is the reference's."""
     v = _host(verts, np.float32).reshape(-1, 3)
     f = _host(faces, np.int32).reshape(-1, 3)
-    header = '\n'.join(['ply', 'format binary_little_endian 1.0', f'element vertex {len(v)}', 'property float x', 'property float y',
-                        'property float z', f'element face {len(f)}', 'property list uchar int vertex_indices', 'end_header']) + '\n'
+    props, fields = ['property float x', 'property float y', 'property float z'], [('p', '<f4', (3,))]
+    if normals is not None:
+        props += ['property float nx', 'property float ny', 'property float nz']
+        fields.append(('n', '<f4', (3,)))
+    if colors is not None:
+        props += ['property uchar red', 'property uchar green', 'property uchar blue']
+        fields.append(('c', 'u1', (3,)))
+    vrec = np.empty(len(v), dtype=np.dtype(fields))
+    vrec['p'] = v
+    for key, arr, dt in (('n', normals, np.float32), ('c', colors, np.uint8)):
+        if arr is not None:
+            a = _host(arr, dt).reshape(-1, 3)
+            if len(a) != len(v):
+                raise ValueError(f'write_ply: {len(a)} attribute rows for {len(v)} vertices')
+            vrec[key] = a
+    header = '\n'.join(['ply', 'format binary_little_endian 1.0', f'element vertex {len(v)}', *props,
+                        f'element face {len(f)}', 'property list uchar int vertex_indices', 'end_header']) + '\n'
     rec = np.empty(len(f), dtype=np.dtype([('n', 'u1'), ('i', '<i4', (3,))]))
     rec['n'] = 3
     rec['i'] = f
     with open(path, 'wb') as fh:
         fh.write(header.encode('ascii'))
-        fh.write(np.ascontiguousarray(v, dtype='<f4').data)
+        fh.write(vrec.tobytes())
         fh.write(rec.tobytes())
 
 

@@ -1083,6 +1083,72 @@ int eg3d_iso_bricks(const eg3d_iso_params* p, void* stream);
 int eg3d_iso_render(const eg3d_iso_params* p, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Mesh attributes: per-vertex normals of the density field and view-baked vertex colours (csrc/mesh_bake.hip).  No reference counterpart
+ *   (the reference's meshes carry x y z and faces only).  One thread per vertex, no atomics, the views walked in index order: bit-identical
+ *   between runs and between the two builds.  Exactly these fp32 operations in this order, no contraction; tests/support/mesh_ref.py restates
+ *   them in numpy and the outputs are compared bit for bit.
+ *
+ * eg3d_mesh_normals (one launch): the unit normal of the trilinear field of vol at points [V][3] (world coordinates).  vol, origin, spacing and
+ *   axes as in eg3d_iso_params.  Per grid axis a: r_a = (x_{axes[a]} - origin_a) / spacing_a, h_a = D_a - 1.  If any r_a is NaN the normal is 0.
+ *   Otherwise p_a = clamp(r_a, 0, h_a), and with field(), clamp and lerp as "Shape views" defines them, per grid axis
+ *     g_a = (field(p with p_a + 1 clamped) - field(p with p_a - 1 clamped)) / ((p_a^+ - p_a^-) * spacing_a);  n_w = -g_a for w = axes[a];
+ *     len = sqrt((n_0^2 + n_1^2) + n_2^2);  normal = n / len when 0 < len < inf, else 0 (a NaN or infinite component makes len NaN or inf).
+ *   The normal points toward lower values: out of the dense region.
+ *   Errors, before any launch: EG3D_ERR_INVALID (null vol, null points / normals with V > 0, V < 0, D < 2, axes no permutation, spacing 0 or not
+ *   finite, origin not finite), EG3D_ERR_TOO_LARGE (grid of 2^31 points or more, V >= 2^31).  V = 0: ok, no launch.
+ *
+ * eg3d_mesh_bake (one launch): the colour of vertex p (normal n) blended from F rendered views.  images fp32 [F][3][H][H] in [-1, 1]; depth
+ *   fp32 [F][R][R] and mask uint8 [F][R][R] as eg3d_iso_render writes them for the same cameras (R need not equal H).
+ *   acc = 0, wsum = 0, views = 0; for f = 0 .. F-1, camera c[25] named as in "Shape views" (m row-major cam2world, o_i = m_i3):
+ *   1. q_i = p_i - o_i;  t = sqrt((q_0^2 + q_1^2) + q_2^2);  c_j = (m_0j q_0 + m_1j q_1) + m_2j q_2, j = 0, 1, 2.
+ *      Skip the view unless t > 0 and c_2 > 0 (the camera looks down +z of its own frame).
+ *   2. xl = c_0 / c_2, yl = c_1 / c_2;  yc = yl * fy + cy;  xc = ((xl * fx + cx) - (cy * sk) / fy) + (sk * yc) / fy  (the inverse of the ray
+ *      lift).  At a resolution r: px = xc * float(r) - 0.5, py = yc * float(r) - 0.5, formed for r = H and for r = R.
+ *      Skip unless 0 <= px <= r - 1 and 0 <= py <= r - 1 at both resolutions (explicit comparisons: NaN skips).
+ *   3. Visibility: x0 = int(floor(px_R)), x1 = min(x0 + 1, R - 1), y0, y1 likewise.  Skip unless one of the pixels (y0,x0), (y0,x1), (y1,x0),
+ *      (y1,x1) of view f has mask != 0 and t <= depth + depth_tol.
+ *   4. c = -((n_0 q_0 + n_1 q_1) + n_2 q_2) / t.  Skip unless c > cos_min.  w = c, then w = w * c, power - 1 times.
+ *   5. H >= 2: bx = min(int(floor(px_H)), H - 2), by likewise, tx = px_H - float(bx), ty = py_H - float(by), lerp(a, b, f) = a + f * (b - a)
+ *      (not clamped);  colour_j = lerp(lerp(I[by][bx], I[by][bx+1], tx), lerp(I[by+1][bx], I[by+1][bx+1], tx), ty) of channel j.  H = 1: the
+ *      single texel.  acc_j = acc_j + w * colour_j;  wsum = wsum + w;  views = min(views + 1, 255).
+ *   Outputs (each may be NULL): color fp32 [V][3] = acc_j / wsum when wsum > 0, else fallback [V][3] (0 without one);  rgb uint8 [V][3] =
+ *     uint8(int(min(max(color * 127.5 + 128, 0), 255))) as eg3d_image_grid_u8;  weight fp32 [V] = wsum;  views uint8 [V].
+ *   Errors, before any launch: EG3D_ERR_INVALID (null cams / images / depth / mask, null points / normals with V > 0, V < 0, F, H or R < 1,
+ *   depth_tol negative or not finite, cos_min outside [0, 1), power outside 1..8), EG3D_ERR_UNSUPPORTED (F > 255, H or R > 16384),
+ *   EG3D_ERR_TOO_LARGE (V >= 2^31).  V = 0: ok, no launch.
+ */
+typedef struct eg3d_mesh_normals_params {
+    const float* vol;                  /* [D0][D1][D2] */
+    const float* points;               /* [V][3] world */
+    float* normals;                    /* [V][3] world */
+    int64_t V;
+    int32_t D0, D1, D2;
+    int32_t axes[3];                   /* world axis of each grid axis */
+    float origin[3];                   /* per grid axis */
+    float spacing[3];                  /* per grid axis, signed */
+} eg3d_mesh_normals_params;
+typedef struct eg3d_mesh_bake_params {
+    const float* points;               /* [V][3] world */
+    const float* normals;              /* [V][3] world */
+    const float* cams;                 /* [F][25] */
+    const float* images;               /* [F][3][H][H] */
+    const float* depth;                /* [F][R][R] */
+    const uint8_t* mask;               /* [F][R][R] */
+    const float* fallback;             /* [V][3] or NULL */
+    float* color;                      /* [V][3] or NULL */
+    uint8_t* rgb;                      /* [V][3] or NULL */
+    float* weight;                     /* [V] or NULL */
+    uint8_t* views;                    /* [V] or NULL */
+    int64_t V;
+    int32_t F, H, R;
+    float depth_tol;                   /* world units, >= 0 */
+    float cos_min;                     /* in [0, 1) */
+    int32_t power;                     /* 1..8 */
+} eg3d_mesh_bake_params;
+int eg3d_mesh_normals(const eg3d_mesh_normals_params* p, void* stream);
+int eg3d_mesh_bake(const eg3d_mesh_bake_params* p, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * SSIM / MS-SSIM (reconstruction metrics) -- pytorch_msssim 1.0's ssim / ms_ssim with win=None, as the reference's evaluation calls it
  *   (training/coaches/single_id_coach.py:87-99; csrc/ssim.hip).  x, y: contiguous fp32 [N,C,H,W], any value range.
  *   Gaussian window win[k] = exp(-(k - win_size/2)^2 / (2 sigma^2)) / sum, applied separably (H then W) per channel, valid (no padding).

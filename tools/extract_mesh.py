@@ -2,10 +2,13 @@
 convert_sdf_samples_to_ply, shape_utils.py:40-100), on the GPU kernels of this package.
 
   python tools/extract_mesh.py --ws pivot_ws.npy --out face.ply [--weights G.safetensors] [--res 512] [--level 10] [--mrc face.mrc]
+                               [--colors [--views N_YAW N_PITCH] [--radiance]]
 
 --weights: a generator archive (inv3d_amd.weights, tools/convert_eg3d_pickle.py); without it, the full-size synthetic generator
 (inv3d_amd.synthetic, seed --seed).  --ws: a [1, num_ws, w_dim] (or [num_ws, w_dim]) .npy latent, e.g. the reference's {image}_ws.npy.
---mrc additionally writes the density grid as create_geometry's '.mrc' branch does."""
+--mrc additionally writes the density grid as create_geometry's '.mrc' branch does.
+--colors adds per-vertex normals (nx ny nz) and colours (red green blue) to the PLY (inference.color_mesh; no reference counterpart): colours
+blended from N_YAW x N_PITCH rendered views around the frontal camera (default 5 x 3), or with --radiance the generator's own radiance at the vertices, without rendering."""
 import argparse
 import os
 import sys
@@ -27,6 +30,9 @@ def main():
     ap.add_argument('--res', type=int, default=512)
     ap.add_argument('--level', type=float, default=10.0)
     ap.add_argument('--mrc', default=None, help='also write the density grid to this .mrc')
+    ap.add_argument('--colors', action='store_true', help='write per-vertex normals and colours too')
+    ap.add_argument('--views', type=int, nargs=2, default=(5, 3), metavar=('N_YAW', 'N_PITCH'), help='bake views around the frontal camera')
+    ap.add_argument('--radiance', action='store_true', help="colour from the generator's radiance at the vertices instead of rendered views")
     a = ap.parse_args()
     from inv3d_amd import inference as INF
     dev = torch.device('cuda')
@@ -46,10 +52,21 @@ def main():
     verts, faces = marching_cubes(grid, a.level)
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
-    INF.write_ply(a.out, verts, faces)
+    note = ''
+    if a.colors:
+        t1 = time.perf_counter()
+        cams = INF.bake_cameras(a.views[0], a.views[1], device=dev)
+        att = INF.color_mesh(G, ws, verts, a.res, level=a.level, grid=grid, cameras=cams, source='radiance' if a.radiance else 'views')
+        torch.cuda.synchronize()
+        INF.write_ply(a.out, verts, faces, normals=att['normals'], colors=att['colors'])
+        seen = int((att['views'] > 0).sum())
+        note = (f'; normals + colours {(time.perf_counter() - t1) * 1e3:.1f} ms, '
+                + ('radiance' if a.radiance else f'{seen} of {verts.shape[0]} vertices coloured from {cams.shape[0]} views'))
+    else:
+        INF.write_ply(a.out, verts, faces)
     if a.mrc:
         INF.write_mrc(a.mrc, grid)
-    print(f'{a.out}: {verts.shape[0]} vertices, {faces.shape[0]} faces ({a.res}^3 grid, level {a.level}; grid + march {dt * 1e3:.1f} ms)')
+    print(f'{a.out}: {verts.shape[0]} vertices, {faces.shape[0]} faces ({a.res}^3 grid, level {a.level}; grid + march {dt * 1e3:.1f} ms{note})')
 
 
 if __name__ == '__main__':

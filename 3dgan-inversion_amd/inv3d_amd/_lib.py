@@ -252,6 +252,17 @@ class MeshBakeParams(C.Structure):
                 ('views', C.c_void_p), ('V', C.c_int64), ('F', C.c_int32), ('H', C.c_int32), ('R', C.c_int32), ('depth_tol', C.c_float),
                 ('cos_min', C.c_float), ('power', C.c_int32)]
 
+
+class CcParams(C.Structure):
+    """eg3d_cc_params: connected components of {vol > level} (eg3d_cc_query_workspace / eg3d_cc_label / eg3d_cc_finish / eg3d_cc_keep)."""
+    _fields_ = [('vol', C.c_void_p), ('labels', C.c_void_p), ('D0', C.c_int32), ('D1', C.c_int32), ('D2', C.c_int32), ('level', C.c_float),
+                ('connectivity', C.c_int32), ('count', C.c_int32), ('workspace', C.c_void_p), ('workspace_bytes', C.c_int64),
+                ('totals', C.c_void_p), ('sizes', C.c_void_p), ('roots', C.c_void_p), ('keep', C.c_void_p), ('out', C.c_void_p),
+                ('fill', C.c_float)]
+
+
+CC_TILE = (8, 8, 64)             # EG3D_CC_TILE0 / 1 / 2: voxels per axis one workgroup labels in LDS
+
 SSIM_MAX_LEVELS = 8
 
 
@@ -432,6 +443,10 @@ _SIGS = {
     'eg3d_iso_render': (C.c_int, [C.POINTER(IsoParams), C.c_void_p]),
     'eg3d_mesh_normals': (C.c_int, [C.POINTER(MeshNormalsParams), C.c_void_p]),
     'eg3d_mesh_bake': (C.c_int, [C.POINTER(MeshBakeParams), C.c_void_p]),
+    'eg3d_cc_query_workspace': (C.c_int, [C.POINTER(CcParams), C.POINTER(C.c_int64)]),
+    'eg3d_cc_label': (C.c_int, [C.POINTER(CcParams), C.c_void_p]),
+    'eg3d_cc_finish': (C.c_int, [C.POINTER(CcParams), C.c_void_p]),
+    'eg3d_cc_keep': (C.c_int, [C.POINTER(CcParams), C.c_void_p]),
     'eg3d_ssim_query_workspace': (C.c_int, [C.POINTER(SsimParams), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64),
                                             C.POINTER(C.c_int64)]),
     'eg3d_ssim_forward': (C.c_int, [C.POINTER(SsimParams), C.c_void_p]),

@@ -31,7 +31,7 @@ import numpy as np
 import torch
 
 from . import dist as D
-from .inference import bake_cameras, color_mesh, density_grid, estimate_w_stats, extract_mesh, write_mrc, write_ply
+from .inference import bake_cameras, clean_grid, color_mesh, density_grid, estimate_w_stats, extract_mesh, write_mrc, write_ply
 from .inversion import LatentProjector, PivotalTuner, psnr_01
 from .metrics import IDLoss, format_metrics_txt, reconstruction_metrics
 from .video import pivot_grid, write_orbit_video, write_png
@@ -63,6 +63,7 @@ class InversionCoach:
                  w_avg_samples: int = 10000, w_stats: Optional[Tuple[torch.Tensor, float]] = None,
                  start_w_fn: Optional[Callable[[torch.Tensor], torch.Tensor]] = None, sr_fp16: bool = True, gen_mesh: bool = False,
                  mesh_dir: Optional[str] = None, mesh_res: int = 512, mesh_level: float = 10.0, mesh_format: str = '.mrc', mesh_colors: bool = False,
+                 mesh_keep: Optional[int] = None, mesh_min_voxels: int = 0,
                  do_evaluation: bool = False, eval_dir: Optional[str] = None, lpips_eval_net: Optional[Callable] = None,
                  id_net: Optional[Callable] = None, save_pivot: bool = False, pivot_dir: Optional[str] = None, shape_views: bool = False,
                  save_grid: bool = False, gen_video: bool = False, media_dir: Optional[str] = None, video_quality: int = 90):
@@ -76,7 +77,9 @@ class InversionCoach:
         {mesh_dir}/{name}_pti{mesh_format} like create_geometry(shape_res=mesh_res, shape_format=mesh_format): '.mrc' = the raw density grid,
         '.ply' = its marching-cubes mesh at `mesh_level` (the reference's level 10).  `mesh_colors` (no reference counterpart; '.ply' only):
         the PLY also carries per-vertex normals and colours (inference.color_mesh with the pivot camera first among the bake views: the view
-        the photograph constrains); x y z and the faces are those of the plain file.
+        the photograph constrains); x y z and the faces are those of the plain file.  `mesh_keep` / `mesh_min_voxels` (no reference
+        counterpart): floater removal, inference.clean_grid(keep=, min_voxels=) on the density grid before it is meshed, coloured or written
+        ('.mrc' then holds the cleaned grid), and on the grid behind `shape_views`; the defaults leave every file as it was.
         `do_evaluation` (global_config.do_evaluation): after Phase B render G.synthesis(w_pivot[:, :14], cam[:, :25]) with the tuned generator and
         write metrics.reconstruction_metrics to {eval_dir}/{name}metrics.txt; `lpips_eval_net` (LPIPSAlex) and `id_net` (IDLoss) are built
         once per coach when None.  `save_pivot` writes {pivot_dir}/{name}_ws.npy and {name}_cam.npy; in the reference it only takes effect
@@ -101,6 +104,9 @@ class InversionCoach:
         if mesh_colors and mesh_format != '.ply':
             raise ValueError("mesh_colors needs mesh_format='.ply': an '.mrc' file is the density grid")
         self.mesh_colors = bool(mesh_colors)
+        if mesh_keep is not None and int(mesh_keep) < 0:
+            raise ValueError(f'mesh_keep must be >= 0 or None, got {mesh_keep!r}')
+        self.mesh_keep, self.mesh_min_voxels = (None if mesh_keep is None else int(mesh_keep)), int(mesh_min_voxels)
         self.gen_mesh, self.mesh_dir, self.mesh_res, self.mesh_level, self.mesh_format = gen_mesh, mesh_dir, int(mesh_res), float(mesh_level), mesh_format
         self.do_evaluation, self.eval_dir, self.save_pivot, self.pivot_dir = do_evaluation, eval_dir, save_pivot, pivot_dir
         self.lpips_eval_net, self.id_net = lpips_eval_net, id_net
@@ -230,30 +236,42 @@ class InversionCoach:
         grid_path = video_path = None
         if self.save_grid:
             grid_path = os.path.join(d, f'{name}.png')
-            write_png(grid_path, pivot_grid(self.G, w_pivot, cam, target, shape=self.shape_views, **self.synth_kwargs))
+            write_png(grid_path, pivot_grid(self.G, w_pivot, cam, target, shape=self.shape_views, shape_kwargs=self._clean_kwargs() or None,
+                                            **self.synth_kwargs))
         if self.gen_video:
             video_path = os.path.join(d, f'{name}_pivot.avi' if pivot else f'{name}.avi')
-            write_orbit_video(self.G, w_pivot, video_path, quality=self.video_quality, shape=self.shape_views, **self.synth_kwargs)
+            write_orbit_video(self.G, w_pivot, video_path, quality=self.video_quality, shape=self.shape_views,
+                              shape_kwargs=self._clean_kwargs() or None, **self.synth_kwargs)
         return grid_path, video_path
+
+    def _clean_kwargs(self) -> dict:
+        """keep / min_voxels for inference.clean_grid and its callers; empty with the defaults, so that nothing is labelled."""
+        if self.mesh_keep is None and self.mesh_min_voxels <= 0:
+            return {}
+        return dict(keep=self.mesh_keep, min_voxels=self.mesh_min_voxels)
 
     def write_mesh(self, name: str, w_pivot: torch.Tensor, cam: Optional[torch.Tensor] = None) -> str:
         """create_geometry(G, w_pivot, outdir=mesh_dir, fname=name + '_pti') with the generator as it is now (the tuned one); with
         mesh_colors the PLY carries normals and colours baked from `cam` (the pivot camera) and inference.bake_cameras()."""
         os.makedirs(self.mesh_dir, exist_ok=True)
         path = os.path.join(self.mesh_dir, f'{name}_pti{self.mesh_format}')
+        clean = self._clean_kwargs()
         if self.mesh_format == '.ply':
             if self.mesh_colors:
                 from .hipops import marching_cubes
                 grid = density_grid(self.G, w_pivot, res=self.mesh_res)                  # extract_mesh's two steps, keeping the grid for the bake
+                if clean:
+                    grid = clean_grid(grid, self.mesh_level, **clean)[0]
                 verts, faces = marching_cubes(grid, self.mesh_level)
                 att = color_mesh(self.G, w_pivot, verts, self.mesh_res, level=self.mesh_level, grid=grid, cameras=self.mesh_cameras(cam),
                                  **self.synth_kwargs)
                 write_ply(path, verts, faces, normals=att['normals'], colors=att['colors'])
             else:
-                verts, faces = extract_mesh(self.G, w_pivot, res=self.mesh_res, level=self.mesh_level)
+                verts, faces = extract_mesh(self.G, w_pivot, res=self.mesh_res, level=self.mesh_level, **clean)
                 write_ply(path, verts, faces)
         else:
-            write_mrc(path, density_grid(self.G, w_pivot, res=self.mesh_res))
+            grid = density_grid(self.G, w_pivot, res=self.mesh_res)
+            write_mrc(path, clean_grid(grid, self.mesh_level, **clean)[0] if clean else grid)
         return path
 
     @staticmethod

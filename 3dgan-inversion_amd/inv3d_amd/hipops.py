@@ -1952,6 +1952,64 @@ def mesh_bake(points: torch.Tensor, normals: torch.Tensor, images: torch.Tensor,
     return out
 
 
+def _cc_grid(vol: torch.Tensor, what: str) -> torch.Tensor:
+    L.require_cuda(vol)
+    if vol.dim() != 3 or vol.dtype != torch.float32:
+        raise L.Eg3dHipError(f'{what}: a 3-D fp32 grid, got {tuple(vol.shape)} {vol.dtype}')
+    return vol.contiguous()
+
+
+def grid_components(vol: torch.Tensor, level: float, connectivity: int = 6) -> dict:
+    """Connected components of {vol > level} of the fp32 grid vol [D0,D1,D2] (eg3d_cc_*; include/eg3d_hip.h "Grid components").  Inside =
+    v > level as in marching_cubes and iso_render (NaN and v == level are outside); connectivity 6 joins face neighbours, 26 also edge and
+    corner neighbours.  Returns a dict:
+      labels int32 [D0,D1,D2]   0 outside, 1..K inside, components numbered in ascending order of their smallest linear index
+      sizes  int32 [K]          voxels per component;   roots int32 [K]  each component's smallest linear index
+      count  K;   inside        voxels above the level (Python ints)
+    The result is a function of the input alone (bit-identical between runs and builds).  Workspace (4 bytes per voxel) from the caching
+    allocator; one host synchronise (the totals)."""
+    vol = _cc_grid(vol, 'grid_components')
+    if connectivity not in (6, 26):
+        raise L.Eg3dHipError(f'grid_components: connectivity 6 or 26, got {connectivity!r}')
+    dev = vol.device
+    labels = torch.empty(vol.shape, dtype=torch.int32, device=dev)
+    p = L.CcParams(vol=vol.data_ptr(), labels=labels.data_ptr(), D0=vol.shape[0], D1=vol.shape[1], D2=vol.shape[2], level=float(level),
+                   connectivity=int(connectivity))
+    lib = L.lib()
+    nbytes = C.c_int64(0)
+    L.check(lib.eg3d_cc_query_workspace(C.byref(p), C.byref(nbytes)), 'cc_query_workspace')
+    ws = torch.empty(nbytes.value, dtype=torch.uint8, device=dev)
+    totals = torch.empty(2, dtype=torch.int64, device=dev)
+    p.workspace, p.workspace_bytes, p.totals = ws.data_ptr(), nbytes.value, totals.data_ptr()
+    L.check(lib.eg3d_cc_label(C.byref(p), L.stream_ptr()), 'cc_label')
+    K, inside = totals.tolist()
+    sizes = torch.empty(K, dtype=torch.int32, device=dev)
+    roots = torch.empty(K, dtype=torch.int32, device=dev)
+    p.count, p.sizes, p.roots = K, (sizes.data_ptr() if K else None), (roots.data_ptr() if K else None)
+    L.check(lib.eg3d_cc_finish(C.byref(p), L.stream_ptr()), 'cc_finish')
+    return dict(labels=labels, sizes=sizes, roots=roots, count=K, inside=inside)
+
+
+def grid_keep(vol: torch.Tensor, labels: torch.Tensor, keep_mask: torch.Tensor, fill: float = -1000.0) -> torch.Tensor:
+    """A copy of the fp32 grid vol in which every voxel of a component the mask drops holds `fill`: out = keep[labels] ? vol : fill with
+    keep = (True, *keep_mask) -- keep_mask [K] is indexed by label - 1 (select_components' result), and label 0, the outside, stays as it
+    was (NaN included).  labels as grid_components returns them.  One streaming launch (eg3d_cc_keep), no host synchronise."""
+    vol = _cc_grid(vol, 'grid_keep')
+    L.require_cuda(labels)
+    if labels.shape != vol.shape or labels.dtype != torch.int32 or not labels.is_contiguous() or labels.device != vol.device:
+        raise L.Eg3dHipError(f'grid_keep: labels must be contiguous int32 {tuple(vol.shape)} on {vol.device}, got {tuple(labels.shape)} {labels.dtype}')
+    if keep_mask.dim() != 1:
+        raise L.Eg3dHipError(f'grid_keep: keep_mask [K], got {tuple(keep_mask.shape)}')
+    K = keep_mask.shape[0]
+    table = torch.ones(K + 1, dtype=torch.uint8, device=vol.device)
+    table[1:] = keep_mask.to(device=vol.device, dtype=torch.bool)
+    out = torch.empty_like(vol)
+    p = L.CcParams(vol=vol.data_ptr(), labels=labels.data_ptr(), D0=vol.shape[0], D1=vol.shape[1], D2=vol.shape[2], count=K, keep=table.data_ptr(),
+                   out=out.data_ptr(), fill=float(fill))
+    L.check(L.lib().eg3d_cc_keep(C.byref(p), L.stream_ptr()), 'cc_keep')
+    return out
+
+
 def _ssim_params(x, y, mode, weights, nonnegative, size_average, win_size, win_sigma, C1, C2):
     N, Ch, Hh, Ww = x.shape
     p = L.SsimParams(x=x.data_ptr(), y=y.data_ptr(), N=N, C=Ch, H=Hh, W=Ww, mode=mode, levels=len(weights), nonnegative=int(bool(nonnegative)),

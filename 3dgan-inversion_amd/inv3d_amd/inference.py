@@ -11,6 +11,9 @@ G.mapping / ImportanceRenderer.run_model on the gfx950 kernels.
   write_mrc                    <- create_geometry's '.mrc' branch (single_id_coach.py:158-160, mrcfile.new_mmap mode 2), no mrcfile
   grid_frame, render_shape,    no reference counterpart: shaded first-hit views of the density surface from the generator's own cameras
   render_shape_orbit              (hipops.iso_render over density_grid's grid), to look at the recovered shape without an external viewer
+  select_components,           no reference counterpart (it exports every blob above the level): floater removal on the density grid --
+  clean_grid                      hipops.grid_components labels {sigma > level}, the components to drop are filled with a low value, and one
+                                  cleaned grid serves marching cubes, the shaded views, the mesh attributes and the .mrc writer
   mesh_to_world, bake_cameras, no reference counterpart (its meshes are bare x y z): per-vertex normals of the density field and vertex colours
   color_mesh, normals_to_mesh     blended from rendered views that see the vertex (hipops.mesh_normals / mesh_bake), for write_ply's optional
                                   nx ny nz / red green blue properties
@@ -131,15 +134,68 @@ def density_grid(G, ws: torch.Tensor, res: int = 512, max_batch: int = 1 << 22, 
     return g
 
 
+def select_components(sizes: torch.Tensor, keep: Optional[int] = 1, min_voxels: int = 0) -> torch.Tensor:
+    """bool [K] over the components of hipops.grid_components (entry i is label i + 1): the `keep` largest that have at least `min_voxels`
+    voxels; keep=None puts no cap on the count.  Ties go to the smaller label.  Plain torch on the device of `sizes` (CPU tensors work): the
+    order is that of one int64 key per component, (size << 32) | (2^31 - 1 - index), descending -- not topk's treatment of equal values."""
+    sizes = torch.as_tensor(sizes)
+    if sizes.dim() != 1:
+        raise ValueError(f'select_components: sizes [K], got {tuple(sizes.shape)}')
+    if keep is not None and int(keep) < 0:
+        raise ValueError(f'select_components: keep >= 0 or None, got {keep!r}')
+    K = sizes.shape[0]
+    idx = torch.arange(K, dtype=torch.int64, device=sizes.device)
+    key = (sizes.to(torch.int64) << 32) | ((1 << 31) - 1 - idx)
+    order = torch.argsort(key, descending=True)                 # the keys are distinct: any sort gives this order
+    order = order[sizes[order] >= int(min_voxels)]              # a prefix: the keys descend with the sizes
+    if keep is not None:
+        order = order[:int(keep)]
+    mask = torch.zeros(K, dtype=torch.bool, device=sizes.device)
+    mask[order] = True
+    return mask
+
+
+def _wants_cleaning(keep, min_voxels) -> bool:
+    return keep is not None or int(min_voxels) > 0
+
+
 @torch.no_grad()
-def extract_mesh(G, ws: torch.Tensor, res: int = 512, level: float = 10.0, max_batch: int = 1 << 22, attributes: bool = False, **synthesis_kwargs):
+def clean_grid(grid: torch.Tensor, level: float, keep: Optional[int] = 1, min_voxels: int = 0, connectivity: int = 6, fill: float = -1000.0):
+    """(cleaned grid, info): `grid` with every connected component of {grid > level} that select_components(keep, min_voxels) drops filled with
+    `fill` (hipops.grid_components, then hipops.grid_keep; the input is not modified).  Components are separated by voxels at or below the
+    level, so on the kept ones marching cubes and the ray marcher see the samples they saw before.  fill must be finite and not above the
+    level (density_grid's padding value by default).  info: count (components found), kept (int64 labels, ascending), sizes (int32 [count]),
+    removed_voxels."""
+    from .hipops import grid_components, grid_keep
+    fill = float(fill)
+    if not math.isfinite(fill):
+        raise ValueError(f'clean_grid: fill must be finite, got {fill}')
+    if fill > float(level):
+        raise ValueError(f'clean_grid: fill {fill} is above the level {level}: the removed components would stay inside')
+    if connectivity not in (6, 26):
+        raise ValueError(f'clean_grid: connectivity 6 or 26, got {connectivity!r}')
+    cc = grid_components(grid, level, connectivity)
+    mask = select_components(cc['sizes'], keep=keep, min_voxels=min_voxels)
+    removed = int(cc['sizes'][~mask].to(torch.int64).sum()) if cc['count'] else 0
+    info = dict(count=cc['count'], kept=torch.nonzero(mask).reshape(-1) + 1, sizes=cc['sizes'], removed_voxels=removed)
+    if removed == 0:
+        return grid, info
+    return grid_keep(grid, cc['labels'], mask, fill), info
+
+
+@torch.no_grad()
+def extract_mesh(G, ws: torch.Tensor, res: int = 512, level: float = 10.0, max_batch: int = 1 << 22, attributes: bool = False,
+                 keep: Optional[int] = None, min_voxels: int = 0, connectivity: int = 6, **synthesis_kwargs):
     """(verts fp32 [V,3], faces int32 [F,3]) on the device: density_grid, then marching cubes at `level` in the coordinates of the reference's
     PLY (marching_cubes(np.transpose(grid, (2,1,0)), level, spacing=[1]*3), origin [0,0,0]: voxel units).  Faces are wound so that their
     right-hand normals point out of the dense region.  Triangles may differ from skimage's Lewiner method in ambiguous cubes; vertices do not.
     attributes=True: (verts, faces, normals fp32 [V,3], colors uint8 [V,3]) with color_mesh's defaults on the same grid; verts and faces are
-    those of the plain call."""
+    those of the plain call.  keep / min_voxels / connectivity: clean_grid first (floater removal); with keep=None and min_voxels=0, the
+    default, nothing is labelled and the call is what it was."""
     from .hipops import marching_cubes
     grid = density_grid(G, ws, res=res, max_batch=max_batch, **synthesis_kwargs)
+    if _wants_cleaning(keep, min_voxels):
+        grid = clean_grid(grid, level, keep=keep, min_voxels=min_voxels, connectivity=connectivity)[0]
     verts, faces = marching_cubes(grid, level)
     if not attributes:
         return verts, faces
@@ -160,15 +216,19 @@ def grid_frame(G, res: int):
 
 @torch.no_grad()
 def render_shape(G, ws: torch.Tensor, cameras: torch.Tensor, res: Optional[int] = None, grid_res: int = 512, level: float = 10.0,
-                 grid: Optional[torch.Tensor] = None, **kw) -> dict:
+                 grid: Optional[torch.Tensor] = None, keep: Optional[int] = None, min_voxels: int = 0, connectivity: int = 6, **kw) -> dict:
     """Shaded first-hit views of the sigma = level surface of one latent from `cameras` [F,25]: hipops.iso_render's dict (depth, normal, mask,
     shade [F,3,res,res] in [-1,1], bricks) plus 'grid'.  res defaults to the generator's image resolution, so a frame registers pixel for pixel
     with G.synthesis(ws, camera)['image'].  The density grid (density_grid at grid_res, laid out as grid_frame says) is built here unless one is
     passed; pass the returned 'grid' and 'bricks' back in (grid=..., bricks=...) to render more views of the same latent.  Further keywords go to
-    hipops.iso_render (step, refine, skip, shade, ambient, background, bricks)."""
+    hipops.iso_render (step, refine, skip, shade, ambient, background, bricks).  keep / min_voxels / connectivity: the grid (built here or
+    passed) goes through clean_grid first, and 'grid' is the cleaned one -- a caller that passes it back in for more views leaves the options
+    out, as render_shape_orbit does; bricks passed in must belong to the cleaned grid."""
     from .hipops import iso_render
     if grid is None:
         grid = density_grid(G, ws, res=grid_res)
+    if _wants_cleaning(keep, min_voxels):
+        grid = clean_grid(grid, level, keep=keep, min_voxels=min_voxels, connectivity=connectivity)[0]
     if grid.dim() != 3 or len(set(grid.shape)) != 1:
         raise ValueError(f'render_shape: a cubic density grid, got {tuple(grid.shape)}')
     origin, spacing, axes = grid_frame(G, grid.shape[0])
@@ -179,14 +239,17 @@ def render_shape(G, ws: torch.Tensor, cameras: torch.Tensor, res: Optional[int] 
 
 @torch.no_grad()
 def render_shape_orbit(G, ws: torch.Tensor, num_frames: int = 240, cameras: Optional[torch.Tensor] = None, res: Optional[int] = None,
-                       grid_res: int = 512, level: float = 10.0, grid: Optional[torch.Tensor] = None, **kw) -> Iterator[torch.Tensor]:
+                       grid_res: int = 512, level: float = 10.0, grid: Optional[torch.Tensor] = None, keep: Optional[int] = None,
+                       min_voxels: int = 0, connectivity: int = 6, **kw) -> Iterator[torch.Tensor]:
     """Yields one shaded [3,res,res] frame per camera of orbit_cameras (or `cameras`), the companion of render_orbit: one density grid and one
-    brick pass for the whole orbit, one launch per frame."""
+    brick pass for the whole orbit, one launch per frame.  keep / min_voxels / connectivity (clean_grid) apply once, with the first frame."""
     dev = ws.device
     cams = orbit_cameras(num_frames, device=dev) if cameras is None else cameras.to(dev)
     state = dict(grid=grid, bricks=kw.pop('bricks', None))
+    clean = dict(keep=keep, min_voxels=min_voxels, connectivity=connectivity)
     for i in range(cams.shape[0]):
-        out = render_shape(G, ws, cams[i:i + 1], res=res, grid_res=grid_res, level=level, grid=state['grid'], bricks=state['bricks'], **kw)
+        out = render_shape(G, ws, cams[i:i + 1], res=res, grid_res=grid_res, level=level, grid=state['grid'], bricks=state['bricks'],
+                           **(clean if i == 0 else {}), **kw)
         state = dict(grid=out['grid'], bricks=out['bricks'])
         yield out['shade'][0]
 
@@ -244,7 +307,7 @@ def _to_u8(color: torch.Tensor) -> torch.Tensor:
 @torch.no_grad()
 def color_mesh(G, ws: torch.Tensor, verts: torch.Tensor, res: int, level: float = 10.0, grid: Optional[torch.Tensor] = None,
                cameras: Optional[torch.Tensor] = None, source: str = 'views', depth_tol: Optional[float] = None, cos_min: float = 0.1,
-               power: int = 2, **synthesis_kwargs) -> dict:
+               power: int = 2, keep: Optional[int] = None, min_voxels: int = 0, connectivity: int = 6, **synthesis_kwargs) -> dict:
     """Normals and colours for the vertices `verts` [V,3] of marching_cubes / extract_mesh at grid resolution `res` and `level`.  Returns a dict:
       world   fp32 [V,3]   the vertices in world coordinates (mesh_to_world)
       normals fp32 [V,3]   unit normals of the density field (hipops.mesh_normals on density_grid's grid, built here unless `grid` is passed)
@@ -258,13 +321,16 @@ def color_mesh(G, ws: torch.Tensor, verts: torch.Tensor, res: int, level: float 
     as the renderer forms image_raw.  source='radiance': the fallback is the colour and nothing is rendered.
     depth_tol=None means two voxels of the grid in world units: a default chosen from geometry (at 512 pixels over the frame a depth pixel is
     about as wide as a voxel of a 512^3 grid, and the mesh vertex and the marcher's hit differ by interpolation, less than a voxel), not
-    tuned on real heads.  Further keywords go to G.synthesis."""
+    tuned on real heads.  keep / min_voxels / connectivity: a grid built here goes through clean_grid first, so that removed floaters neither
+    shape the normals nor occlude the views (a grid that is passed in is taken as it is).  Further keywords go to G.synthesis."""
     from .hipops import iso_bricks, iso_render, mesh_bake, mesh_normals
     if source not in ('views', 'radiance'):
         raise ValueError(f"color_mesh: source 'views' or 'radiance', got {source!r}")
     res = int(res)
     if grid is None:
         grid = density_grid(G, ws, res=res)
+        if _wants_cleaning(keep, min_voxels):
+            grid = clean_grid(grid, level, keep=keep, min_voxels=min_voxels, connectivity=connectivity)[0]
     if tuple(grid.shape) != (res, res, res):
         raise ValueError(f'color_mesh: a {res}^3 density grid, got {tuple(grid.shape)}')
     dev = grid.device

@@ -192,10 +192,10 @@ def write_orbit_video(G, ws: torch.Tensor, path: str, num_frames: int = 240, ima
     """gen_interp_video for one latent: inference.render_orbit's frames, `batch` at a time through hipops.jpeg_encode (4:2:0; grey for
     image_depth), one device-to-host copy per batch, into a Motion-JPEG AVI at `path`.  Returns the number of frames written.
     shape=True (no reference counterpart): every frame is image | shape side by side, twice the width -- the shaded first-hit view of the
-    density surface from the same camera at the frame's resolution (inference.render_shape; shape_kwargs: grid_res, level, shade, ...).  The
-    density grid and its brick maxima are built once per video.  With shape=False the file is what it was before the option existed."""
+    density surface from the same camera at the frame's resolution (inference.render_shape; shape_kwargs: grid_res, level, shade, keep,
+    min_voxels, connectivity, ...).  The density grid and its brick maxima are built once per video, and so is inference.clean_grid's pass.  With shape=False the file is what it was before the option existed."""
     from .hipops import jpeg_encode
-    from .inference import density_grid, orbit_cameras, render_orbit, render_shape
+    from .inference import clean_grid, density_grid, orbit_cameras, render_orbit, render_shape
     if batch < 1:
         raise ValueError('write_orbit_video: batch >= 1')
     writer, pending, n = None, [], 0
@@ -206,6 +206,9 @@ def write_orbit_video(G, ws: torch.Tensor, path: str, num_frames: int = 240, ima
         # before the first frame: the grid runs the backbone, and render_orbit keeps the planes of its first frame for the later ones
         grid = skw.pop('grid', None)
         state = dict(grid=density_grid(G, ws, res=skw.get('grid_res', 512)) if grid is None else grid, bricks=skw.pop('bricks', None))
+        clean = {k: skw.pop(k) for k in ('keep', 'min_voxels', 'connectivity') if k in skw}      # floater removal: once per video, not per frame
+        if clean.get('keep') is not None or int(clean.get('min_voxels', 0)) > 0:
+            state['grid'] = clean_grid(state['grid'], skw.get('level', 10.0), **clean)[0]
 
     def beside(i, frame):
         out = render_shape(G, ws, cams[i:i + 1], res=frame.shape[-1], grid=state['grid'], bricks=state['bricks'], **skw)

@@ -1149,6 +1149,72 @@ int eg3d_mesh_normals(const eg3d_mesh_normals_params* p, void* stream);
 int eg3d_mesh_bake(const eg3d_mesh_bake_params* p, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Grid components: connected-component labelling of {vol > level} and removal of components (csrc/grid_components.hip).  No reference
+ *   counterpart (the reference exports every blob above the level).  tests/support/cc_ref.py restates the result in numpy; the outputs are
+ *   compared exactly.
+ *   vol: contiguous fp32 [D0][D1][D2] (i2 fastest), D0, D1, D2 >= 1, D0*D1*D2 < 2^31.  A voxel is inside iff v > level, the rule of marching
+ *   cubes and of the ray marcher: NaN is outside, v == level is outside, +inf is inside.  Two inside voxels are adjacent when their indices
+ *   differ by at most one on every axis and, with connectivity 6, on exactly one axis (faces); with 26 on one, two or three (faces, edges,
+ *   corners).  A component is a class of the transitive closure.
+ *   Result: labels int32 [D0][D1][D2]: 0 outside; inside 1..K, the components numbered in ascending order of their smallest linear index
+ *   ((i0 * D1 + i1) * D2 + i2: raster order of first appearance).  roots int32 [K]: that smallest index.  sizes int32 [K]: voxels.
+ *   totals int64[2] on the device = (K, inside voxels).  The result is a function of (vol, level, connectivity) alone: integer arithmetic,
+ *   and although the merge is lock-free and its intermediate trees depend on the schedule, the partition, each component's smallest index
+ *   and the integer sums do not.  Bit-identical between runs and between the two builds.
+ *   Protocol (workspace lent by the caller; the library allocates nothing):
+ *     eg3d_cc_query_workspace  host only: workspace bytes (a parent volume of one int32 per voxel, plus the scan's counters)
+ *     eg3d_cc_label            passes (a)-(d) below; writes totals
+ *     (host reads totals: one synchronise; allocates sizes [K], roots [K]; sets count = K)
+ *     eg3d_cc_finish           passes (e), (f): writes labels, sizes, roots.  count = 0 (K = 0, a normal result): labels are zero-filled, no
+ *                              launch of (e) or (f).  A count below K truncates roots / sizes (never written beyond count entries).
+ *   Passes (tile = EG3D_CC_TILE0 x EG3D_CC_TILE1 x EG3D_CC_TILE2 voxels, one workgroup each; chunk = 4096 consecutive voxels):
+ *     (a) per tile: occupancy and a union-find over the tile's own adjacencies in LDS; parent[v] = linear index of the smallest voxel of v's
+ *         component within the tile (v itself for that voxel: a local root), -1 outside.  16-byte loads and stores when D2 % 4 == 0.
+ *     (b) per tile: every inside voxel with a forward neighbour (higher linear index) in another tile unites the two sets: find both roots,
+ *         compare-and-swap the larger root's parent from itself to the smaller, on failure continue from the value returned.
+ *     (c) per chunk: count roots (parent[v] == v) and inside voxels.            (d) one workgroup: exclusive scan over the chunks, totals.
+ *     (e) per chunk: each root takes rank = chunk offset + its place in the chunk; parent[root] = -2 - rank; roots[rank] = root.
+ *     (f) per tile: every inside voxel walks to its root, labels[v] = rank + 1; voxel counts are summed in LDS per local root and added to
+ *         sizes with one atomic per local root.
+ *   Rules of the device code (gfx950: per-XCD L2s are not coherent with each other and a CU's L1 is never refreshed by another CU's stores):
+ *     - in (b) every access to a parent word is an agent-scope atomic (__hip_atomic_load relaxed, atomicMin, atomicCAS), never a plain load or
+ *       store.  A stale value would still be harmless: every value a parent word ever held is an ancestor of the voxel in the final forest;
+ *     - (b) writes only parent words of local roots; every other pass reads only what an earlier launch wrote, or its own writes;
+ *     - no workgroup waits for another: no flags, no spin loops, no grid barriers.  Every loop over parents ends because a parent is
+ *       strictly smaller than its child, and every retry of a union continues from a strictly smaller index;
+ *     - counters are cleared by a kernel on the same stream.
+ *   Errors, before any launch: EG3D_ERR_INVALID (null params / vol / labels / workspace / totals, any D < 1, connectivity not 6 or 26, short
+ *   workspace, count < 0, null sizes / roots with count > 0), EG3D_ERR_TOO_LARGE (2^31 voxels or more).
+ *
+ * eg3d_cc_keep (one streaming launch): out[i] = (l = labels[i]; l < 1 || l > count || keep[l]) ? vol[i] : fill.  keep: uint8 [count + 1];
+ *   entry 0 is never read, the outside stays as it was (NaN included).  out may alias vol.  Errors: EG3D_ERR_INVALID (null params / vol /
+ *   labels / out, null keep with count > 0, any D < 1, count < 0), EG3D_ERR_TOO_LARGE.
+ */
+#define EG3D_CC_TILE0 8
+#define EG3D_CC_TILE1 8
+#define EG3D_CC_TILE2 64
+typedef struct eg3d_cc_params {
+    const float* vol;                  /* [D0][D1][D2] */
+    int32_t* labels;                   /* [D0][D1][D2] */
+    int32_t D0, D1, D2;
+    float level;
+    int32_t connectivity;              /* 6 | 26 */
+    int32_t count;                     /* K: eg3d_cc_finish, eg3d_cc_keep */
+    void* workspace;                   /* eg3d_cc_query_workspace's bytes; carries the state from eg3d_cc_label to eg3d_cc_finish */
+    int64_t workspace_bytes;
+    int64_t* totals;                   /* device int64[2] */
+    int32_t* sizes;                    /* [count] */
+    int32_t* roots;                    /* [count] */
+    const uint8_t* keep;               /* [count + 1] */
+    float* out;                        /* [D0][D1][D2] */
+    float fill;
+} eg3d_cc_params;
+int eg3d_cc_query_workspace(const eg3d_cc_params* p, int64_t* workspace_bytes);
+int eg3d_cc_label(const eg3d_cc_params* p, void* stream);
+int eg3d_cc_finish(const eg3d_cc_params* p, void* stream);
+int eg3d_cc_keep(const eg3d_cc_params* p, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * SSIM / MS-SSIM (reconstruction metrics) -- pytorch_msssim 1.0's ssim / ms_ssim with win=None, as the reference's evaluation calls it
  *   (training/coaches/single_id_coach.py:87-99; csrc/ssim.hip).  x, y: contiguous fp32 [N,C,H,W], any value range.
  *   Gaussian window win[k] = exp(-(k - win_size/2)^2 / (2 sigma^2)) / sum, applied separably (H then W) per channel, valid (no padding).

@@ -2,13 +2,16 @@
 convert_sdf_samples_to_ply, shape_utils.py:40-100), on the GPU kernels of this package.
 
   python tools/extract_mesh.py --ws pivot_ws.npy --out face.ply [--weights G.safetensors] [--res 512] [--level 10] [--mrc face.mrc]
-                               [--colors [--views N_YAW N_PITCH] [--radiance]]
+                               [--colors [--views N_YAW N_PITCH] [--radiance]] [--keep N] [--min-voxels M] [--connectivity {6,26}]
 
 --weights: a generator archive (inv3d_amd.weights, tools/convert_eg3d_pickle.py); without it, the full-size synthetic generator
 (inv3d_amd.synthetic, seed --seed).  --ws: a [1, num_ws, w_dim] (or [num_ws, w_dim]) .npy latent, e.g. the reference's {image}_ws.npy.
 --mrc additionally writes the density grid as create_geometry's '.mrc' branch does.
 --colors adds per-vertex normals (nx ny nz) and colours (red green blue) to the PLY (inference.color_mesh; no reference counterpart): colours
-blended from N_YAW x N_PITCH rendered views around the frontal camera (default 5 x 3), or with --radiance the generator's own radiance at the vertices, without rendering."""
+blended from N_YAW x N_PITCH rendered views around the frontal camera (default 5 x 3), or with --radiance the generator's own radiance at the vertices, without rendering.
+--keep N / --min-voxels M remove floaters first (inference.clean_grid; no reference counterpart): only the N largest connected components of
+{sigma > level} that have at least M voxels stay (--connectivity 6: face neighbours, 26: edges and corners too), in the mesh, its colours and the
+--mrc grid alike; the components found and kept and the voxels removed are printed.  Without either option nothing is labelled."""
 import argparse
 import os
 import sys
@@ -33,6 +36,9 @@ def main():
     ap.add_argument('--colors', action='store_true', help='write per-vertex normals and colours too')
     ap.add_argument('--views', type=int, nargs=2, default=(5, 3), metavar=('N_YAW', 'N_PITCH'), help='bake views around the frontal camera')
     ap.add_argument('--radiance', action='store_true', help="colour from the generator's radiance at the vertices instead of rendered views")
+    ap.add_argument('--keep', type=int, default=None, help='keep only the N largest connected components above the level')
+    ap.add_argument('--min-voxels', type=int, default=0, help='drop connected components of fewer voxels')
+    ap.add_argument('--connectivity', type=int, default=6, choices=(6, 26))
     a = ap.parse_args()
     from inv3d_amd import inference as INF
     dev = torch.device('cuda')
@@ -49,10 +55,17 @@ def main():
     t0 = time.perf_counter()
     grid = INF.density_grid(G, ws, res=a.res)
     from inv3d_amd.hipops import marching_cubes
+    cleaned = ''
+    if a.keep is not None or a.min_voxels > 0:
+        t1 = time.perf_counter()
+        grid, info = INF.clean_grid(grid, a.level, keep=a.keep, min_voxels=a.min_voxels, connectivity=a.connectivity)
+        torch.cuda.synchronize()
+        cleaned = (f'; {info["count"]} components found, {info["kept"].numel()} kept, {info["removed_voxels"]} voxels removed '
+                   f'({(time.perf_counter() - t1) * 1e3:.1f} ms)')
     verts, faces = marching_cubes(grid, a.level)
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
-    note = ''
+    note = cleaned
     if a.colors:
         t1 = time.perf_counter()
         cams = INF.bake_cameras(a.views[0], a.views[1], device=dev)
@@ -60,7 +73,7 @@ def main():
         torch.cuda.synchronize()
         INF.write_ply(a.out, verts, faces, normals=att['normals'], colors=att['colors'])
         seen = int((att['views'] > 0).sum())
-        note = (f'; normals + colours {(time.perf_counter() - t1) * 1e3:.1f} ms, '
+        note += (f'; normals + colours {(time.perf_counter() - t1) * 1e3:.1f} ms, '
                 + ('radiance' if a.radiance else f'{seen} of {verts.shape[0]} vertices coloured from {cams.shape[0]} views'))
     else:
         INF.write_ply(a.out, verts, faces)

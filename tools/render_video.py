@@ -6,7 +6,8 @@ single_id_coach.py:61-62,84-85 calls it), frames encoded by the GPU JPEG encoder
 --weights: a generator archive (inv3d_amd.weights, tools/convert_eg3d_pickle.py); without it, the full-size synthetic generator
 (inv3d_amd.synthetic, seed --seed).  --ws: a [1, num_ws, w_dim] (or [num_ws, w_dim]) .npy latent, e.g. the coach's {image}_ws.npy.
 --depth renders image_depth (grey frames) instead of the colour image.  --shape puts the shaded first-hit view of the density surface
-(--shape-level, --shape-grid, --shape-shade lambert | normal) beside every frame: twice the width, one density grid per video."""
+(--shape-level, --shape-grid, --shape-shade lambert | normal) beside every frame: twice the width, one density grid per video.
+With --shape, --keep N / --min-voxels M / --connectivity {6,26} remove floaters from that grid first (inference.clean_grid, once per video)."""
 import argparse
 import os
 import sys
@@ -34,6 +35,9 @@ def main():
     ap.add_argument('--shape-level', type=float, default=10.0, help='density level of the surface')
     ap.add_argument('--shape-grid', type=int, default=512, help='side of the density grid')
     ap.add_argument('--shape-shade', default='lambert', choices=['lambert', 'normal'])
+    ap.add_argument('--keep', type=int, default=None, help='--shape: keep only the N largest connected components above the level')
+    ap.add_argument('--min-voxels', type=int, default=0, help='--shape: drop connected components of fewer voxels')
+    ap.add_argument('--connectivity', type=int, default=6, choices=(6, 26))
     a = ap.parse_args()
     from inv3d_amd import video as V
     dev = torch.device('cuda')
@@ -47,9 +51,10 @@ def main():
     ws = torch.from_numpy(np.load(a.ws)).float().to(dev)
     if ws.dim() == 2:
         ws = ws.unsqueeze(0)
+    clean = dict(keep=a.keep, min_voxels=a.min_voxels, connectivity=a.connectivity) if (a.keep is not None or a.min_voxels > 0) else {}
     t0 = time.perf_counter()
     n = V.write_orbit_video(G, ws, a.out, num_frames=a.frames, image_mode='image_depth' if a.depth else 'image', fps=a.fps, quality=a.quality,
-                            batch=a.batch, shape=a.shape, shape_kwargs=dict(level=a.shape_level, grid_res=a.shape_grid, shade=a.shape_shade))
+                            batch=a.batch, shape=a.shape, shape_kwargs=dict(level=a.shape_level, grid_res=a.shape_grid, shade=a.shape_shade, **clean))
     dt = time.perf_counter() - t0
     print(f'{a.out}: {n} frames, {os.path.getsize(a.out)} bytes ({dt * 1e3:.1f} ms, {n / dt:.1f} frames/s)')
 

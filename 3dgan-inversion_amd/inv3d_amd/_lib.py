@@ -263,6 +263,23 @@ class CcParams(C.Structure):
 
 CC_TILE = (8, 8, 64)             # EG3D_CC_TILE0 / 1 / 2: voxels per axis one workgroup labels in LDS
 
+
+class SimplifyParams(C.Structure):
+    """eg3d_simplify_params: vertex clustering (eg3d_simplify_query_workspace / _keys / _heads / _clusters / _mark / _emit)."""
+    _fields_ = [('verts', C.c_void_p), ('faces', C.c_void_p), ('V', C.c_int64), ('F', C.c_int64), ('cell', C.c_float), ('origin', C.c_float * 3),
+                ('flags', C.c_void_p), ('keys', C.c_void_p), ('sorted_keys', C.c_void_p), ('order', C.c_void_p), ('heads', C.c_void_p),
+                ('head_scan', C.c_void_p), ('tri', C.c_void_p), ('alive', C.c_void_p), ('face_order', C.c_void_p), ('used', C.c_void_p),
+                ('alive_scan', C.c_void_p), ('used_scan', C.c_void_p), ('workspace', C.c_void_p), ('workspace_bytes', C.c_int64),
+                ('out_verts', C.c_void_p), ('out_vert_capacity', C.c_int64), ('out_faces', C.c_void_p), ('out_face_capacity', C.c_int64),
+                ('vertex_map', C.c_void_p)]
+
+
+class SmoothParams(C.Structure):
+    """eg3d_smooth_params: Taubin passes over a CSR adjacency (eg3d_smooth_query_workspace / eg3d_smooth)."""
+    _fields_ = [('verts', C.c_void_p), ('out', C.c_void_p), ('rowptr', C.c_void_p), ('cols', C.c_void_p), ('pinned', C.c_void_p), ('V', C.c_int64),
+                ('nnz', C.c_int64), ('iterations', C.c_int32), ('lam', C.c_float), ('mu', C.c_float), ('workspace', C.c_void_p),
+                ('workspace_bytes', C.c_int64)]
+
 SSIM_MAX_LEVELS = 8
 
 
@@ -447,6 +464,14 @@ _SIGS = {
     'eg3d_cc_label': (C.c_int, [C.POINTER(CcParams), C.c_void_p]),
     'eg3d_cc_finish': (C.c_int, [C.POINTER(CcParams), C.c_void_p]),
     'eg3d_cc_keep': (C.c_int, [C.POINTER(CcParams), C.c_void_p]),
+    'eg3d_simplify_query_workspace': (C.c_int, [C.POINTER(SimplifyParams), C.POINTER(C.c_int64)]),
+    'eg3d_simplify_keys': (C.c_int, [C.POINTER(SimplifyParams), C.c_void_p]),
+    'eg3d_simplify_heads': (C.c_int, [C.POINTER(SimplifyParams), C.c_void_p]),
+    'eg3d_simplify_clusters': (C.c_int, [C.POINTER(SimplifyParams), C.c_void_p]),
+    'eg3d_simplify_mark': (C.c_int, [C.POINTER(SimplifyParams), C.c_void_p]),
+    'eg3d_simplify_emit': (C.c_int, [C.POINTER(SimplifyParams), C.c_void_p]),
+    'eg3d_smooth_query_workspace': (C.c_int, [C.POINTER(SmoothParams), C.POINTER(C.c_int64)]),
+    'eg3d_smooth': (C.c_int, [C.POINTER(SmoothParams), C.c_void_p]),
     'eg3d_ssim_query_workspace': (C.c_int, [C.POINTER(SsimParams), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64),
                                             C.POINTER(C.c_int64)]),
     'eg3d_ssim_forward': (C.c_int, [C.POINTER(SsimParams), C.c_void_p]),

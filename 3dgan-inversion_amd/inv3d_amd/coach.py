@@ -25,13 +25,15 @@ e4e.py, pose_net.py and metrics.py.
 from dataclasses import dataclass, field
 from typing import Callable, Dict, List, Optional, Sequence, Tuple
 
+import math
 import os
 
 import numpy as np
 import torch
 
 from . import dist as D
-from .inference import bake_cameras, clean_grid, color_mesh, density_grid, estimate_w_stats, extract_mesh, write_mrc, write_ply
+from .inference import (bake_cameras, clean_grid, color_mesh, density_grid, estimate_w_stats, extract_mesh, simplify_mesh, smooth_mesh, write_mrc,
+                        write_ply)
 from .inversion import LatentProjector, PivotalTuner, psnr_01
 from .metrics import IDLoss, format_metrics_txt, reconstruction_metrics
 from .video import pivot_grid, write_orbit_video, write_png
@@ -63,7 +65,7 @@ class InversionCoach:
                  w_avg_samples: int = 10000, w_stats: Optional[Tuple[torch.Tensor, float]] = None,
                  start_w_fn: Optional[Callable[[torch.Tensor], torch.Tensor]] = None, sr_fp16: bool = True, gen_mesh: bool = False,
                  mesh_dir: Optional[str] = None, mesh_res: int = 512, mesh_level: float = 10.0, mesh_format: str = '.mrc', mesh_colors: bool = False,
-                 mesh_keep: Optional[int] = None, mesh_min_voxels: int = 0,
+                 mesh_keep: Optional[int] = None, mesh_min_voxels: int = 0, mesh_simplify: Optional[float] = None, mesh_smooth: int = 0,
                  do_evaluation: bool = False, eval_dir: Optional[str] = None, lpips_eval_net: Optional[Callable] = None,
                  id_net: Optional[Callable] = None, save_pivot: bool = False, pivot_dir: Optional[str] = None, shape_views: bool = False,
                  save_grid: bool = False, gen_video: bool = False, media_dir: Optional[str] = None, video_quality: int = 90):
@@ -80,6 +82,9 @@ class InversionCoach:
         the photograph constrains); x y z and the faces are those of the plain file.  `mesh_keep` / `mesh_min_voxels` (no reference
         counterpart): floater removal, inference.clean_grid(keep=, min_voxels=) on the density grid before it is meshed, coloured or written
         ('.mrc' then holds the cleaned grid), and on the grid behind `shape_views`; the defaults leave every file as it was.
+        `mesh_simplify` (a cell size in voxels) / `mesh_smooth` (Taubin iterations; no reference counterpart; '.ply' only): the mesh goes
+        through inference.simplify_mesh, then inference.smooth_mesh, before it is written; with `mesh_colors` the normals and colours are
+        those of the final vertices.  None and 0, the defaults, run neither.
         `do_evaluation` (global_config.do_evaluation): after Phase B render G.synthesis(w_pivot[:, :14], cam[:, :25]) with the tuned generator and
         write metrics.reconstruction_metrics to {eval_dir}/{name}metrics.txt; `lpips_eval_net` (LPIPSAlex) and `id_net` (IDLoss) are built
         once per coach when None.  `save_pivot` writes {pivot_dir}/{name}_ws.npy and {name}_cam.npy; in the reference it only takes effect
@@ -107,6 +112,13 @@ class InversionCoach:
         if mesh_keep is not None and int(mesh_keep) < 0:
             raise ValueError(f'mesh_keep must be >= 0 or None, got {mesh_keep!r}')
         self.mesh_keep, self.mesh_min_voxels = (None if mesh_keep is None else int(mesh_keep)), int(mesh_min_voxels)
+        if mesh_simplify is not None and not (float(mesh_simplify) > 0.0 and math.isfinite(float(mesh_simplify))):
+            raise ValueError(f'mesh_simplify must be a positive finite cell size or None, got {mesh_simplify!r}')
+        if int(mesh_smooth) < 0:
+            raise ValueError(f'mesh_smooth must be >= 0 iterations, got {mesh_smooth!r}')
+        if (mesh_simplify is not None or int(mesh_smooth) > 0) and mesh_format != '.ply':
+            raise ValueError("mesh_simplify / mesh_smooth need mesh_format='.ply': an '.mrc' file is the density grid")
+        self.mesh_simplify, self.mesh_smooth = (None if mesh_simplify is None else float(mesh_simplify)), int(mesh_smooth)
         self.gen_mesh, self.mesh_dir, self.mesh_res, self.mesh_level, self.mesh_format = gen_mesh, mesh_dir, int(mesh_res), float(mesh_level), mesh_format
         self.do_evaluation, self.eval_dir, self.save_pivot, self.pivot_dir = do_evaluation, eval_dir, save_pivot, pivot_dir
         self.lpips_eval_net, self.id_net = lpips_eval_net, id_net
@@ -263,11 +275,16 @@ class InversionCoach:
                 if clean:
                     grid = clean_grid(grid, self.mesh_level, **clean)[0]
                 verts, faces = marching_cubes(grid, self.mesh_level)
+                if self.mesh_simplify is not None:
+                    verts, faces, _ = simplify_mesh(verts, faces, self.mesh_simplify)
+                if self.mesh_smooth > 0:
+                    verts = smooth_mesh(verts, faces, iterations=self.mesh_smooth)
                 att = color_mesh(self.G, w_pivot, verts, self.mesh_res, level=self.mesh_level, grid=grid, cameras=self.mesh_cameras(cam),
                                  **self.synth_kwargs)
                 write_ply(path, verts, faces, normals=att['normals'], colors=att['colors'])
             else:
-                verts, faces = extract_mesh(self.G, w_pivot, res=self.mesh_res, level=self.mesh_level, **clean)
+                verts, faces = extract_mesh(self.G, w_pivot, res=self.mesh_res, level=self.mesh_level, simplify=self.mesh_simplify,
+                                            smooth=self.mesh_smooth, **clean)
                 write_ply(path, verts, faces)
         else:
             grid = density_grid(self.G, w_pivot, res=self.mesh_res)

@@ -2010,6 +2010,134 @@ def grid_keep(vol: torch.Tensor, labels: torch.Tensor, keep_mask: torch.Tensor, 
     return out
 
 
+def _mesh_faces(t: torch.Tensor, what: str, dev) -> torch.Tensor:
+    L.require_cuda(t)
+    if t.dim() != 2 or t.shape[1] != 3 or t.dtype != torch.int32 or not t.is_contiguous():
+        raise L.Eg3dHipError(f'{what} must be contiguous int32 [F, 3], got {tuple(t.shape)} {t.dtype}')
+    if t.device != dev:
+        raise L.Eg3dHipError(f'{what} is on {t.device}, expected {dev}')
+    return t
+
+
+def mesh_simplify(verts: torch.Tensor, faces: torch.Tensor, cell: float, origin=(0.0, 0.0, 0.0)) -> dict:
+    """Vertex clustering (eg3d_simplify_*; specified step by step in include/eg3d_hip.h "Mesh simplification and smoothing"): the vertices
+    verts fp32 [V,3] that fall in one cell of the grid of side `cell` anchored at `origin` become one vertex at their mean; faces int32 [F,3]
+    that collapse, or repeat an earlier face with the same winding, are dropped, and so are clusters no face is left on.  Returns a dict:
+      verts      fp32 [V',3]   in ascending (cell z, y, x) order, the order marching_cubes emits
+      faces      int32 [F',3]  the survivors in their original order, each rotated so that its smallest index comes first (winding kept)
+      vertex_map int32 [V]     the output vertex every input vertex went to, -1 where its cluster was removed
+      clusters   int           occupied cells, before the unreferenced ones are removed
+    A vertex that is not finite or lies outside cells [0, 2^21) of an axis, and a face index outside [0, V), raise.  The result is a function
+    of the input alone (no atomics, fixed summation order).  The sorts and prefix sums between the kernels are torch's; one host synchronise
+    (the flags and the counts)."""
+    cell = float(cell)
+    origin = [float(v) for v in origin]
+    if not (cell > 0.0 and math.isfinite(cell)):
+        raise ValueError(f'mesh_simplify: cell must be positive and finite, got {cell}')
+    if len(origin) != 3 or not all(math.isfinite(v) for v in origin):
+        raise ValueError(f'mesh_simplify: origin must be three finite numbers, got {origin}')
+    verts = _mesh_rows(verts, 'mesh_simplify: verts')
+    dev = verts.device
+    faces = _mesh_faces(faces, 'mesh_simplify: faces', dev)
+    V, F = verts.shape[0], faces.shape[0]
+    i32 = dict(dtype=torch.int32, device=dev)
+    lib, st = L.lib(), L.stream_ptr()
+    flags, keys, heads = torch.empty(2, **i32), torch.empty(V, dtype=torch.int64, device=dev), torch.empty(V, **i32)
+    tri, alive, used = torch.empty((3, F), **i32), torch.empty(F, **i32), torch.empty(V, **i32)
+    vertex_map = torch.empty(V, **i32)
+    p = L.SimplifyParams(verts=verts.data_ptr(), faces=faces.data_ptr(), V=V, F=F, cell=cell, flags=flags.data_ptr(), keys=keys.data_ptr(),
+                         heads=heads.data_ptr(), tri=tri.data_ptr(), alive=alive.data_ptr(), used=used.data_ptr(), vertex_map=vertex_map.data_ptr())
+    p.origin[:] = origin
+    nbytes = C.c_int64(0)
+    L.check(lib.eg3d_simplify_query_workspace(C.byref(p), C.byref(nbytes)), 'simplify_query_workspace')
+    ws = torch.empty(nbytes.value, dtype=torch.uint8, device=dev)
+    p.workspace, p.workspace_bytes = ws.data_ptr(), nbytes.value
+    L.check(lib.eg3d_simplify_keys(C.byref(p), st), 'simplify_keys')
+    skeys, order = torch.sort(keys, stable=True)
+    p.sorted_keys, p.order = skeys.data_ptr(), order.data_ptr()
+    L.check(lib.eg3d_simplify_heads(C.byref(p), st), 'simplify_heads')
+    head_scan = torch.cumsum(heads, 0, dtype=torch.int32)
+    p.head_scan = head_scan.data_ptr()
+    L.check(lib.eg3d_simplify_clusters(C.byref(p), st), 'simplify_clusters')
+    face_order = None
+    for k in (2, 1, 0):                                   # three stable column sorts: lexicographic in (column 0, 1, 2, index), any K
+        idx = torch.sort(tri[k] if face_order is None else tri[k][face_order], stable=True)[1]
+        face_order = idx if face_order is None else face_order[idx]
+    p.face_order = face_order.data_ptr()
+    L.check(lib.eg3d_simplify_mark(C.byref(p), st), 'simplify_mark')
+    alive_scan, used_scan = torch.cumsum(alive, 0, dtype=torch.int32), torch.cumsum(used, 0, dtype=torch.int32)
+    p.alive_scan, p.used_scan = alive_scan.data_ptr(), used_scan.data_ptr()
+    zero = torch.zeros(1, **i32)
+    last = lambda t: t[-1:] if t.numel() else zero      # noqa: E731
+    bad_vertex, bad_face, K, F2, V2 = torch.cat([flags, last(head_scan), last(alive_scan), last(used_scan)]).tolist()
+    if bad_vertex:
+        raise L.Eg3dHipError(f'mesh_simplify: a vertex is not finite or lies outside cells [0, 2^21) of the grid (cell {cell}, origin {origin})')
+    if bad_face:
+        raise L.Eg3dHipError(f'mesh_simplify: a face index lies outside [0, {V})')
+    out_verts, out_faces = torch.empty((V2, 3), dtype=torch.float32, device=dev), torch.empty((F2, 3), **i32)
+    p.out_verts, p.out_vert_capacity = (out_verts.data_ptr() if V2 else None), V2
+    p.out_faces, p.out_face_capacity = (out_faces.data_ptr() if F2 else None), F2
+    L.check(lib.eg3d_simplify_emit(C.byref(p), st), 'simplify_emit')
+    return dict(verts=out_verts, faces=out_faces, vertex_map=vertex_map, clusters=K)
+
+
+def mesh_adjacency(faces: torch.Tensor, V: int):
+    """(rowptr int32 [V+1], cols int32 [nnz], boundary uint8 [V]) of the faces [F,3] (any integer dtype) with indices in [0, V): row i of the CSR holds the
+    distinct j != i that share a face edge with i, ascending; boundary marks the endpoints of undirected edges that occur exactly once among
+    the faces' edges.  Plain torch on integers (sort, unique, searchsorted): the result is unique.  What eg3d_smooth reads."""
+    dev = faces.device
+    f = faces.to(torch.int64)
+    a, b = torch.cat([f[:, 0], f[:, 1], f[:, 2]]), torch.cat([f[:, 1], f[:, 2], f[:, 0]])
+    keep = a != b                                         # a face with a repeated index adds no self-edge
+    lo, hi = torch.minimum(a, b)[keep], torch.maximum(a, b)[keep]
+    ukey, count = torch.unique(lo * V + hi, return_counts=True)
+    lo, hi = torch.div(ukey, V, rounding_mode='floor'), torch.remainder(ukey, V)
+    boundary = torch.zeros(V, dtype=torch.uint8, device=dev)
+    once = count == 1
+    boundary[lo[once]] = 1
+    boundary[hi[once]] = 1
+    dkey = torch.sort(torch.cat([lo * V + hi, hi * V + lo]))[0]       # distinct: (row, column) ascending
+    rows, cols = torch.div(dkey, V, rounding_mode='floor'), torch.remainder(dkey, V).to(torch.int32)
+    if rows.numel() > _INT32_MAX:
+        L.check(-3, f'mesh_adjacency ({rows.numel()} directed edges)')
+    rowptr = torch.searchsorted(rows, torch.arange(V + 1, dtype=torch.int64, device=dev)).to(torch.int32)
+    return rowptr, cols.contiguous(), boundary
+
+
+def mesh_smooth(verts: torch.Tensor, faces: torch.Tensor, iterations: int = 10, lam: float = 0.5, mu: float = -0.53,
+                pin_boundary: bool = True) -> torch.Tensor:
+    """fp32 [V,3]: Taubin lambda|mu smoothing of verts fp32 [V,3] over the edges of faces int32 [F,3] with uniform (umbrella) weights
+    (eg3d_smooth; include/eg3d_hip.h "Mesh simplification and smoothing").  One iteration moves every vertex by lam times its offset from the
+    mean of its neighbours, then by mu times (mu < -lam: the second pass undoes the shrinkage of the first).  pin_boundary keeps the endpoints
+    of edges that belong to one face only where they are.  A vertex without neighbours stays.  iterations=0 returns a copy.  A face index
+    outside [0, V) raises.  The adjacency is built once per call with torch's integer sort / unique (mesh_adjacency: host synchronises there);
+    then 2 * iterations launches with no host synchronise between them.  Jacobi passes with a fixed order of every sum: the result is a
+    function of the input alone."""
+    iterations, lam, mu = int(iterations), float(lam), float(mu)
+    if iterations < 0:
+        raise ValueError(f'mesh_smooth: iterations >= 0, got {iterations}')
+    if not (math.isfinite(lam) and math.isfinite(mu)):
+        raise ValueError(f'mesh_smooth: lam and mu must be finite, got {lam}, {mu}')
+    verts = _mesh_rows(verts, 'mesh_smooth: verts')
+    dev = verts.device
+    faces = _mesh_faces(faces, 'mesh_smooth: faces', dev)
+    V = verts.shape[0]
+    if faces.numel() and bool(((faces < 0) | (faces >= V)).any()):
+        raise L.Eg3dHipError(f'mesh_smooth: a face index lies outside [0, {V})')
+    out = torch.empty_like(verts)
+    p = L.SmoothParams(verts=verts.data_ptr(), out=out.data_ptr(), V=V, iterations=iterations, lam=lam, mu=mu)
+    if iterations > 0 and V > 0:
+        rowptr, cols, boundary = mesh_adjacency(faces, V)
+        p.rowptr, p.cols, p.nnz = rowptr.data_ptr(), (cols.data_ptr() if cols.numel() else None), cols.numel()
+        p.pinned = boundary.data_ptr() if pin_boundary else None
+    nbytes = C.c_int64(0)
+    L.check(L.lib().eg3d_smooth_query_workspace(C.byref(p), C.byref(nbytes)), 'smooth_query_workspace')
+    ws = torch.empty(nbytes.value, dtype=torch.uint8, device=dev)
+    p.workspace, p.workspace_bytes = (ws.data_ptr() if nbytes.value else None), nbytes.value
+    L.check(L.lib().eg3d_smooth(C.byref(p), L.stream_ptr()), 'smooth')
+    return out
+
+
 def _ssim_params(x, y, mode, weights, nonnegative, size_average, win_size, win_sigma, C1, C2):
     N, Ch, Hh, Ww = x.shape
     p = L.SsimParams(x=x.data_ptr(), y=y.data_ptr(), N=N, C=Ch, H=Hh, W=Ww, mode=mode, levels=len(weights), nonnegative=int(bool(nonnegative)),

@@ -17,6 +17,8 @@ G.mapping / ImportanceRenderer.run_model on the gfx950 kernels.
   mesh_to_world, bake_cameras, no reference counterpart (its meshes are bare x y z): per-vertex normals of the density field and vertex colours
   color_mesh, normals_to_mesh     blended from rendered views that see the vertex (hipops.mesh_normals / mesh_bake), for write_ply's optional
                                   nx ny nz / red green blue properties
+  simplify_mesh, smooth_mesh   no reference counterpart (its PLYs carry every marching-cubes triangle): vertex clustering and Taubin
+                                  smoothing of the extracted mesh (hipops.mesh_simplify / mesh_smooth), between marching cubes and the attributes
 
 Differences from the reference that do not change results: the tri-planes of a fixed latent are synthesised once per orbit / per grid
 instead of once per frame / per chunk (the reference re-runs the backbone every time), and grid coordinates are generated per chunk on
@@ -183,20 +185,57 @@ def clean_grid(grid: torch.Tensor, level: float, keep: Optional[int] = 1, min_vo
     return grid_keep(grid, cc['labels'], mask, fill), info
 
 
+def _check_mesh_options(simplify, smooth, what: str) -> None:
+    if simplify is not None and not (float(simplify) > 0.0 and math.isfinite(float(simplify))):
+        raise ValueError(f'{what}: simplify must be a positive finite cell size or None, got {simplify!r}')
+    if int(smooth) < 0:
+        raise ValueError(f'{what}: smooth must be >= 0 iterations, got {smooth!r}')
+
+
+@torch.no_grad()
+def simplify_mesh(verts: torch.Tensor, faces: torch.Tensor, cell: float, origin=(0.0, 0.0, 0.0)):
+    """(verts, faces, info): the mesh with the vertices of every cell of side `cell` (in the vertices' own units: voxels for extract_mesh's
+    output) merged into their mean, collapsed and repeated faces dropped (hipops.mesh_simplify; the inputs are not modified).  Cell 2 leaves
+    about a fifth of a marching-cubes mesh's faces, cell 4 about a seventeenth.  Placement is the members' mean, not a quadric minimiser: the
+    result is reproducible to the bit, and on a marching-cubes mesh, whose vertices already lie on the surface at sub-voxel spacing, the mean
+    stays within the cell's extent of it.  info: clusters (occupied cells), vertex_map (int32 per input vertex, -1 where its cluster went)."""
+    from .hipops import mesh_simplify
+    r = mesh_simplify(verts, faces, cell, origin)
+    return r['verts'], r['faces'], dict(clusters=r['clusters'], vertex_map=r['vertex_map'])
+
+
+@torch.no_grad()
+def smooth_mesh(verts: torch.Tensor, faces: torch.Tensor, iterations: int = 10, lam: float = 0.5, mu: float = -0.53,
+                pin_boundary: bool = True) -> torch.Tensor:
+    """The vertices after `iterations` Taubin lambda|mu iterations over the faces' edges (hipops.mesh_smooth; the input is not modified): the
+    voxel staircase of a marching-cubes mesh goes, the volume stays (the mu pass undoes the lam pass's shrinkage).  Faces are unchanged.
+    pin_boundary keeps the rim of an open mesh where it is."""
+    from .hipops import mesh_smooth
+    return mesh_smooth(verts, faces, iterations=iterations, lam=lam, mu=mu, pin_boundary=pin_boundary)
+
+
 @torch.no_grad()
 def extract_mesh(G, ws: torch.Tensor, res: int = 512, level: float = 10.0, max_batch: int = 1 << 22, attributes: bool = False,
-                 keep: Optional[int] = None, min_voxels: int = 0, connectivity: int = 6, **synthesis_kwargs):
+                 keep: Optional[int] = None, min_voxels: int = 0, connectivity: int = 6, simplify: Optional[float] = None, smooth: int = 0,
+                 smooth_kwargs: Optional[dict] = None, **synthesis_kwargs):
     """(verts fp32 [V,3], faces int32 [F,3]) on the device: density_grid, then marching cubes at `level` in the coordinates of the reference's
     PLY (marching_cubes(np.transpose(grid, (2,1,0)), level, spacing=[1]*3), origin [0,0,0]: voxel units).  Faces are wound so that their
     right-hand normals point out of the dense region.  Triangles may differ from skimage's Lewiner method in ambiguous cubes; vertices do not.
     attributes=True: (verts, faces, normals fp32 [V,3], colors uint8 [V,3]) with color_mesh's defaults on the same grid; verts and faces are
     those of the plain call.  keep / min_voxels / connectivity: clean_grid first (floater removal); with keep=None and min_voxels=0, the
-    default, nothing is labelled and the call is what it was."""
+    default, nothing is labelled and the call is what it was.  simplify (a cell size in voxels) / smooth (Taubin iterations; smooth_kwargs:
+    lam, mu, pin_boundary): simplify_mesh with origin 0, then smooth_mesh, after marching cubes; the attributes are then those of the final
+    vertices (normals and colours are functions of a vertex's position alone).  With simplify=None and smooth=0, the default, neither runs."""
     from .hipops import marching_cubes
+    _check_mesh_options(simplify, smooth, 'extract_mesh')
     grid = density_grid(G, ws, res=res, max_batch=max_batch, **synthesis_kwargs)
     if _wants_cleaning(keep, min_voxels):
         grid = clean_grid(grid, level, keep=keep, min_voxels=min_voxels, connectivity=connectivity)[0]
     verts, faces = marching_cubes(grid, level)
+    if simplify is not None:
+        verts, faces, _ = simplify_mesh(verts, faces, float(simplify))
+    if int(smooth) > 0:
+        verts = smooth_mesh(verts, faces, iterations=int(smooth), **(smooth_kwargs or {}))
     if not attributes:
         return verts, faces
     att = color_mesh(G, ws, verts, res, level=level, grid=grid, **synthesis_kwargs)

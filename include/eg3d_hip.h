@@ -1215,6 +1215,105 @@ int eg3d_cc_finish(const eg3d_cc_params* p, void* stream);
 int eg3d_cc_keep(const eg3d_cc_params* p, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Mesh simplification and smoothing: vertex clustering (Rossignac-Borrel, mean placement) and Taubin lambda|mu passes
+ *   (csrc/mesh_simplify.hip).  No reference counterpart (the reference's PLYs carry every marching-cubes triangle).  One thread per vertex,
+ *   cluster or face; no atomics; every floating-point sum has a fixed order: the outputs are functions of the inputs alone, bit-identical
+ *   between runs and between the two builds.  Exactly these operations in this order, no contraction; tests/support/simplify_ref.py restates
+ *   them in numpy and the outputs are compared bit for bit.  V, F <= INT32_MAX.
+ *
+ * Simplify.  verts fp32 [V][3], faces int32 [F][3], cell fp32 > 0, origin fp32[3].
+ *   1. Cell of vertex v, column k: c_k = floorf(__fdiv_rn(__fsub_rn(v_k, origin_k), cell)).  v is valid when 0 <= c_k < 2^21 for the three
+ *      columns (NaN and the infinities are not).
+ *   2. key(v) = c_2 * 2^42 + c_1 * 2^21 + c_0 (int64; column 2 slowest: the order in which eg3d_mc_emit lays vertices out).
+ *   3. Clusters = the distinct keys in ascending order; id(v) = the rank of key(v); K of them.
+ *   4. Position of a cluster, per column: s = 0.0; for the members in ascending v: s = s + (double)v_k (fp64); (float)(s / (double)n).
+ *   5. Faces: g = id[f].  A face with two equal ids dies.  The triple is rotated so that its smallest id comes first (winding kept).  A face
+ *      dies if a face of lower index survived with the same rotated triple (the oppositely wound triple is another face).  Survivors keep
+ *      their relative order.
+ *   6. Clusters no surviving face references are removed; the others keep ascending key order and are renumbered from 0, and the faces with
+ *      them.  vertex_map int32 [V] = the new index of the vertex's cluster, or -1.
+ *   V = 0 or F = 0 is a normal result (F = 0: no faces, no vertices, vertex_map all -1).
+ *   flags int32[2] on the device: [0] != 0 when a vertex is invalid, [1] != 0 when a face index lies outside [0, V) (such an index is never
+ *   dereferenced; the face dies).  The caller reads them with the counts and discards the result when one is set.
+ *   Protocol (the caller sorts and scans between the entries; every sorted or added value is an integer, so those steps are unique too):
+ *     eg3d_simplify_query_workspace  host only: bytes of the workspace (ids, segment starts, cluster positions), carried from _clusters to _emit
+ *     eg3d_simplify_keys      clears flags; keys[v] = key(v), INT64_MAX for an invalid vertex (flagged)
+ *     (caller: stable ascending sort of keys -> sorted_keys, order: the members of a cluster are adjacent, in ascending v)
+ *     eg3d_simplify_heads     heads[i] = 1 where sorted_keys[i] opens a cluster, else 0
+ *     (caller: head_scan = inclusive prefix sum of heads, int32: rank + 1 of every sorted position; head_scan[V-1] = K)
+ *     eg3d_simplify_clusters  ids and segment starts; one thread per cluster walks its segment (step 4); tri [3][F] (planar: column k of face f
+ *                             at tri[k * F + f]) = the rotated id triples, (-1, -1, -1) for a face with a bad index; alive[f] = 1 unless the
+ *                             face is degenerate or bad; used[0..V) cleared
+ *     (caller: face_order = the faces sorted by (tri column 0, 1, 2, index), e.g. three stable sorts by column 2, 1, 0)
+ *     eg3d_simplify_mark      alive[face_order[j]] = 0 where its triple equals that of face_order[j-1]; then used[g] = 1 for the ids of
+ *                             the faces still alive
+ *     (caller: alive_scan, used_scan = inclusive prefix sums, int32; reads flags, K, F' = alive_scan[F-1], V' = used_scan[V-1]: the one
+ *      synchronise; allocates out_verts [V'][3], out_faces [F'][3])
+ *     eg3d_simplify_emit      out_faces[alive_scan[f] - 1][k] = used_scan[tri_k[f]] - 1 for alive f; out_verts[used_scan[c] - 1] = position
+ *                             of used cluster c; vertex_map.  Never writes beyond the capacities.
+ *   Errors, before any launch: EG3D_ERR_INVALID (null params, V or F < 0, cell <= 0 or not finite, origin not finite [_keys], a null pointer
+ *   among those the entry uses while its count is > 0, short workspace, negative capacity), EG3D_ERR_TOO_LARGE (V, F or a capacity > INT32_MAX).
+ *
+ * Smooth (eg3d_smooth): Taubin smoothing with uniform (umbrella) weights over a CSR adjacency the caller builds once.  rowptr int32 [V+1],
+ *   cols int32 [nnz]: row i = the distinct j != i that share a face edge with i, ascending.  pinned uint8 [V] or NULL: vertices that never move
+ *   (the caller passes the endpoints of edges that occur once among the faces' undirected edges).
+ *   One pass with factor f reads p and writes q (another buffer), per vertex i with n = its row's length and per component:
+ *     s = 0;  for j in row order: s = __fadd_rn(s, p_j);  m = __fdiv_rn(s, (float)n);  d = __fsub_rn(m, p_i);
+ *     q_i = __fadd_rn(p_i, __fmul_rn(f, d));   n = 0 or pinned: q_i = p_i.
+ *   One iteration = a pass with lam, then a pass with mu: 2 * iterations launches between the workspace and out (verts is only read; out must
+ *   not be verts), no host synchronise.  iterations = 0 copies verts to out.  eg3d_smooth_query_workspace, host only: one [V][3] buffer.
+ *   Errors, before any launch: EG3D_ERR_INVALID (null params, V, nnz or iterations < 0, lam or mu not finite, null verts / out or out == verts
+ *   with V > 0, null rowptr, null cols with nnz > 0, short workspace), EG3D_ERR_TOO_LARGE (V or nnz > INT32_MAX).  V = 0: ok, no launch.
+ */
+typedef struct eg3d_simplify_params {
+    const float* verts;                /* [V][3] */
+    const int32_t* faces;              /* [F][3] */
+    int64_t V, F;
+    float cell;
+    float origin[3];
+    int32_t* flags;                    /* device int32[2] */
+    int64_t* keys;                     /* [V]  _keys writes */
+    const int64_t* sorted_keys;        /* [V]  _heads reads */
+    const int64_t* order;              /* [V]  the sort's permutation: sorted_keys[i] = keys[order[i]] */
+    int32_t* heads;                    /* [V] */
+    const int32_t* head_scan;          /* [V] */
+    int32_t* tri;                      /* [3][F] */
+    int32_t* alive;                    /* [F] */
+    const int64_t* face_order;         /* [F] */
+    int32_t* used;                     /* [V] */
+    const int32_t* alive_scan;         /* [F] */
+    const int32_t* used_scan;          /* [V] */
+    void* workspace;                   /* eg3d_simplify_query_workspace's bytes */
+    int64_t workspace_bytes;
+    float* out_verts;                  /* [out_vert_capacity][3] */
+    int64_t out_vert_capacity;
+    int32_t* out_faces;                /* [out_face_capacity][3] */
+    int64_t out_face_capacity;
+    int32_t* vertex_map;               /* [V] */
+} eg3d_simplify_params;
+int eg3d_simplify_query_workspace(const eg3d_simplify_params* p, int64_t* workspace_bytes);
+int eg3d_simplify_keys(const eg3d_simplify_params* p, void* stream);
+int eg3d_simplify_heads(const eg3d_simplify_params* p, void* stream);
+int eg3d_simplify_clusters(const eg3d_simplify_params* p, void* stream);
+int eg3d_simplify_mark(const eg3d_simplify_params* p, void* stream);
+int eg3d_simplify_emit(const eg3d_simplify_params* p, void* stream);
+
+typedef struct eg3d_smooth_params {
+    const float* verts;                /* [V][3] */
+    float* out;                        /* [V][3] */
+    const int32_t* rowptr;             /* [V + 1] */
+    const int32_t* cols;               /* [nnz] */
+    const uint8_t* pinned;             /* [V] or NULL */
+    int64_t V, nnz;
+    int32_t iterations;
+    float lam, mu;
+    void* workspace;                   /* eg3d_smooth_query_workspace's bytes */
+    int64_t workspace_bytes;
+} eg3d_smooth_params;
+int eg3d_smooth_query_workspace(const eg3d_smooth_params* p, int64_t* workspace_bytes);
+int eg3d_smooth(const eg3d_smooth_params* p, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * SSIM / MS-SSIM (reconstruction metrics) -- pytorch_msssim 1.0's ssim / ms_ssim with win=None, as the reference's evaluation calls it
  *   (training/coaches/single_id_coach.py:87-99; csrc/ssim.hip).  x, y: contiguous fp32 [N,C,H,W], any value range.
  *   Gaussian window win[k] = exp(-(k - win_size/2)^2 / (2 sigma^2)) / sum, applied separably (H then W) per channel, valid (no padding).

@@ -3,6 +3,7 @@ convert_sdf_samples_to_ply, shape_utils.py:40-100), on the GPU kernels of this p
 
   python tools/extract_mesh.py --ws pivot_ws.npy --out face.ply [--weights G.safetensors] [--res 512] [--level 10] [--mrc face.mrc]
                                [--colors [--views N_YAW N_PITCH] [--radiance]] [--keep N] [--min-voxels M] [--connectivity {6,26}]
+                               [--simplify CELL] [--smooth N]
 
 --weights: a generator archive (inv3d_amd.weights, tools/convert_eg3d_pickle.py); without it, the full-size synthetic generator
 (inv3d_amd.synthetic, seed --seed).  --ws: a [1, num_ws, w_dim] (or [num_ws, w_dim]) .npy latent, e.g. the reference's {image}_ws.npy.
@@ -11,7 +12,10 @@ convert_sdf_samples_to_ply, shape_utils.py:40-100), on the GPU kernels of this p
 blended from N_YAW x N_PITCH rendered views around the frontal camera (default 5 x 3), or with --radiance the generator's own radiance at the vertices, without rendering.
 --keep N / --min-voxels M remove floaters first (inference.clean_grid; no reference counterpart): only the N largest connected components of
 {sigma > level} that have at least M voxels stay (--connectivity 6: face neighbours, 26: edges and corners too), in the mesh, its colours and the
---mrc grid alike; the components found and kept and the voxels removed are printed.  Without either option nothing is labelled."""
+--mrc grid alike; the components found and kept and the voxels removed are printed.  Without either option nothing is labelled.
+--simplify CELL merges the vertices of every CELL-voxel cell into their mean and drops the faces that collapse (inference.simplify_mesh; no
+reference counterpart): CELL 2 leaves about a fifth of the faces.  --smooth N runs N Taubin iterations over the result
+(inference.smooth_mesh).  With --colors the normals and colours are those of the final vertices.  The counts before and after are printed."""
 import argparse
 import os
 import sys
@@ -39,7 +43,11 @@ def main():
     ap.add_argument('--keep', type=int, default=None, help='keep only the N largest connected components above the level')
     ap.add_argument('--min-voxels', type=int, default=0, help='drop connected components of fewer voxels')
     ap.add_argument('--connectivity', type=int, default=6, choices=(6, 26))
+    ap.add_argument('--simplify', type=float, default=None, metavar='CELL', help='vertex clustering with cells of CELL voxels')
+    ap.add_argument('--smooth', type=int, default=0, metavar='N', help='Taubin smoothing iterations')
     a = ap.parse_args()
+    if (a.simplify is not None and not a.simplify > 0) or a.smooth < 0:
+        ap.error('--simplify takes a positive cell size, --smooth a count >= 0')
     from inv3d_amd import inference as INF
     dev = torch.device('cuda')
     if a.weights:
@@ -66,6 +74,16 @@ def main():
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     note = cleaned
+    if a.simplify is not None or a.smooth > 0:
+        t1 = time.perf_counter()
+        v0, f0 = verts.shape[0], faces.shape[0]
+        if a.simplify is not None:
+            verts, faces, _ = INF.simplify_mesh(verts, faces, a.simplify)
+        if a.smooth > 0:
+            verts = INF.smooth_mesh(verts, faces, iterations=a.smooth)
+        torch.cuda.synchronize()
+        note += (f'; from {v0} vertices, {f0} faces' + (f', cells of {a.simplify:g} voxels' if a.simplify is not None else '')
+                 + (f', {a.smooth} smoothing iterations' if a.smooth > 0 else '') + f' ({(time.perf_counter() - t1) * 1e3:.1f} ms)')
     if a.colors:
         t1 = time.perf_counter()
         cams = INF.bake_cameras(a.views[0], a.views[1], device=dev)

@@ -253,6 +253,15 @@ class MeshBakeParams(C.Structure):
                 ('cos_min', C.c_float), ('power', C.c_int32)]
 
 
+class MeshTextureParams(C.Structure):
+    """eg3d_mesh_texture_params: a per-face texture atlas baked from rendered views (eg3d_mesh_texture)."""
+    _fields_ = [('points', C.c_void_p), ('normals', C.c_void_p), ('faces', C.c_void_p), ('cams', C.c_void_p), ('images', C.c_void_p),
+                ('depth', C.c_void_p), ('mask', C.c_void_p), ('fallback', C.c_void_p), ('texture', C.c_void_p), ('views', C.c_void_p),
+                ('uv', C.c_void_p), ('corner', C.c_void_p), ('bad_faces', C.c_void_p), ('V', C.c_int64), ('F', C.c_int64), ('N', C.c_int32),
+                ('H', C.c_int32), ('R', C.c_int32), ('tile', C.c_int32), ('fill', C.c_int32), ('depth_tol', C.c_float), ('cos_min', C.c_float),
+                ('power', C.c_int32)]
+
+
 class CcParams(C.Structure):
     """eg3d_cc_params: connected components of {vol > level} (eg3d_cc_query_workspace / eg3d_cc_label / eg3d_cc_finish / eg3d_cc_keep)."""
     _fields_ = [('vol', C.c_void_p), ('labels', C.c_void_p), ('D0', C.c_int32), ('D1', C.c_int32), ('D2', C.c_int32), ('level', C.c_float),
@@ -460,6 +469,8 @@ _SIGS = {
     'eg3d_iso_render': (C.c_int, [C.POINTER(IsoParams), C.c_void_p]),
     'eg3d_mesh_normals': (C.c_int, [C.POINTER(MeshNormalsParams), C.c_void_p]),
     'eg3d_mesh_bake': (C.c_int, [C.POINTER(MeshBakeParams), C.c_void_p]),
+    'eg3d_mesh_texture_size': (C.c_int, [C.c_int64, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    'eg3d_mesh_texture': (C.c_int, [C.POINTER(MeshTextureParams), C.c_void_p]),
     'eg3d_cc_query_workspace': (C.c_int, [C.POINTER(CcParams), C.POINTER(C.c_int64)]),
     'eg3d_cc_label': (C.c_int, [C.POINTER(CcParams), C.c_void_p]),
     'eg3d_cc_finish': (C.c_int, [C.POINTER(CcParams), C.c_void_p]),

@@ -32,8 +32,8 @@ import numpy as np
 import torch
 
 from . import dist as D
-from .inference import (bake_cameras, clean_grid, color_mesh, density_grid, estimate_w_stats, extract_mesh, simplify_mesh, smooth_mesh, write_mrc,
-                        write_ply)
+from .inference import (bake_cameras, clean_grid, color_mesh, density_grid, estimate_w_stats, extract_mesh, simplify_mesh, smooth_mesh, texture_mesh,
+                        write_mrc, write_obj, write_ply)
 from .inversion import LatentProjector, PivotalTuner, psnr_01
 from .metrics import IDLoss, format_metrics_txt, reconstruction_metrics
 from .video import pivot_grid, write_orbit_video, write_png
@@ -66,6 +66,7 @@ class InversionCoach:
                  start_w_fn: Optional[Callable[[torch.Tensor], torch.Tensor]] = None, sr_fp16: bool = True, gen_mesh: bool = False,
                  mesh_dir: Optional[str] = None, mesh_res: int = 512, mesh_level: float = 10.0, mesh_format: str = '.mrc', mesh_colors: bool = False,
                  mesh_keep: Optional[int] = None, mesh_min_voxels: int = 0, mesh_simplify: Optional[float] = None, mesh_smooth: int = 0,
+                 mesh_texture_tile: int = 8,
                  do_evaluation: bool = False, eval_dir: Optional[str] = None, lpips_eval_net: Optional[Callable] = None,
                  id_net: Optional[Callable] = None, save_pivot: bool = False, pivot_dir: Optional[str] = None, shape_views: bool = False,
                  save_grid: bool = False, gen_video: bool = False, media_dir: Optional[str] = None, video_quality: int = 90):
@@ -77,14 +78,17 @@ class InversionCoach:
         tied to their standard deviation; `w_stats=(w_avg, w_std)` overrides the estimate, `w_avg_samples=0` starts at w = 0, std 1.
         `gen_mesh` (global_config.gen_mesh): after Phase B write the tuned generator's shape at the pivot latent to
         {mesh_dir}/{name}_pti{mesh_format} like create_geometry(shape_res=mesh_res, shape_format=mesh_format): '.mrc' = the raw density grid,
-        '.ply' = its marching-cubes mesh at `mesh_level` (the reference's level 10).  `mesh_colors` (no reference counterpart; '.ply' only):
+        '.ply' = its marching-cubes mesh at `mesh_level` (the reference's level 10).  `mesh_colors` (no reference counterpart; '.ply', and implied by '.obj'):
         the PLY also carries per-vertex normals and colours (inference.color_mesh with the pivot camera first among the bake views: the view
         the photograph constrains); x y z and the faces are those of the plain file.  `mesh_keep` / `mesh_min_voxels` (no reference
         counterpart): floater removal, inference.clean_grid(keep=, min_voxels=) on the density grid before it is meshed, coloured or written
         ('.mrc' then holds the cleaned grid), and on the grid behind `shape_views`; the defaults leave every file as it was.
-        `mesh_simplify` (a cell size in voxels) / `mesh_smooth` (Taubin iterations; no reference counterpart; '.ply' only): the mesh goes
+        `mesh_simplify` (a cell size in voxels) / `mesh_smooth` (Taubin iterations; no reference counterpart; '.ply' and '.obj'): the mesh goes
         through inference.simplify_mesh, then inference.smooth_mesh, before it is written; with `mesh_colors` the normals and colours are
         those of the final vertices.  None and 0, the defaults, run neither.
+        mesh_format='.obj' (no reference counterpart): {name}_pti.obj, {name}_pti.mtl and {name}_pti.png -- the mesh with normals and a
+        texture atlas baked from the same views (inference.texture_mesh with `mesh_texture_tile` texels per block side, then
+        inference.write_obj); mesh_colors is implied, and mesh_keep / mesh_min_voxels / mesh_simplify / mesh_smooth compose as for '.ply'.
         `do_evaluation` (global_config.do_evaluation): after Phase B render G.synthesis(w_pivot[:, :14], cam[:, :25]) with the tuned generator and
         write metrics.reconstruction_metrics to {eval_dir}/{name}metrics.txt; `lpips_eval_net` (LPIPSAlex) and `id_net` (IDLoss) are built
         once per coach when None.  `save_pivot` writes {pivot_dir}/{name}_ws.npy and {name}_cam.npy; in the reference it only takes effect
@@ -102,13 +106,18 @@ class InversionCoach:
             raise ValueError('do_evaluation needs an eval_dir')
         if save_pivot and not pivot_dir:
             raise ValueError('save_pivot needs a pivot_dir')
-        if mesh_format not in ('.mrc', '.ply'):
-            raise ValueError(f"mesh_format must be '.mrc' or '.ply', got {mesh_format!r}")
+        if mesh_format not in ('.mrc', '.ply', '.obj'):
+            raise ValueError(f"mesh_format must be '.mrc', '.ply' or '.obj', got {mesh_format!r}")
         if gen_mesh and not mesh_dir:
             raise ValueError('gen_mesh needs a mesh_dir')
-        if mesh_colors and mesh_format != '.ply':
-            raise ValueError("mesh_colors needs mesh_format='.ply': an '.mrc' file is the density grid")
-        self.mesh_colors = bool(mesh_colors)
+        if mesh_colors and mesh_format == '.mrc':
+            raise ValueError("mesh_colors needs mesh_format='.ply' or '.obj': an '.mrc' file is the density grid")
+        self.mesh_colors = bool(mesh_colors) or mesh_format == '.obj'
+        if not 4 <= int(mesh_texture_tile) <= 64:
+            raise ValueError(f'mesh_texture_tile must lie in [4, 64], got {mesh_texture_tile!r}')
+        if int(mesh_texture_tile) != 8 and mesh_format != '.obj':
+            raise ValueError("mesh_texture_tile needs mesh_format='.obj': only an '.obj' file carries a texture")
+        self.mesh_texture_tile = int(mesh_texture_tile)
         if mesh_keep is not None and int(mesh_keep) < 0:
             raise ValueError(f'mesh_keep must be >= 0 or None, got {mesh_keep!r}')
         self.mesh_keep, self.mesh_min_voxels = (None if mesh_keep is None else int(mesh_keep)), int(mesh_min_voxels)
@@ -116,8 +125,8 @@ class InversionCoach:
             raise ValueError(f'mesh_simplify must be a positive finite cell size or None, got {mesh_simplify!r}')
         if int(mesh_smooth) < 0:
             raise ValueError(f'mesh_smooth must be >= 0 iterations, got {mesh_smooth!r}')
-        if (mesh_simplify is not None or int(mesh_smooth) > 0) and mesh_format != '.ply':
-            raise ValueError("mesh_simplify / mesh_smooth need mesh_format='.ply': an '.mrc' file is the density grid")
+        if (mesh_simplify is not None or int(mesh_smooth) > 0) and mesh_format == '.mrc':
+            raise ValueError("mesh_simplify / mesh_smooth need mesh_format='.ply' or '.obj': an '.mrc' file is the density grid")
         self.mesh_simplify, self.mesh_smooth = (None if mesh_simplify is None else float(mesh_simplify)), int(mesh_smooth)
         self.gen_mesh, self.mesh_dir, self.mesh_res, self.mesh_level, self.mesh_format = gen_mesh, mesh_dir, int(mesh_res), float(mesh_level), mesh_format
         self.do_evaluation, self.eval_dir, self.save_pivot, self.pivot_dir = do_evaluation, eval_dir, save_pivot, pivot_dir
@@ -264,11 +273,12 @@ class InversionCoach:
 
     def write_mesh(self, name: str, w_pivot: torch.Tensor, cam: Optional[torch.Tensor] = None) -> str:
         """create_geometry(G, w_pivot, outdir=mesh_dir, fname=name + '_pti') with the generator as it is now (the tuned one); with
-        mesh_colors the PLY carries normals and colours baked from `cam` (the pivot camera) and inference.bake_cameras()."""
+        mesh_colors the PLY carries normals and colours baked from `cam` (the pivot camera) and inference.bake_cameras(); '.obj' writes the
+        OBJ (the path returned), its MTL and its PNG atlas baked from the same views."""
         os.makedirs(self.mesh_dir, exist_ok=True)
         path = os.path.join(self.mesh_dir, f'{name}_pti{self.mesh_format}')
         clean = self._clean_kwargs()
-        if self.mesh_format == '.ply':
+        if self.mesh_format in ('.ply', '.obj'):
             if self.mesh_colors:
                 from .hipops import marching_cubes
                 grid = density_grid(self.G, w_pivot, res=self.mesh_res)                  # extract_mesh's two steps, keeping the grid for the bake
@@ -279,6 +289,11 @@ class InversionCoach:
                     verts, faces, _ = simplify_mesh(verts, faces, self.mesh_simplify)
                 if self.mesh_smooth > 0:
                     verts = smooth_mesh(verts, faces, iterations=self.mesh_smooth)
+                if self.mesh_format == '.obj':
+                    att = texture_mesh(self.G, w_pivot, verts, faces, self.mesh_res, level=self.mesh_level, grid=grid, cameras=self.mesh_cameras(cam),
+                                       tile=self.mesh_texture_tile, **self.synth_kwargs)
+                    write_obj(path, verts, faces, att['uv'], att['texture'], normals=att['normals'])
+                    return path
                 att = color_mesh(self.G, w_pivot, verts, self.mesh_res, level=self.mesh_level, grid=grid, cameras=self.mesh_cameras(cam),
                                  **self.synth_kwargs)
                 write_ply(path, verts, faces, normals=att['normals'], colors=att['colors'])

@@ -1908,6 +1908,26 @@ def mesh_normals(vol: torch.Tensor, points: torch.Tensor, origin, spacing, axes=
     return out
 
 
+def _bake_views(what: str, images, depth, mask, cams, dev):
+    """The views of mesh_bake / mesh_texture checked: (F, cams as contiguous fp32)."""
+    L.require_cuda(images, depth, mask, cams)
+    if cams.dim() != 2 or cams.shape[1] != 25 or cams.shape[0] < 1:
+        raise L.Eg3dHipError(f'{what}: cameras [F >= 1, 25], got {tuple(cams.shape)}')
+    F = cams.shape[0]
+    if images.dim() != 4 or images.shape[0] != F or images.shape[1] != 3 or images.shape[2] != images.shape[3] or images.shape[2] < 1 \
+            or images.dtype != torch.float32 or not images.is_contiguous():
+        raise L.Eg3dHipError(f'{what}: images must be contiguous fp32 [{F}, 3, H, H], got {tuple(images.shape)} {images.dtype}')
+    if depth.dim() != 3 or depth.shape[0] != F or depth.shape[1] != depth.shape[2] or depth.shape[1] < 1 or depth.dtype != torch.float32 \
+            or not depth.is_contiguous():
+        raise L.Eg3dHipError(f'{what}: depth must be contiguous fp32 [{F}, R, R], got {tuple(depth.shape)} {depth.dtype}')
+    if tuple(mask.shape) != tuple(depth.shape) or mask.dtype != torch.uint8 or not mask.is_contiguous():
+        raise L.Eg3dHipError(f'{what}: mask must be contiguous uint8 {tuple(depth.shape)}, got {tuple(mask.shape)} {mask.dtype}')
+    for name, t in (('images', images), ('depth', depth), ('mask', mask), ('cams', cams)):
+        if t.device != dev:
+            raise L.Eg3dHipError(f'{what}: {name} is on {t.device}, expected {dev}')
+    return F, cams.to(dtype=torch.float32).contiguous()
+
+
 def mesh_bake(points: torch.Tensor, normals: torch.Tensor, images: torch.Tensor, depth: torch.Tensor, mask: torch.Tensor, cams: torch.Tensor,
               fallback: Optional[torch.Tensor] = None, depth_tol: float = 0.0, cos_min: float = 0.1, power: int = 2) -> dict:
     """Vertex colours from rendered views (eg3d_mesh_bake; specified operation by operation in include/eg3d_hip.h "Mesh attributes").
@@ -1924,24 +1944,9 @@ def mesh_bake(points: torch.Tensor, normals: torch.Tensor, images: torch.Tensor,
     points = _mesh_rows(points, 'mesh_bake: points')
     dev, V = points.device, points.shape[0]
     normals = _mesh_rows(normals, 'mesh_bake: normals', dev, V)
-    L.require_cuda(images, depth, mask, cams)
-    if cams.dim() != 2 or cams.shape[1] != 25 or cams.shape[0] < 1:
-        raise L.Eg3dHipError(f'mesh_bake: cameras [F >= 1, 25], got {tuple(cams.shape)}')
-    F = cams.shape[0]
-    if images.dim() != 4 or images.shape[0] != F or images.shape[1] != 3 or images.shape[2] != images.shape[3] or images.shape[2] < 1 \
-            or images.dtype != torch.float32 or not images.is_contiguous():
-        raise L.Eg3dHipError(f'mesh_bake: images must be contiguous fp32 [{F}, 3, H, H], got {tuple(images.shape)} {images.dtype}')
-    if depth.dim() != 3 or depth.shape[0] != F or depth.shape[1] != depth.shape[2] or depth.shape[1] < 1 or depth.dtype != torch.float32 \
-            or not depth.is_contiguous():
-        raise L.Eg3dHipError(f'mesh_bake: depth must be contiguous fp32 [{F}, R, R], got {tuple(depth.shape)} {depth.dtype}')
-    if tuple(mask.shape) != tuple(depth.shape) or mask.dtype != torch.uint8 or not mask.is_contiguous():
-        raise L.Eg3dHipError(f'mesh_bake: mask must be contiguous uint8 {tuple(depth.shape)}, got {tuple(mask.shape)} {mask.dtype}')
+    F, cams = _bake_views('mesh_bake', images, depth, mask, cams, dev)
     if fallback is not None:
         fallback = _mesh_rows(fallback, 'mesh_bake: fallback', dev, V)
-    for name, t in (('images', images), ('depth', depth), ('mask', mask), ('cams', cams)):
-        if t.device != dev:
-            raise L.Eg3dHipError(f'mesh_bake: {name} is on {t.device}, expected {dev}')
-    cams = cams.to(dtype=torch.float32).contiguous()
     out = dict(color=torch.empty((V, 3), dtype=torch.float32, device=dev), rgb=torch.empty((V, 3), dtype=torch.uint8, device=dev),
                weight=torch.empty((V,), dtype=torch.float32, device=dev), views=torch.empty((V,), dtype=torch.uint8, device=dev))
     p = L.MeshBakeParams(points=points.data_ptr(), normals=normals.data_ptr(), cams=cams.data_ptr(), images=images.data_ptr(), depth=depth.data_ptr(),
@@ -1949,6 +1954,47 @@ def mesh_bake(points: torch.Tensor, normals: torch.Tensor, images: torch.Tensor,
                          rgb=out['rgb'].data_ptr(), weight=out['weight'].data_ptr(), views=out['views'].data_ptr(), V=V, F=F, H=images.shape[2],
                          R=depth.shape[1], depth_tol=float(depth_tol), cos_min=float(cos_min), power=int(power))
     L.check(L.lib().eg3d_mesh_bake(C.byref(p), L.stream_ptr()), 'mesh_bake')
+    return out
+
+
+def mesh_texture(points: torch.Tensor, normals: torch.Tensor, faces: torch.Tensor, images: torch.Tensor, depth: torch.Tensor, mask: torch.Tensor,
+                 cams: torch.Tensor, fallback: Optional[torch.Tensor] = None, tile: int = 8, fill: int = 128, depth_tol: float = 0.0,
+                 cos_min: float = 0.1, power: int = 2) -> dict:
+    """A texture atlas for the mesh (points, normals fp32 [V,3] in world coordinates, faces int32 [F,3]) baked from the rendered views
+    (eg3d_mesh_texture; specified operation by operation in include/eg3d_hip.h "Mesh texture").  Two faces share a tile x tile block of the
+    atlas, one per triangle of its diagonal, the corner opposite a face's longest edge at the right angle; every texel interpolates its
+    face's vertices and goes through mesh_bake's view loop (images, depth, mask, cams, depth_tol, cos_min, power as there; `fallback` [V,3]
+    is interpolated too).  A bilinear lookup inside a face's uv triangle reads only that face's texels.  Returns a dict:
+      texture uint8 [Ht,Wt,3]  (Ht, Wt) = mesh_texture_size(F, tile); texels no face owns hold `fill`
+      views   uint8 [Ht,Wt]    how many views coloured the texel (0: fallback or fill)
+      uv      fp32 [F,3,2]     per face corner, in the faces' own corner order: (u, v) in [0,1] with the origin at the top-left texel
+      corner  uint8 [F]        the face corner that took the right angle
+    The bytes are a function of the inputs alone.  A face index outside [0, V) raises (no such vertex is read).  One launch besides the
+    counter's; one host synchronise (the counter)."""
+    points = _mesh_rows(points, 'mesh_texture: points')
+    dev, V = points.device, points.shape[0]
+    normals = _mesh_rows(normals, 'mesh_texture: normals', dev, V)
+    faces = _mesh_faces(faces, 'mesh_texture: faces', dev)
+    N, cams = _bake_views('mesh_texture', images, depth, mask, cams, dev)
+    if fallback is not None:
+        fallback = _mesh_rows(fallback, 'mesh_texture: fallback', dev, V)
+    if not 4 <= int(tile) <= 64 or not 0 <= int(fill) <= 255:
+        raise L.Eg3dHipError(f'mesh_texture: tile in [4, 64] and fill in [0, 255], got tile = {tile!r}, fill = {fill!r}')
+    F = faces.shape[0]
+    Ht, Wt = mesh_texture_size(F, tile)
+    out = dict(texture=torch.empty((Ht, Wt, 3), dtype=torch.uint8, device=dev), views=torch.empty((Ht, Wt), dtype=torch.uint8, device=dev),
+               uv=torch.empty((F, 3, 2), dtype=torch.float32, device=dev), corner=torch.empty((F,), dtype=torch.uint8, device=dev))
+    bad = torch.empty(1, dtype=torch.int32, device=dev)
+    p = L.MeshTextureParams(points=points.data_ptr(), normals=normals.data_ptr(), faces=faces.data_ptr(), cams=cams.data_ptr(),
+                            images=images.data_ptr(), depth=depth.data_ptr(), mask=mask.data_ptr(),
+                            fallback=None if fallback is None else fallback.data_ptr(), texture=out['texture'].data_ptr(),
+                            views=out['views'].data_ptr(), uv=out['uv'].data_ptr(), corner=out['corner'].data_ptr(), bad_faces=bad.data_ptr(),
+                            V=V, F=F, N=N, H=images.shape[2], R=depth.shape[1], tile=int(tile), fill=int(fill), depth_tol=float(depth_tol),
+                            cos_min=float(cos_min), power=int(power))
+    L.check(L.lib().eg3d_mesh_texture(C.byref(p), L.stream_ptr()), 'mesh_texture')
+    n_bad = int(bad.item())
+    if n_bad:
+        raise L.Eg3dHipError(f'mesh_texture: {n_bad} face(s) with an index outside [0, {V})')
     return out
 
 
@@ -2365,6 +2411,24 @@ def image_grid_size(N: int, H: int, W: int, nrow: int, padding: int = 2):
     xmaps = min(int(nrow), N)
     ymaps = -(-N // xmaps)
     return ymaps * (H + padding) + padding, xmaps * (W + padding) + padding
+
+
+MESH_TEXTURE_MAX_SIDE = 16384
+
+
+def mesh_texture_size(F: int, tile: int = 8):
+    """(Ht, Wt) of mesh_texture's atlas for F faces: two faces per tile x tile block, ceil(sqrt(blocks)) blocks per row (integer arithmetic;
+    eg3d_mesh_texture_size computes the same).  F = 0 gives one block.  A side above 16384 raises."""
+    F, tile = int(F), int(tile)
+    if F < 0 or not 4 <= tile <= 64:
+        raise ValueError(f'mesh_texture_size: F >= 0 and tile in [4, 64], got F = {F}, tile = {tile}')
+    nb = max(-(-F // 2), 1)
+    per_row = math.isqrt(nb - 1) + 1                      # ceil(sqrt(nb)) for nb >= 1
+    Ht, Wt = tile * -(-nb // per_row), tile * per_row
+    if max(Ht, Wt) > MESH_TEXTURE_MAX_SIDE:
+        raise L.Eg3dHipError(f'mesh_texture: {F} faces at tile {tile} need a {Ht} x {Wt} atlas, above {MESH_TEXTURE_MAX_SIDE} a side: '
+                             'simplify the mesh first (simplify_mesh) or lower `tile`')
+    return Ht, Wt
 
 
 def image_grid_u8(img: torch.Tensor, nrow: int, padding: int = 2, pad_value: int = 0) -> torch.Tensor:

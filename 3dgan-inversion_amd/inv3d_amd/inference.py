@@ -19,11 +19,14 @@ G.mapping / ImportanceRenderer.run_model on the gfx950 kernels.
                                   nx ny nz / red green blue properties
   simplify_mesh, smooth_mesh   no reference counterpart (its PLYs carry every marching-cubes triangle): vertex clustering and Taubin
                                   smoothing of the extracted mesh (hipops.mesh_simplify / mesh_smooth), between marching cubes and the attributes
+  texture_mesh, write_obj      no reference counterpart: a per-face texture atlas baked from color_mesh's views (hipops.mesh_texture), so that
+                                  colour resolution no longer follows the vertex count, and the OBJ + MTL + image that carry it
 
 Differences from the reference that do not change results: the tri-planes of a fixed latent are synthesised once per orbit / per grid
 instead of once per frame / per chunk (the reference re-runs the backbone every time), and grid coordinates are generated per chunk on
 the device instead of materialising res^3 x 3 floats on the host."""
 import math
+import os
 import struct
 from typing import Iterator, Optional, Tuple
 
@@ -344,6 +347,50 @@ def _to_u8(color: torch.Tensor) -> torch.Tensor:
 
 
 @torch.no_grad()
+def _mesh_views(G, ws, verts, res, level, grid, cameras, source, depth_tol, keep, min_voxels, connectivity, what, synthesis_kwargs):
+    """What color_mesh and texture_mesh share: (dict(world, world_normals, normals), the radiance fallback [V,3], the rendered views --
+    dict(cams, images, depth, mask, depth_tol) -- or None for source='radiance' and for a mesh without vertices)."""
+    from .hipops import iso_bricks, iso_render, mesh_normals
+    if source not in ('views', 'radiance'):
+        raise ValueError(f"{what}: source 'views' or 'radiance', got {source!r}")
+    res = int(res)
+    if grid is None:
+        grid = density_grid(G, ws, res=res)
+        if _wants_cleaning(keep, min_voxels):
+            grid = clean_grid(grid, level, keep=keep, min_voxels=min_voxels, connectivity=connectivity)[0]
+    if tuple(grid.shape) != (res, res, res):
+        raise ValueError(f'{what}: a {res}^3 density grid, got {tuple(grid.shape)}')
+    dev = grid.device
+    verts = verts.to(dev)
+    origin, spacing, axes = grid_frame(G, res)
+    world, _ = mesh_to_world(G, verts, None, res)
+    V = world.shape[0]
+    world_normals = mesh_normals(grid, world, origin, spacing, axes)
+    out = dict(world=world, world_normals=world_normals, normals=normals_to_mesh(G, world_normals, res))
+    fallback = torch.empty((V, 3), dtype=torch.float32, device=dev)
+    if V:
+        bkw = {k: v for k, v in synthesis_kwargs.items() if k not in ('force_fp32', 'render_uniforms', 'sr_fp16', 'neural_rendering_resolution')}
+        planes = G.backbone.synthesis(ws[:1], noise_mode='const', **bkw)
+        planes = planes.view(1, 3, -1, planes.shape[-2], planes.shape[-1])
+        for head in range(0, V, 1 << 22):
+            rgb = G.renderer.run_model(planes, G.decoder, world[head:head + (1 << 22)].unsqueeze(0), None, G.rendering_kwargs)['rgb']
+            fallback[head:head + (1 << 22)] = rgb.reshape(-1, rgb.shape[-1])[:, :3].float() * 2 - 1
+    if source == 'radiance' or V == 0:
+        return out, fallback, None
+    cams = (bake_cameras(device=dev) if cameras is None else cameras.to(dev)).float().contiguous()
+    kw = dict(noise_mode='const', **synthesis_kwargs)
+    images = None
+    for i in range(cams.shape[0]):
+        img = G.synthesis(ws[:1], cams[i:i + 1], cache_backbone=(i == 0), use_cached_backbone=(i > 0), **kw)['image']
+        if images is None:
+            images = torch.empty((cams.shape[0], *img.shape[1:]), dtype=torch.float32, device=dev)
+        images[i] = img[0]
+    iso = iso_render(grid, cams, images.shape[-1], level, origin, spacing, axes=axes, bricks=iso_bricks(grid))
+    tol = 2.0 * abs(spacing[0]) if depth_tol is None else float(depth_tol)
+    return out, fallback, dict(cams=cams, images=images, depth=iso['depth'], mask=iso['mask'], depth_tol=tol)
+
+
+@torch.no_grad()
 def color_mesh(G, ws: torch.Tensor, verts: torch.Tensor, res: int, level: float = 10.0, grid: Optional[torch.Tensor] = None,
                cameras: Optional[torch.Tensor] = None, source: str = 'views', depth_tol: Optional[float] = None, cos_min: float = 0.1,
                power: int = 2, keep: Optional[int] = None, min_voxels: int = 0, connectivity: int = 6, **synthesis_kwargs) -> dict:
@@ -362,46 +409,51 @@ def color_mesh(G, ws: torch.Tensor, verts: torch.Tensor, res: int, level: float 
     about as wide as a voxel of a 512^3 grid, and the mesh vertex and the marcher's hit differ by interpolation, less than a voxel), not
     tuned on real heads.  keep / min_voxels / connectivity: a grid built here goes through clean_grid first, so that removed floaters neither
     shape the normals nor occlude the views (a grid that is passed in is taken as it is).  Further keywords go to G.synthesis."""
-    from .hipops import iso_bricks, iso_render, mesh_bake, mesh_normals
-    if source not in ('views', 'radiance'):
-        raise ValueError(f"color_mesh: source 'views' or 'radiance', got {source!r}")
-    res = int(res)
-    if grid is None:
-        grid = density_grid(G, ws, res=res)
-        if _wants_cleaning(keep, min_voxels):
-            grid = clean_grid(grid, level, keep=keep, min_voxels=min_voxels, connectivity=connectivity)[0]
-    if tuple(grid.shape) != (res, res, res):
-        raise ValueError(f'color_mesh: a {res}^3 density grid, got {tuple(grid.shape)}')
-    dev = grid.device
-    verts = verts.to(dev)
-    origin, spacing, axes = grid_frame(G, res)
-    world, _ = mesh_to_world(G, verts, None, res)
-    V = world.shape[0]
-    world_normals = mesh_normals(grid, world, origin, spacing, axes)
-    out = dict(world=world, world_normals=world_normals, normals=normals_to_mesh(G, world_normals, res))
-    fallback = torch.empty((V, 3), dtype=torch.float32, device=dev)
-    if V:
-        bkw = {k: v for k, v in synthesis_kwargs.items() if k not in ('force_fp32', 'render_uniforms', 'sr_fp16', 'neural_rendering_resolution')}
-        planes = G.backbone.synthesis(ws[:1], noise_mode='const', **bkw)
-        planes = planes.view(1, 3, -1, planes.shape[-2], planes.shape[-1])
-        for head in range(0, V, 1 << 22):
-            rgb = G.renderer.run_model(planes, G.decoder, world[head:head + (1 << 22)].unsqueeze(0), None, G.rendering_kwargs)['rgb']
-            fallback[head:head + (1 << 22)] = rgb.reshape(-1, rgb.shape[-1])[:, :3].float() * 2 - 1
-    if source == 'radiance' or V == 0:
-        out.update(color=fallback, colors=_to_u8(fallback), views=torch.zeros(V, dtype=torch.uint8, device=dev))
+    from .hipops import mesh_bake
+    out, fallback, views = _mesh_views(G, ws, verts, res, level, grid, cameras, source, depth_tol, keep, min_voxels, connectivity, 'color_mesh',
+                                       synthesis_kwargs)
+    if views is None:
+        out.update(color=fallback, colors=_to_u8(fallback), views=torch.zeros(fallback.shape[0], dtype=torch.uint8, device=fallback.device))
         return out
-    cams = (bake_cameras(device=dev) if cameras is None else cameras.to(dev)).float().contiguous()
-    kw = dict(noise_mode='const', **synthesis_kwargs)
-    images = None
-    for i in range(cams.shape[0]):
-        img = G.synthesis(ws[:1], cams[i:i + 1], cache_backbone=(i == 0), use_cached_backbone=(i > 0), **kw)['image']
-        if images is None:
-            images = torch.empty((cams.shape[0], *img.shape[1:]), dtype=torch.float32, device=dev)
-        images[i] = img[0]
-    iso = iso_render(grid, cams, images.shape[-1], level, origin, spacing, axes=axes, bricks=iso_bricks(grid))
-    tol = 2.0 * abs(spacing[0]) if depth_tol is None else float(depth_tol)
-    baked = mesh_bake(world, world_normals, images, iso['depth'], iso['mask'], cams, fallback=fallback, depth_tol=tol, cos_min=cos_min, power=power)
+    baked = mesh_bake(out['world'], out['world_normals'], views['images'], views['depth'], views['mask'], views['cams'], fallback=fallback,
+                      depth_tol=views['depth_tol'], cos_min=cos_min, power=power)
     out.update(color=baked['color'], colors=baked['rgb'], views=baked['views'])
+    return out
+
+
+@torch.no_grad()
+def texture_mesh(G, ws: torch.Tensor, verts: torch.Tensor, faces: torch.Tensor, res: int, level: float = 10.0, grid: Optional[torch.Tensor] = None,
+                 cameras: Optional[torch.Tensor] = None, tile: int = 8, fill: int = 128, depth_tol: Optional[float] = None, cos_min: float = 0.1,
+                 power: int = 2, keep: Optional[int] = None, min_voxels: int = 0, connectivity: int = 6, **synthesis_kwargs) -> dict:
+    """color_mesh's dict for the mesh (verts [V,3], faces int32 [F,3]) plus a texture atlas baked from the same views:
+      texture       uint8 [Ht,Wt,3]  hipops.mesh_texture's atlas, (Ht, Wt) = hipops.mesh_texture_size(F, tile)
+      uv            fp32 [F,3,2]     per corner of `faces`, in their order; origin at the top-left texel (write_obj flips v)
+      texture_views uint8 [Ht,Wt]    how many views coloured the texel (0: the interpolated radiance fallback, or `fill` where no face lies)
+    The views, depth maps, normals and the per-vertex radiance fallback are color_mesh's, rendered once for both bakes, so the per-vertex
+    results are color_mesh's bit for bit.  A texture keeps the views' detail whatever the vertex count: it is what simplify_mesh's output
+    wants.  Where the voxel -> world map mirrors, the bake runs on mesh_to_world's re-wound faces and uv comes back in the order of `faces`.
+    An atlas side above 16384 raises: simplify first or lower `tile`."""
+    from .hipops import mesh_bake, mesh_texture, mesh_texture_size
+    out, fallback, views = _mesh_views(G, ws, verts, res, level, grid, cameras, 'views', depth_tol, keep, min_voxels, connectivity, 'texture_mesh',
+                                       synthesis_kwargs)
+    dev = fallback.device
+    faces = faces.to(device=dev, dtype=torch.int32).contiguous()
+    F = faces.shape[0]
+    if views is None:                                     # no vertices: nothing was rendered
+        if F:
+            raise ValueError(f'texture_mesh: {F} faces without vertices')
+        Ht, Wt = mesh_texture_size(0, tile)
+        out.update(color=fallback, colors=_to_u8(fallback), views=torch.zeros(0, dtype=torch.uint8, device=dev),
+                   texture=torch.full((Ht, Wt, 3), int(fill), dtype=torch.uint8, device=dev), uv=torch.zeros((0, 3, 2), device=dev),
+                   texture_views=torch.zeros((Ht, Wt), dtype=torch.uint8, device=dev))
+        return out
+    kw = dict(fallback=fallback, depth_tol=views['depth_tol'], cos_min=cos_min, power=power)
+    baked = mesh_bake(out['world'], out['world_normals'], views['images'], views['depth'], views['mask'], views['cams'], **kw)
+    wfaces = mesh_to_world(G, verts, faces, int(res))[1]
+    tex = mesh_texture(out['world'], out['world_normals'], wfaces, views['images'], views['depth'], views['mask'], views['cams'], tile=tile, fill=fill,
+                       **kw)
+    uv = tex['uv'] if wfaces is faces else tex['uv'][:, [0, 2, 1]].contiguous()
+    out.update(color=baked['color'], colors=baked['rgb'], views=baked['views'], texture=tex['texture'], uv=uv, texture_views=tex['views'])
     return out
 
 
@@ -441,6 +493,68 @@ def write_ply(path: str, verts, faces, normals=None, colors=None) -> None:
         fh.write(header.encode('ascii'))
         fh.write(vrec.tobytes())
         fh.write(rec.tobytes())
+
+
+def _obj_rows(tag: str, a: np.ndarray) -> str:
+    fmt = tag + ' %.9g' * a.shape[1]                      # 9 significant digits: an fp32 value reads back as itself
+    return ''.join(fmt % tuple(r) + '\n' for r in a.tolist())
+
+
+def write_obj(path: str, verts, faces, uv, texture, normals=None, texture_format: str = 'png') -> tuple:
+    """Wavefront OBJ + MTL + image for a textured mesh (texture_mesh's verts, faces, 'uv' and 'texture').  Three files: `path` (the OBJ),
+    and beside it stem.mtl and stem.png / stem.jpg with path's stem.  Returns the three paths.
+      OBJ  'mtllib stem.mtl', 'usemtl stem', V lines 'v x y z' (the vertices as given: the frame of write_ply, so the two files overlay),
+           V lines 'vn' when normals [V,3] are given, 3 F lines 'vt u v' (three per face, v = 1 - uv's: OBJ's origin is bottom-left), and
+           F lines 'f a/ta/na b/tb/nb c/tc/nc' ('f a/ta ...' without normals), indices from 1.
+      MTL  'newmtl stem', 'Kd 1 1 1', 'map_Kd' with the image's base name.
+      image  texture uint8 [Ht,Wt,3]: 'png' through video.write_png (lossless: the atlas bytes), 'jpg' through hipops.jpeg_encode on the
+           GPU at 4:4:4 (chroma subsampling would smear neighbouring faces' texels into each other)."""
+    if texture_format not in ('png', 'jpg'):
+        raise ValueError(f"write_obj: texture_format 'png' or 'jpg', got {texture_format!r}")
+    v = _host(verts, np.float32).reshape(-1, 3)
+    f = _host(faces, np.int32).reshape(-1, 3)
+    t = _host(uv, np.float32).reshape(-1, 3, 2)
+    if len(t) != len(f):
+        raise ValueError(f'write_obj: {len(t)} uv rows for {len(f)} faces')
+    n = None if normals is None else _host(normals, np.float32).reshape(-1, 3)
+    if n is not None and len(n) != len(v):
+        raise ValueError(f'write_obj: {len(n)} normals for {len(v)} vertices')
+    if len(f) and (f.min() < 0 or f.max() >= len(v)):
+        raise ValueError(f'write_obj: a face index outside [0, {len(v)})')
+    tex = texture if isinstance(texture, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(texture))
+    if tex.dim() != 3 or tex.shape[2] != 3 or tex.dtype != torch.uint8:
+        raise ValueError(f'write_obj: texture uint8 [Ht,Wt,3], got {tuple(tex.shape)} {tex.dtype}')
+    base = os.path.splitext(path)[0]
+    stem = os.path.basename(base)
+    mtl_path, img_path = base + '.mtl', f'{base}.{texture_format}'
+    if texture_format == 'png':
+        from .video import write_png
+        write_png(img_path, tex)
+    else:
+        from .hipops import jpeg_encode
+        data, offsets = jpeg_encode((tex if tex.is_cuda else tex.cuda()).permute(2, 0, 1).unsqueeze(0).contiguous(), subsampling='444')
+        with open(img_path, 'wb') as fh:
+            fh.write(data[int(offsets[0]):int(offsets[1])].cpu().numpy().tobytes())
+    with open(mtl_path, 'w') as fh:
+        fh.write(f'newmtl {stem}\nKd 1 1 1\nmap_Kd {os.path.basename(img_path)}\n')
+    vt = t.reshape(-1, 2).astype(np.float64)
+    vt[:, 1] = 1.0 - vt[:, 1]
+    a = f.astype(np.int64) + 1
+    ti = np.arange(1, 3 * len(f) + 1, dtype=np.int64).reshape(-1, 3)
+    if n is None:
+        rows = np.stack([a[:, 0], ti[:, 0], a[:, 1], ti[:, 1], a[:, 2], ti[:, 2]], 1)
+        ffmt = 'f %d/%d %d/%d %d/%d\n'
+    else:
+        rows = np.stack([a[:, 0], ti[:, 0], a[:, 0], a[:, 1], ti[:, 1], a[:, 1], a[:, 2], ti[:, 2], a[:, 2]], 1)
+        ffmt = 'f %d/%d/%d %d/%d/%d %d/%d/%d\n'
+    with open(path, 'w') as fh:
+        fh.write(f'mtllib {os.path.basename(mtl_path)}\nusemtl {stem}\n')
+        fh.write(_obj_rows('v', v))
+        if n is not None:
+            fh.write(_obj_rows('vn', n))
+        fh.write(_obj_rows('vt', vt))
+        fh.write(''.join(ffmt % tuple(r) for r in rows.tolist()))
+    return path, mtl_path, img_path
 
 
 def write_mrc(path: str, grid) -> None:

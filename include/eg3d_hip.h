@@ -1149,6 +1149,67 @@ int eg3d_mesh_normals(const eg3d_mesh_normals_params* p, void* stream);
 int eg3d_mesh_bake(const eg3d_mesh_bake_params* p, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Mesh texture: a per-face texture atlas baked from the views (csrc/mesh_bake.hip, beside the vertex bake whose view loop it calls).  No
+ *   reference counterpart.  One thread per texel, every texel a function of its own face: bit-identical between runs and between the two
+ *   builds.  Exactly these fp32 operations in this order, no contraction; tests/support/texture_ref.py restates them in numpy and the outputs
+ *   are compared bit for bit.  V vertices, F faces (int32 [F][3]), N views; T = tile, an integer in [4, 64].
+ *
+ * Layout (eg3d_mesh_texture_size, host only).  Faces 2b and 2b + 1 share block b, a T x T square of texels.  nb = max(ceil(F / 2), 1);
+ *   per_row = ceil(sqrt(nb)) (integers);  Wt = T * per_row;  Ht = T * ceil(nb / per_row).  Block b sits at column b % per_row, row
+ *   b / per_row of the atlas; texel (i, j) of a block (i along x, j along y, origin top-left) is atlas texel (x, y) = (T * column + i,
+ *   T * row + j).  The even face (lower) owns the texels with i + j <= T - 1, the odd face (upper) those with i + j >= T.  A texel whose
+ *   face index is >= F (the upper half of a last block, F = 0) holds `fill` in its three channels and 0 views.
+ * Corner order.  Corner k of a face has vertex index f_k and position v_k.  e_0 = |v_2 - v_1|^2, e_1 = |v_0 - v_2|^2, e_2 = |v_1 - v_0|^2,
+ *   each (dx*dx + dy*dy) + dz*dz of the component differences (the edge opposite corner k).  r = 0;  r = 1 if e_1 > e_r;  r = 2 if e_2 > e_r
+ *   (a NaN compares false; ties keep the lower corner).  A_0, A_1, A_2 = corners r, (r + 1) % 3, (r + 2) % 3: cyclic, the winding is kept,
+ *   and the corner opposite the longest edge takes the right angle of the texel triangle.
+ * Texel triangle (block-local texel centres): lower A_0 (0, 0), A_1 (T - 2, 0), A_2 (0, T - 2); upper A_0 (T - 1, T - 1), A_1 (2, T - 1),
+ *   A_2 (T - 1, 2).  A bilinear lookup inside a face's triangle (edges included) reads only texels the face owns.
+ * Per texel.  Lower: b_1 = float(i) / float(T - 2), b_2 = float(j) / float(T - 2).  Upper: b_1 = float(T - 1 - i) / float(T - 3),
+ *   b_2 = float(T - 1 - j) / float(T - 3).  b_0 = (1 - b_1) - b_2 (negative on the owned texels beyond the hypotenuse: extrapolation in the
+ *   face's plane, so no dilation pass).  Position, normal (not renormalised) and fallback colour, per component: (b_0 A_0 + b_1 A_1) + b_2 A_2
+ *   of the three vertices' values.  The point and normal go through steps 1-5 of eg3d_mesh_bake's view loop (the same device function);
+ *   colour = acc_j / wsum when wsum > 0, else the interpolated fallback (0 without one);  texture = uint8(int(min(max(colour * 127.5 + 128,
+ *   0), 255)));  views = the loop's count.  At a triangle corner of a face with finite vertices b is (1, 0, 0), (0, 1, 0) or (0, 0, 1)
+ *   and the texel is eg3d_mesh_bake's rgb and views of that vertex.
+ * uv [F][3][2]: for corner k of face f in the face's ORIGINAL order, with (x, y) the atlas texel of the triangle corner it was rotated to
+ *   (corner k is A_((k - r) mod 3)):  u = (float(x) + 0.5) / float(Wt),  v = (float(y) + 0.5) / float(Ht);  origin top-left.
+ *   corner uint8 [F] = r.
+ * A face with an index outside [0, V): no vertex of it is read; its texels hold `fill` and 0 views, r = 0 (uv as for r = 0), and
+ *   *bad_faces (device int32, cleared by a launch on the same stream, may be NULL) counts such faces -- an integer atomic add on this path
+ *   only; no output depends on it.  The caller reads it with one synchronise and discards the result when it is not 0.
+ * Outputs (each may be NULL and is then left alone): texture uint8 [Ht][Wt][3], views uint8 [Ht][Wt], uv, corner.  With all of them and
+ *   bad_faces NULL: ok, no launch.  Otherwise one launch over the Ht * Wt texels (plus the counter's), F = 0 included.
+ * Errors, before any launch: EG3D_ERR_INVALID (null params / cams / images / depth / mask, null points / normals with V > 0, null faces with
+ *   F > 0, V or F < 0, N, H or R < 1, depth_tol negative or not finite, cos_min outside [0, 1), power outside 1..8, tile outside [4, 64],
+ *   fill outside 0..255), EG3D_ERR_UNSUPPORTED (N > 255, H or R > 16384, an atlas side above 16384), EG3D_ERR_TOO_LARGE (V or F >= 2^31).
+ */
+typedef struct eg3d_mesh_texture_params {
+    const float* points;               /* [V][3] world */
+    const float* normals;              /* [V][3] world */
+    const int32_t* faces;              /* [F][3] */
+    const float* cams;                 /* [N][25] */
+    const float* images;               /* [N][3][H][H] */
+    const float* depth;                /* [N][R][R] */
+    const uint8_t* mask;               /* [N][R][R] */
+    const float* fallback;             /* [V][3] or NULL */
+    uint8_t* texture;                  /* [Ht][Wt][3] or NULL */
+    uint8_t* views;                    /* [Ht][Wt] or NULL */
+    float* uv;                         /* [F][3][2] or NULL */
+    uint8_t* corner;                   /* [F] or NULL */
+    int32_t* bad_faces;                /* device int32[1] or NULL */
+    int64_t V, F;
+    int32_t N, H, R;
+    int32_t tile;                      /* 4..64 */
+    int32_t fill;                      /* 0..255 */
+    float depth_tol;                   /* world units, >= 0 */
+    float cos_min;                     /* in [0, 1) */
+    int32_t power;                     /* 1..8 */
+} eg3d_mesh_texture_params;
+int eg3d_mesh_texture_size(int64_t F, int32_t tile, int32_t* Ht, int32_t* Wt);
+int eg3d_mesh_texture(const eg3d_mesh_texture_params* p, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Grid components: connected-component labelling of {vol > level} and removal of components (csrc/grid_components.hip).  No reference
  *   counterpart (the reference exports every blob above the level).  tests/support/cc_ref.py restates the result in numpy; the outputs are
  *   compared exactly.

@@ -3,7 +3,7 @@ convert_sdf_samples_to_ply, shape_utils.py:40-100), on the GPU kernels of this p
 
   python tools/extract_mesh.py --ws pivot_ws.npy --out face.ply [--weights G.safetensors] [--res 512] [--level 10] [--mrc face.mrc]
                                [--colors [--views N_YAW N_PITCH] [--radiance]] [--keep N] [--min-voxels M] [--connectivity {6,26}]
-                               [--simplify CELL] [--smooth N]
+                               [--simplify CELL] [--smooth N] [--obj [--tile T] [--texture-format {png,jpg}]]
 
 --weights: a generator archive (inv3d_amd.weights, tools/convert_eg3d_pickle.py); without it, the full-size synthetic generator
 (inv3d_amd.synthetic, seed --seed).  --ws: a [1, num_ws, w_dim] (or [num_ws, w_dim]) .npy latent, e.g. the reference's {image}_ws.npy.
@@ -15,7 +15,11 @@ blended from N_YAW x N_PITCH rendered views around the frontal camera (default 5
 --mrc grid alike; the components found and kept and the voxels removed are printed.  Without either option nothing is labelled.
 --simplify CELL merges the vertices of every CELL-voxel cell into their mean and drops the faces that collapse (inference.simplify_mesh; no
 reference counterpart): CELL 2 leaves about a fifth of the faces.  --smooth N runs N Taubin iterations over the result
-(inference.smooth_mesh).  With --colors the normals and colours are those of the final vertices.  The counts before and after are printed."""
+(inference.smooth_mesh).  With --colors the normals and colours are those of the final vertices.  The counts before and after are printed.
+--obj writes a textured mesh instead of a PLY (inference.texture_mesh / write_obj; no reference counterpart): --out names the .obj, and its
+.mtl and .png (or .jpg) land beside it.  Two faces share a block of T x T texels (--tile, default 8) baked from the same views as --colors;
+a mesh that is too large for a 16384-texel atlas side wants --simplify first.  The atlas size and the share of its texels coloured from
+views are printed."""
 import argparse
 import os
 import sys
@@ -45,9 +49,14 @@ def main():
     ap.add_argument('--connectivity', type=int, default=6, choices=(6, 26))
     ap.add_argument('--simplify', type=float, default=None, metavar='CELL', help='vertex clustering with cells of CELL voxels')
     ap.add_argument('--smooth', type=int, default=0, metavar='N', help='Taubin smoothing iterations')
+    ap.add_argument('--obj', action='store_true', help='write --out as an OBJ with an MTL and a texture atlas beside it')
+    ap.add_argument('--tile', type=int, default=8, metavar='T', help='texels per side of the block two faces share (4..64)')
+    ap.add_argument('--texture-format', default='png', choices=('png', 'jpg'))
     a = ap.parse_args()
     if (a.simplify is not None and not a.simplify > 0) or a.smooth < 0:
         ap.error('--simplify takes a positive cell size, --smooth a count >= 0')
+    if not 4 <= a.tile <= 64 or (a.obj and a.radiance):
+        ap.error('--tile takes 4..64; --obj bakes from views, not with --radiance')
     from inv3d_amd import inference as INF
     dev = torch.device('cuda')
     if a.weights:
@@ -84,7 +93,18 @@ def main():
         torch.cuda.synchronize()
         note += (f'; from {v0} vertices, {f0} faces' + (f', cells of {a.simplify:g} voxels' if a.simplify is not None else '')
                  + (f', {a.smooth} smoothing iterations' if a.smooth > 0 else '') + f' ({(time.perf_counter() - t1) * 1e3:.1f} ms)')
-    if a.colors:
+    if a.obj:
+        t1 = time.perf_counter()
+        cams = INF.bake_cameras(a.views[0], a.views[1], device=dev)
+        att = INF.texture_mesh(G, ws, verts, faces, a.res, level=a.level, grid=grid, cameras=cams, tile=a.tile)
+        torch.cuda.synchronize()
+        paths = INF.write_obj(a.out, verts, faces, att['uv'], att['texture'], normals=att['normals'], texture_format=a.texture_format)
+        Ht, Wt = att['texture'].shape[:2]
+        nf = faces.shape[0]
+        seen, owned = int((att['texture_views'] > 0).sum()), (nf // 2) * a.tile * a.tile + (nf % 2) * a.tile * (a.tile + 1) // 2
+        note += (f'; normals + texture {(time.perf_counter() - t1) * 1e3:.1f} ms, atlas {Ht} x {Wt} ({os.path.basename(paths[2])}), '
+                 f'{seen} of {owned} owned texels ({100.0 * seen / max(owned, 1):.1f} %) coloured from {cams.shape[0]} views')
+    elif a.colors:
         t1 = time.perf_counter()
         cams = INF.bake_cameras(a.views[0], a.views[1], device=dev)
         att = INF.color_mesh(G, ws, verts, a.res, level=a.level, grid=grid, cameras=cams, source='radiance' if a.radiance else 'views')

@@ -10,6 +10,14 @@
 //                                           (integer histograms: LDS, then one integer add per bin and workgroup)
 //   fpad_final                              second blend towards the median, round half to even, uint8
 //   u8_to_target_kernel                     (v / 255 - 0.5) / 0.5, NHWC -> NCHW
+// and the way back (eg3d_paste_back8; no reference counterpart, the reference's alignment goes one way only):
+//   paste_back_kernel                       N edited aligned frames blended into the one photograph they share: one thread per (frame, photo
+//                                           pixel of the region), a wave along 64 pixels of a photo row; the affine map photo -> aligned frame,
+//                                           quad_warp_kernel's bilinear taps (not truncated), a smoothstep feather from the frame's edge, an
+//                                           optional mask through the same taps, round half to even -- fp64, the header's operation order,
+//                                           no division; HWC or planar output (the JPEG encoder's input), the region alone or inside the photo
+//   photo_frames_kernel / photo_frames16    the photo into every frame before the region is written (whole = 1): bytes (also HWC -> planes),
+//                                           or 16 bytes per thread where the buffers allow
 // Integer atomics only (order-independent) and no floating-point sum across threads: both builds and every batch size give the same bytes.
 // The translation unit is compiled with -ffp-contract=off (Makefile): every product and sum below is its own rounded operation.
 #include "common.h"
@@ -359,7 +367,126 @@ __global__ void __launch_bounds__(256) u8_to_target_kernel(const uint8_t* __rest
     out[i] = (v / 255.f - 0.5f) / 0.5f;                                          // IEEE division (HIP's default): not v * (1 / 255)
 }
 
+// ---------------------------------------------------------------------------------------------------------------- paste-back
+struct PasteGeom {
+    double m[6];
+    double inv_feather, inv255;          // host doubles: no division on the device
+    int64_t mask_stride;                 // bytes between the masks of two frames; 0: one mask for all
+    int32_t Wp, S;
+    int32_t x0, y0, rw, rh;              // the region in the photo
+    int32_t Ho, Wo, ox, oy;              // a frame of dst and where the region starts in it
+    int32_t chw;
+};
+
+// grid (ceil(total / 256), N): frame n of dst = the photo, its [total] bytes as they are (ch = 1) or its ch planes one after the other
+__global__ void __launch_bounds__(256) photo_frames_kernel(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst, int64_t hw, int ch) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x, total = hw * ch;  // output index [c][pixel]
+    if (i >= total) return;
+    int64_t j = i;
+    if (ch > 1) {
+        const int64_t c = i / hw;
+        j = (i - c * hw) * ch + c;
+    }
+    dst[(int64_t)blockIdx.y * total + i] = src[j];
+}
+
+// the same copy, 16 bytes per thread: grid (ceil(n16 / 256), N); both buffers 16-byte aligned and the photo a multiple of 16 bytes
+__global__ void __launch_bounds__(256) photo_frames16_kernel(const uint4* __restrict__ src, uint4* __restrict__ dst, int64_t n16) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < n16) dst[(int64_t)blockIdx.y * n16 + i] = src[i];
+}
+
+// grid (ceil(rw / 64), ceil(rh / 4), N), block 256: a wave along 64 photo pixels of a row, one thread per (frame, region pixel)
+template <int CH>
+__global__ void __launch_bounds__(256) paste_back_kernel(const uint8_t* __restrict__ photo, const uint8_t* __restrict__ edits,
+                                                         const uint8_t* __restrict__ mask, uint8_t* __restrict__ dst, PasteGeom g) {
+    const int rx = blockIdx.x * 64 + (threadIdx.x & 63), ry = blockIdx.y * 4 + (threadIdx.x >> 6), n = blockIdx.z;
+    if (rx >= g.rw || ry >= g.rh) return;
+    const int X = g.x0 + rx, Y = g.y0 + ry, S = g.S;
+    const uint8_t* ph = photo + ((int64_t)Y * g.Wp + X) * CH;
+    const int64_t plane = (int64_t)g.Ho * g.Wo, pix = (int64_t)(g.oy + ry) * g.Wo + (g.ox + rx);
+    uint8_t* o = dst + (int64_t)n * plane * CH + (g.chw ? pix : pix * CH);
+    const int64_t cs = g.chw ? plane : 1;
+    const double Xc = X + 0.5, Yc = Y + 0.5, Sd = (double)S;
+    const double u = g.m[0] + g.m[1] * Xc + g.m[2] * Yc;                          // left to right, every operation rounded on its own
+    const double v = g.m[3] + g.m[4] * Xc + g.m[5] * Yc;
+    if (!(u >= 0.0 && u < Sd && v >= 0.0 && v < Sd)) {                           // outside the aligned frame (or NaN): the photo's pixel
+#pragma unroll
+        for (int c = 0; c < CH; ++c) o[c * cs] = ph[c];
+        return;
+    }
+    const double xin = u - 0.5, yin = v - 0.5;
+    const double fxd = floor(xin), fyd = floor(yin);
+    const double dx = xin - fxd, dy = yin - fyd;
+    const int fx = (int)fxd, fy = (int)fyd;                                     // within [-1, S - 1]
+    const int xa = min(max(fx, 0), S - 1), xb = min(max(fx + 1, 0), S - 1);
+    const int ya = min(max(fy, 0), S - 1), yb = min(max(fy + 1, 0), S - 1);
+    const double d = fmin(fmin(u, Sd - u), fmin(v, Sd - v));
+    const double f = g.inv_feather > 0.0 ? fmin(d * g.inv_feather, 1.0) : 1.0;
+    double a = (f * f) * (3.0 - 2.0 * f);
+    if (mask != nullptr) {
+        const uint8_t* mk = mask + (int64_t)n * g.mask_stride;
+        const double p00 = mk[(int64_t)ya * S + xa], p01 = mk[(int64_t)ya * S + xb], p10 = mk[(int64_t)yb * S + xa], p11 = mk[(int64_t)yb * S + xb];
+        const double r0 = p00 + (p01 - p00) * dx;
+        const double r1 = p10 + (p11 - p10) * dx;
+        a = a * ((r0 + (r1 - r0) * dy) * g.inv255);
+    }
+    const uint8_t* ra = edits + (((int64_t)n * S + ya) * S) * CH;
+    const uint8_t* rb = edits + (((int64_t)n * S + yb) * S) * CH;
+#pragma unroll
+    for (int c = 0; c < CH; ++c) {
+        const double p00 = ra[xa * CH + c], p01 = ra[xb * CH + c], p10 = rb[xa * CH + c], p11 = rb[xb * CH + c];
+        const double r0 = p00 + (p01 - p00) * dx;
+        const double r1 = p10 + (p11 - p10) * dx;
+        const double val = r0 + (r1 - r0) * dy;
+        const double pv = ph[c];
+        const double r = rint(pv + (val - pv) * a);                               // round half to even
+        o[c * cs] = (uint8_t)(int)fmin(fmax(r, 0.0), 255.0);                      // a can pass 1 by a rounding: stay inside the byte
+    }
+}
+
 }  // namespace
+
+extern "C" int eg3d_paste_back8(const eg3d_paste_back8_params* p, void* stream) {
+    if (p == nullptr || p->photo == nullptr || p->edits == nullptr || p->dst == nullptr) return EG3D_ERR_INVALID;
+    if (!img_dims_ok(p->N, p->Hp, p->Wp, p->C) || !img_dims_ok(p->N, p->S, p->S, p->C)) return EG3D_ERR_INVALID;
+    if (p->x0 < 0 || p->y0 < 0 || p->x1 < p->x0 || p->y1 < p->y0 || p->x1 > p->Wp || p->y1 > p->Hp) return EG3D_ERR_INVALID;
+    if (p->layout != EG3D_PASTE_HWC && p->layout != EG3D_PASTE_CHW) return EG3D_ERR_INVALID;
+    if (p->mask != nullptr && p->mask_frames != 1 && p->mask_frames != p->N) return EG3D_ERR_INVALID;
+    if (!(p->inv_feather >= 0.0)) return EG3D_ERR_INVALID;
+    hipStream_t st = (hipStream_t)stream;
+    const int chw = p->layout == EG3D_PASTE_CHW;
+    if (p->whole) {
+        const int64_t hw = (int64_t)p->Hp * p->Wp, total = hw * p->C;
+        const bool planes = chw && p->C > 1;                                     // one launch for the N frames (copy_bytes_kernel fills one buffer)
+        const bool wide = !planes && total % 16 == 0 && ((reinterpret_cast<uintptr_t>(p->photo) | reinterpret_cast<uintptr_t>(p->dst)) & 15) == 0;
+        if (wide)
+            hipLaunchKernelGGL(photo_frames16_kernel, dim3((unsigned)((total / 16 + 255) / 256), (unsigned)p->N), dim3(256), 0, st,
+                               reinterpret_cast<const uint4*>(p->photo), reinterpret_cast<uint4*>(p->dst), total / 16);
+        else
+            hipLaunchKernelGGL(photo_frames_kernel, dim3((unsigned)((total + 255) / 256), (unsigned)p->N), dim3(256), 0, st, p->photo, p->dst,
+                               planes ? hw : total, planes ? p->C : 1);
+        EG3D_LAUNCH_CHECK();
+    }
+    PasteGeom g;
+    for (int i = 0; i < 6; ++i) g.m[i] = p->m[i];
+    g.inv_feather = p->inv_feather;
+    g.inv255 = 1.0 / 255.0;
+    g.mask_stride = p->mask != nullptr && p->mask_frames > 1 ? (int64_t)p->S * p->S : 0;
+    g.Wp = p->Wp; g.S = p->S;
+    g.x0 = p->x0; g.y0 = p->y0; g.rw = p->x1 - p->x0; g.rh = p->y1 - p->y0;
+    g.Ho = p->whole ? p->Hp : g.rh; g.Wo = p->whole ? p->Wp : g.rw;
+    g.ox = p->whole ? p->x0 : 0; g.oy = p->whole ? p->y0 : 0;
+    g.chw = chw;
+    if (g.rw == 0 || g.rh == 0) return EG3D_OK;
+    const dim3 grid((unsigned)((g.rw + 63) / 64), (unsigned)((g.rh + 3) / 4), (unsigned)p->N);
+    if (p->C == 3)
+        hipLaunchKernelGGL(paste_back_kernel<3>, grid, dim3(256), 0, st, p->photo, p->edits, p->mask, p->dst, g);
+    else
+        hipLaunchKernelGGL(paste_back_kernel<1>, grid, dim3(256), 0, st, p->photo, p->edits, p->mask, p->dst, g);
+    EG3D_LAUNCH_CHECK();
+    return EG3D_OK;
+}
 
 extern "C" int eg3d_resample8_query_workspace(const eg3d_resample8_params* p, int64_t* workspace_bytes) {
     if (workspace_bytes == nullptr) return EG3D_ERR_INVALID;

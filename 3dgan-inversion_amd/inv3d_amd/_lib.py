@@ -341,6 +341,17 @@ class FeatherPadParams(C.Structure):
                 ('N', C.c_int32), ('H', C.c_int32), ('W', C.c_int32), ('C', C.c_int32), ('left', C.c_int32), ('top', C.c_int32),
                 ('right', C.c_int32), ('bottom', C.c_int32), ('radius', C.c_int32)]
 
+
+class PasteBack8Params(C.Structure):
+    """eg3d_paste_back8_params: edited aligned frames blended into the source photograph (eg3d_paste_back8)."""
+    _fields_ = [('photo', C.c_void_p), ('edits', C.c_void_p), ('mask', C.c_void_p), ('dst', C.c_void_p), ('m', C.c_double * 6),
+                ('inv_feather', C.c_double), ('N', C.c_int32), ('Hp', C.c_int32), ('Wp', C.c_int32), ('C', C.c_int32), ('S', C.c_int32),
+                ('x0', C.c_int32), ('y0', C.c_int32), ('x1', C.c_int32), ('y1', C.c_int32), ('mask_frames', C.c_int32), ('whole', C.c_int32),
+                ('layout', C.c_int32)]
+
+
+PASTE_HWC, PASTE_CHW = 0, 1
+
 _SIGS = {
     'eg3d_abi_version': (C.c_int, []),
     'eg3d_status_string': (C.c_char_p, [C.c_int]),
@@ -508,6 +519,7 @@ _SIGS = {
     'eg3d_feather_pad_query_workspace': (C.c_int, [C.POINTER(FeatherPadParams), C.POINTER(C.c_int64)]),
     'eg3d_feather_pad': (C.c_int, [C.POINTER(FeatherPadParams), C.c_void_p]),
     'eg3d_u8_to_target': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    'eg3d_paste_back8': (C.c_int, [C.POINTER(PasteBack8Params), C.c_void_p]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGS)

@@ -69,6 +69,7 @@ class InversionCoach:
                  mesh_texture_tile: int = 8,
                  do_evaluation: bool = False, eval_dir: Optional[str] = None, lpips_eval_net: Optional[Callable] = None,
                  id_net: Optional[Callable] = None, save_pivot: bool = False, pivot_dir: Optional[str] = None, shape_views: bool = False,
+                 on_tuned: Optional[Callable[[str, torch.Tensor], None]] = None,
                  save_grid: bool = False, gen_video: bool = False, media_dir: Optional[str] = None, video_quality: int = 90):
         """Hyper-parameter names and defaults follow configs/hyperparameters.py.  `early_stop_interval` = how often Phase B reads the
         early-stop state back to the host (1 = every step like the reference).  With the library's Adam the TEST itself runs on the device
@@ -97,7 +98,10 @@ class InversionCoach:
         {media_dir}/pivot/{name}.png before Phase B and {media_dir}/{name}.png after it.  `gen_video` (global_config.gen_video):
         video.write_orbit_video (240 frames, 60 fps, JPEG quality `video_quality`) as {media_dir}/pivot/{name}_pivot.avi and {media_dir}/{name}.avi.
         `shape_views` (no reference counterpart): both get shaded views of the density surface beside the renders (shape=True of
-        video.pivot_grid: a second row; of video.write_orbit_video: image | shape, twice the width)."""
+        video.pivot_grid: a second row; of video.write_orbit_video: image | shape, twice the width).
+        `on_tuned` (no reference counterpart): called as on_tuned(name, image) after Phase B with the tuned reconstruction, fp32 [1,3,H,W] --
+        what tools/run_inversion.py --paste-back blends into the photograph (images.paste_back)."""
+        self.on_tuned = on_tuned
         if (save_grid or gen_video) and not media_dir:
             raise ValueError('save_grid / gen_video need a media_dir')
         self.save_grid, self.gen_video, self.media_dir, self.video_quality = save_grid, gen_video, media_dir, int(video_quality)
@@ -223,6 +227,8 @@ class InversionCoach:
             img = G.synthesis(w_pivot, cam_pivot, noise_mode='const', force_fp32=True, **self.synth_kwargs)['image']
             psnr_tuned = float(psnr_01(img, target))
             mse = float(((img.clamp(-1, 1) - target) ** 2).mean() / 4.0)
+            if self.on_tuned is not None:
+                self.on_tuned(name, img)
         state = {k: v.detach().clone() for k, v in G.state_dict().items()} if self.keep else None
         G.requires_grad_(False)
         mesh_path = self.write_mesh(name, w_pivot, cam_pivot) if self.gen_mesh else None

@@ -2674,3 +2674,46 @@ def u8_to_target(img: torch.Tensor) -> torch.Tensor:
     out = torch.empty((N, 3, Hi, Wi), dtype=torch.float32, device=x.device)
     L.check(L.lib().eg3d_u8_to_target(L.ptr(x), N, Hi, Wi, L.ptr(out), L.stream_ptr()), 'u8_to_target')
     return out
+
+
+def paste_back(photo: torch.Tensor, edits: torch.Tensor, matrix, region, feather_px: float = 0.0, mask: Optional[torch.Tensor] = None,
+               whole: bool = True, layout: str = 'hwc') -> torch.Tensor:
+    """Edited aligned frames blended into their photograph on the device (eg3d_paste_back8; include/eg3d_hip.h states the arithmetic): photo
+    uint8 [Hp,Wp,C], edits uint8 [N,S,S,C] (or [S,S,C]: the frame axis is dropped from the result too), C = 1 | 3; matrix = the six float64
+    numbers m0..m5 of the affine map photo -> aligned frame (images.paste_plan); region = (x0, y0, x1, y1) inside the photo, the only pixels
+    that are computed; feather_px = the width in aligned pixels over which the blend weight rises from the frame's edge (0: a hard edge);
+    mask = uint8 [S,S] or [N,S,S] in the aligned frame, 255 = all of the edit.  whole=True gives the whole photograph per frame, [N,Hp,Wp,C]
+    (two launches: the photo into every frame, then the region); whole=False the region alone, [N, y1 - y0, x1 - x0, C] (one launch).
+    layout='chw' gives [N,C,H,W] instead, what jpeg_encode takes."""
+    ph, _ = _u8_images(photo, 'paste_back (photo)')
+    x, squeeze = _u8_images(edits, 'paste_back (edits)')
+    if photo.dim() != 3 or x.shape[-1] != ph.shape[-1] or x.shape[1] != x.shape[2] or x.device != ph.device:
+        raise L.Eg3dHipError(f'paste_back: one photo [Hp,Wp,C] and square edits [N,S,S,C] of the same C and device, got {tuple(photo.shape)} and '
+                             f'{tuple(edits.shape)}')
+    if layout not in ('hwc', 'chw'):
+        raise L.Eg3dHipError(f"paste_back: layout 'hwc' | 'chw', got {layout!r}")
+    N, S, _, Ch = x.shape
+    _, Hp, Wp, _ = ph.shape
+    m = [float(v) for v in np.asarray(matrix, dtype=np.float64).reshape(-1)]
+    x0, y0, x1, y1 = (int(v) for v in region)
+    if len(m) != 6 or not (0 <= x0 <= x1 <= Wp and 0 <= y0 <= y1 <= Hp):
+        raise L.Eg3dHipError(f'paste_back: six matrix numbers and a region inside the {Wp} x {Hp} photo, got {len(m)} and {tuple(region)}')
+    feather_px = float(feather_px)
+    if not feather_px >= 0.0:
+        raise L.Eg3dHipError(f'paste_back: feather_px >= 0, got {feather_px}')
+    mk = None
+    if mask is not None:
+        L.require_cuda(mask)
+        if mask.dtype != torch.uint8 or tuple(mask.shape) not in ((S, S), (N, S, S)) or mask.device != ph.device:
+            raise L.Eg3dHipError(f'paste_back: mask uint8 [{S},{S}] or [{N},{S},{S}], got {tuple(mask.shape)} {mask.dtype}')
+        mk = mask.contiguous()
+    Ho, Wo = (Hp, Wp) if whole else (y1 - y0, x1 - x0)
+    out = torch.empty((N, Ch, Ho, Wo) if layout == 'chw' else (N, Ho, Wo, Ch), dtype=torch.uint8, device=ph.device)
+    if out.numel() > 0:
+        p = L.PasteBack8Params(photo=ph.data_ptr(), edits=x.data_ptr(), mask=mk.data_ptr() if mk is not None else None, dst=out.data_ptr(),
+                               inv_feather=1.0 / feather_px if feather_px > 0.0 else 0.0, N=N, Hp=Hp, Wp=Wp, C=Ch, S=S, x0=x0, y0=y0, x1=x1, y1=y1,
+                               mask_frames=N if (mk is not None and mk.dim() == 3) else 1, whole=int(bool(whole)),
+                               layout=L.PASTE_CHW if layout == 'chw' else L.PASTE_HWC)
+        p.m[:] = m
+        L.check(L.lib().eg3d_paste_back8(C.byref(p), L.stream_ptr()), 'paste_back8')
+    return out[0] if squeeze else out

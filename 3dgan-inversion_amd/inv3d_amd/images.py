@@ -4,6 +4,10 @@
                               float64, statement by statement; every pixel step one of the kernels of csrc/imgprep.hip (hipops.pil_resize,
                               feather_pad, pil_quad_warp), the crop a slice.  Landmarks (68 x 2) come from a file, as in EG3D's preprocessing:
                               there is no landmark detector here
+  paste_plan, paste_back   <- no reference counterpart (its alignment goes one way only): the inverse geometry of align_plan as one affine map
+                              photo -> aligned frame in host float64, and the edited frame(s) blended back into the photograph by
+                              hipops.paste_back (csrc/imgprep.hip): what tools/paste_back.py, video.write_orbit_video(paste=...),
+                              tools/run_ganspace.py --paste-photo and tools/run_inversion.py --paste-back write
   e4e_image_transform      <- training/coaches/base_coach.py:41-45: ToPILImage, Resize((256, 256)), ToTensor, Normalize
   load_landmarks           <- a .json ({name: 68 x 2}) or .npz (one array per name) mapping
   load_targets             <- ImagesDataset / make_dataset + ToTensor / Normalize: the (name, target, None) tuples InversionCoach.run takes
@@ -106,6 +110,91 @@ def align_face(img_u8: torch.Tensor, landmarks, output_size: int) -> torch.Tenso
     # transform_size = output_size in the reference, so its closing `if output_size < transform_size: img.resize(...)` (alignment.py:110-111)
     # is dead code: the warp writes the output size directly, and it stays dead here
     return hipops.pil_quad_warp(img, (output_size, output_size), plan.quad)
+
+
+class PastePlan(NamedTuple):
+    matrix: Tuple[float, ...]                      # m0..m5: u = m0 + m1 X + m2 Y, v = m3 + m4 X + m5 Y, photo -> aligned frame (centres at + 0.5)
+    region: Tuple[int, int, int, int]              # (x0, y0, x1, y1): the aligned square's bounding box in the photo, clamped to it
+    presize: Optional[int]                         # side to shrink the edit to before the paste (scale > 1), or None
+    scale: float                                   # aligned pixels per photo pixel
+
+
+def paste_plan(height: int, width: int, landmarks, output_size: int) -> PastePlan:
+    """The inverse geometry of align_face for a photograph of height x width and an aligned frame of output_size (host float64).  align_face
+    is shrink, crop, pad, QUAD warp; the quad is a rotated square, so the QUAD map is affine and photo -> aligned frame is one affine map:
+        P = (X sx + ox, Y sy + oy),  (u, v) = A^-1 (P - (a0, a4))
+    with sx, sy = the scale the LANCZOS shrink really applied (shrunk size / size, not 1 / shrink), (ox, oy) = pad - crop offsets and
+    a0..a7 = hipops.pil_quad_coeffs of the plan's quad.  A general quad (bilinear coefficients a3, a7 that matter) has no such inverse and
+    raises ValueError.  No reference counterpart: the reference's alignment goes one way only."""
+    from .hipops import pil_quad_coeffs
+    S = int(output_size)
+    plan = align_plan(height, width, landmarks, S)
+    a = pil_quad_coeffs((S, S), plan.quad)
+    if not np.isfinite(a).all() or max(abs(a[3]), abs(a[7])) * S * S > 1e-6:
+        raise ValueError('paste_plan: the quad is no parallelogram: a general quad is not a supported inverse')
+    det = a[1] * a[6] - a[2] * a[5]
+    if det == 0.0:
+        raise ValueError('paste_plan: a degenerate quad')
+    sx = plan.shrink_size[0] / float(width) if plan.shrink_size is not None else 1.0
+    sy = plan.shrink_size[1] / float(height) if plan.shrink_size is not None else 1.0
+    ox = float((plan.pad[0] if plan.pad is not None else 0) - (plan.crop[0] if plan.crop is not None else 0))
+    oy = float((plan.pad[1] if plan.pad is not None else 0) - (plan.crop[1] if plan.crop is not None else 0))
+    i00, i01, i10, i11 = a[6] / det, -a[2] / det, -a[5] / det, a[1] / det          # A^-1
+    tx, ty = ox - a[0], oy - a[4]
+    matrix = (i00 * tx + i01 * ty, i00 * sx, i01 * sy, i10 * tx + i11 * ty, i10 * sx, i11 * sy)
+    # the square's corners pulled back to the photo: X = (a0 + a1 u + a2 v - ox) / sx
+    xs = [(a[0] + a[1] * u + a[2] * v - ox) / sx for u, v in ((0, 0), (0, S), (S, S), (S, 0))]
+    ys = [(a[4] + a[5] * u + a[6] * v - oy) / sy for u, v in ((0, 0), (0, S), (S, S), (S, 0))]
+    clamp = lambda v, hi: int(min(max(v, 0), hi))
+    region = (clamp(np.floor(min(xs)), width), clamp(np.floor(min(ys)), height), clamp(np.ceil(max(xs)), width), clamp(np.ceil(max(ys)), height))
+    scale = float(np.sqrt(abs(matrix[1] * matrix[5] - matrix[2] * matrix[4])))
+    presize = max(1, int(np.rint(S / scale))) if scale > 1.0 else None
+    return PastePlan(tuple(float(v) for v in matrix), region, presize, scale)
+
+
+def _edit_frames(edit: torch.Tensor):
+    """uint8 [N,S,S,3] frames (and whether the frame axis was added) of what paste_back accepts."""
+    from . import hipops
+    if edit.dtype == torch.uint8 and edit.dim() in (3, 4) and edit.shape[-1] == 3 and edit.shape[-2] == edit.shape[-3]:
+        return (edit[None] if edit.dim() == 3 else edit), edit.dim() == 3
+    if edit.dtype == torch.float32 and edit.dim() == 4 and edit.shape[1] == 3 and edit.shape[2] == edit.shape[3]:
+        n, _, s, _ = edit.shape
+        return hipops.image_grid_u8(edit, nrow=1, padding=0).reshape(n, s, s, 3), False
+    raise ValueError(f'paste_back: edit uint8 [S,S,3] or [N,S,S,3], or fp32 [N,3,S,S] in [-1,1], got {tuple(edit.shape)} {edit.dtype}')
+
+
+def paste_back(photo_u8: torch.Tensor, edit: torch.Tensor, landmarks, feather: float = 0.08, mask: Optional[torch.Tensor] = None,
+               region: str = 'photo', layout: str = 'hwc') -> torch.Tensor:
+    """The closing step of an edit: the aligned S x S result(s) blended back into the photograph they were aligned from, on the device
+    (hipops.paste_back).  photo_u8 uint8 [H,W,3] and the landmarks align_face took; edit uint8 [S,S,3] or [N,S,S,3], or the generator's fp32
+    [N,3,S,S] in [-1,1] (quantised as hipops.image_grid_u8 does) -- S is the edit's own side, whatever side the photo was aligned at.
+    feather = the blend ramp from the frame's edge as a fraction of the side; mask = uint8 [S,S] or [N,S,S] in the aligned frame.
+    region='photo': the whole photograph per frame ([H,W,3] for one [S,S,3] edit, else [N,H,W,3]); a face wholly outside the photo gives the
+    photo unchanged.  region='bbox': only the aligned square's bounding box in the photo (PastePlan.region); ValueError if that is empty.
+    Where the face is smaller in the photo than in the frame (PastePlan.scale > 1) the edit and the mask are first shrunk to presize with
+    Pillow's LANCZOS (hipops.pil_resize), so the bilinear taps do not alias.  layout='chw' gives [N,3,H,W] for the JPEG encoder."""
+    from . import hipops
+    if region not in ('photo', 'bbox'):
+        raise ValueError(f"paste_back: region 'photo' | 'bbox', got {region!r}")
+    if photo_u8.dim() != 3:
+        raise ValueError(f'paste_back: one uint8 [H,W,3] photo, got {tuple(photo_u8.shape)}')
+    frames, squeeze = _edit_frames(edit)
+    S = int(frames.shape[1])
+    plan = paste_plan(photo_u8.shape[0], photo_u8.shape[1], landmarks, S)
+    x0, y0, x1, y1 = plan.region
+    if region == 'bbox' and (x1 <= x0 or y1 <= y0):
+        raise ValueError('paste_back: the aligned square lies wholly outside the photo')
+    matrix, feather_px = np.asarray(plan.matrix, dtype=np.float64), float(feather) * S
+    if mask is not None and mask.dim() not in (2, 3):
+        raise ValueError(f'paste_back: mask uint8 [S,S] or [N,S,S], got {tuple(mask.shape)}')
+    if plan.presize is not None and plan.presize != S:
+        ps = plan.presize
+        frames = hipops.pil_resize(frames, (ps, ps), 'lanczos')
+        if mask is not None:
+            mask = hipops.pil_resize(mask[..., None], (ps, ps), 'lanczos')[..., 0]
+        matrix, feather_px = matrix * (ps / S), feather_px * (ps / S)
+    out = hipops.paste_back(photo_u8, frames, matrix, plan.region, feather_px=feather_px, mask=mask, whole=region == 'photo', layout=layout)
+    return out[0] if squeeze else out
 
 
 def e4e_image_transform(target: torch.Tensor) -> torch.Tensor:

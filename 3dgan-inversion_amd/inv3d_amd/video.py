@@ -188,16 +188,23 @@ def write_png(path: str, u8_hwc) -> None:
 # ---- the per-image outputs -----------------------------------------------------------------------------------------------------------------------
 @torch.no_grad()
 def write_orbit_video(G, ws: torch.Tensor, path: str, num_frames: int = 240, image_mode: str = 'image', fps: int = 60, quality: int = 90,
-                      batch: int = 16, shape: bool = False, shape_kwargs: Optional[dict] = None, **synthesis_kwargs) -> int:
+                      batch: int = 16, shape: bool = False, shape_kwargs: Optional[dict] = None, paste=None, paste_kwargs: Optional[dict] = None,
+                      **synthesis_kwargs) -> int:
     """gen_interp_video for one latent: inference.render_orbit's frames, `batch` at a time through hipops.jpeg_encode (4:2:0; grey for
     image_depth), one device-to-host copy per batch, into a Motion-JPEG AVI at `path`.  Returns the number of frames written.
     shape=True (no reference counterpart): every frame is image | shape side by side, twice the width -- the shaded first-hit view of the
     density surface from the same camera at the frame's resolution (inference.render_shape; shape_kwargs: grid_res, level, shade, keep,
-    min_voxels, connectivity, ...).  The density grid and its brick maxima are built once per video, and so is inference.clean_grid's pass.  With shape=False the file is what it was before the option existed."""
+    min_voxels, connectivity, ...).  The density grid and its brick maxima are built once per video, and so is inference.clean_grid's pass.  With shape=False the file is what it was before the option existed.
+    paste=(photo uint8 [H,W,3] on the device, landmarks 68 x 2) (no reference counterpart): every frame is blended back into the photograph
+    the latent was inverted from (images.paste_back, `batch` frames per call, planar output straight into the encoder) and the video shows
+    the photo, by default the face's bounding box in it (paste_kwargs: region='photo' for the whole photograph, feather, mask).  Colour frames
+    only, and not together with shape.  With paste=None the file is what it was before the option existed."""
     from .hipops import jpeg_encode
     from .inference import clean_grid, density_grid, orbit_cameras, render_orbit, render_shape
     if batch < 1:
         raise ValueError('write_orbit_video: batch >= 1')
+    if paste is not None and (shape or image_mode != 'image'):
+        raise ValueError("write_orbit_video: paste takes the colour frames alone (image_mode='image', shape=False)")
     writer, pending, n = None, [], 0
     if shape:
         skw = dict(shape_kwargs or {})
@@ -217,10 +224,14 @@ def write_orbit_video(G, ws: torch.Tensor, path: str, num_frames: int = 240, ima
 
     def flush():
         nonlocal writer, n
-        data, offsets = jpeg_encode(torch.stack(pending), quality=quality)
+        frames = torch.stack(pending)
+        if paste is not None:
+            from .images import paste_back
+            frames = paste_back(paste[0], frames, paste[1], layout='chw', **dict(dict(region='bbox'), **(paste_kwargs or {})))
+        data, offsets = jpeg_encode(frames, quality=quality)
         host, off = data.cpu().numpy(), offsets.tolist()                 # (offsets are already on the host: one copy, the bytes)
         if writer is None:
-            writer = MjpegAviWriter(path, pending[0].shape[-1], pending[0].shape[-2], fps=fps)
+            writer = MjpegAviWriter(path, frames.shape[-1], frames.shape[-2], fps=fps)
         for i in range(len(pending)):
             writer.write(host[off[i]:off[i + 1]].tobytes())
         n += len(pending)

@@ -1633,6 +1633,37 @@ int eg3d_feather_pad(const eg3d_feather_pad_params* p, void* stream);
  *   correctly rounded fp32 operation (a true division by 255, not a multiplication by its reciprocal). */
 int eg3d_u8_to_target(const uint8_t* img, int N, int H, int W, float* out, void* stream);
 
+/* eg3d_paste_back8: the inverse of the ingestion -- N edited S x S images (the aligned frame) blended into one photograph, which all frames
+ *   share.  m[0..5] is the affine map photo -> aligned frame in Pillow's continuous coordinates (pixel centres at + 0.5; inv3d_amd/images.py
+ *   paste_plan builds it from align_plan).  For every photo pixel (X, Y) of the region x0 <= X < x1, y0 <= Y < y1 and every frame, in fp64,
+ *   every operation rounded on its own, in this order (no FMA contraction, no division on the device):
+ *     Xc = X + 0.5, Yc = Y + 0.5;  u = m0 + m1 Xc + m2 Yc,  v = m3 + m4 Xc + m5 Yc
+ *     !(u >= 0 && u < S && v >= 0 && v < S) (NaN too): out = photo
+ *     val  = bilinear(edit, u - 0.5, v - 0.5): eg3d_quad_warp8's taps, edge clamp and r0 / r1 / v order, not truncated
+ *     d = min(min(u, S - u), min(v, S - v));  f = inv_feather > 0 ? min(d inv_feather, 1) : 1;  a = (f f) (3 - 2 f)
+ *     mask given: a = a (bilinear(mask, same taps) (1 / 255))         (1 / 255 a host double)
+ *     out = uint8(rint(photo + (val - photo) a)), ties to even
+ *   whole = 0: dst holds the region only, [N, y1 - y0, x1 - x0, C] (layout EG3D_PASTE_HWC) or [N, C, y1 - y0, x1 - x0] (EG3D_PASTE_CHW, what
+ *   eg3d_jpeg_encode takes).  whole = 1: dst holds the whole photograph per frame, [N,Hp,Wp,C] or [N,C,Hp,Wp]: one launch copies the photo
+ *   into every frame, a second one writes the region.  An empty region is valid: nothing is launched for whole = 0, only the copy for whole = 1.
+ *   The region must lie inside the photo; sides 1..65535.  No atomics, no sum across threads: both builds give the same bytes. */
+#define EG3D_PASTE_HWC 0
+#define EG3D_PASTE_CHW 1
+typedef struct eg3d_paste_back8_params {
+    const uint8_t* photo;              /* [Hp,Wp,C] */
+    const uint8_t* edits;              /* [N,S,S,C] */
+    const uint8_t* mask;               /* NULL, [S,S] (mask_frames = 1) or [N,S,S] (mask_frames = N) */
+    uint8_t* dst;
+    double m[6];
+    double inv_feather;                /* 1 / feather width in aligned pixels; 0: a hard edge */
+    int32_t N, Hp, Wp, C, S;
+    int32_t x0, y0, x1, y1;
+    int32_t mask_frames;               /* 1 or N; ignored without a mask */
+    int32_t whole;
+    int32_t layout;
+} eg3d_paste_back8_params;
+int eg3d_paste_back8(const eg3d_paste_back8_params* p, void* stream);
+
 /* Measurement aid (bench.py): a register-only v_mfma_f32_32x32x16_f16 loop on caller-supplied fp16 data -- what the matrix pipe sustains on
  * this chip at its current power / clock state, timed inside the benchmark run.  in: 4096 x 8 fp16 (64 KiB); out: blocks x 256 floats;
  * executes blocks x 4 waves x iters x 24 MFMAs of 32 x 32 x 16.  No reference counterpart. */

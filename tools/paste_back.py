@@ -1,0 +1,55 @@
+"""Paste-back from the command line: edited aligned images blended back into the photograph they were aligned from, on the GPU kernels of
+this package (inv3d_amd/images.py paste_back, csrc/imgprep.hip).  No reference counterpart: the reference's alignment goes one way only.
+
+  python tools/paste_back.py --photo photo.jpg --landmarks landmarks.json --edit a_inter_1.png a_inter_2.png --out-dir pasted
+                             [--feather 0.08] [--mask mask.png] [--bbox]
+
+--landmarks: a .json {name: 68 x 2} or an .npz with an entry for the photo (its file name up to the first dot) -- the points align_face took.
+--edit: square RGB images in the aligned frame (any side); each is written as {out-dir}/{edit name}.png, the whole photograph with the edit in
+it, or with --bbox only the face's bounding box in the photo.  --feather: the blend ramp from the frame's edge as a fraction of the side.
+--mask: a grey image of the edits' side in the aligned frame, 255 = all of the edit."""
+import argparse
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, '3dgan-inversion_amd'))
+
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(description=__doc__.splitlines()[0])
+    ap.add_argument('--photo', required=True)
+    ap.add_argument('--landmarks', required=True, help='.json {name: 68 x 2} or .npz')
+    ap.add_argument('--edit', required=True, nargs='+', metavar='FILE')
+    ap.add_argument('--out-dir', required=True)
+    ap.add_argument('--feather', type=float, default=0.08)
+    ap.add_argument('--mask', default=None)
+    ap.add_argument('--bbox', action='store_true')
+    a = ap.parse_args(argv)
+    from inv3d_amd import images, video
+    dev = torch.device('cuda')
+    lms, key = images.load_landmarks(a.landmarks), os.path.basename(a.photo).split('.')[0]
+    if key not in lms:
+        raise SystemExit(f'{a.landmarks} has no entry for {key}')
+    photo = images.decode_rgb(a.photo, dev)
+    mask = None
+    if a.mask is not None:
+        from PIL import Image
+        with Image.open(a.mask) as im:
+            mask = torch.from_numpy(np.array(im.convert('L'), dtype=np.uint8)).to(dev)
+    os.makedirs(a.out_dir, exist_ok=True)
+    written = []
+    for path in a.edit:
+        edit = images.decode_rgb(path, dev)
+        out = os.path.join(a.out_dir, os.path.basename(path).split('.')[0] + '.png')
+        video.write_png(out, images.paste_back(photo, edit, lms[key], feather=a.feather, mask=mask, region='bbox' if a.bbox else 'photo'))
+        written.append(out)
+        print(out)
+    return written
+
+
+if __name__ == '__main__':
+    main()

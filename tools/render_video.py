@@ -7,7 +7,9 @@ single_id_coach.py:61-62,84-85 calls it), frames encoded by the GPU JPEG encoder
 (inv3d_amd.synthetic, seed --seed).  --ws: a [1, num_ws, w_dim] (or [num_ws, w_dim]) .npy latent, e.g. the coach's {image}_ws.npy.
 --depth renders image_depth (grey frames) instead of the colour image.  --shape puts the shaded first-hit view of the density surface
 (--shape-level, --shape-grid, --shape-shade lambert | normal) beside every frame: twice the width, one density grid per video.
-With --shape, --keep N / --min-voxels M / --connectivity {6,26} remove floaters from that grid first (inference.clean_grid, once per video)."""
+With --shape, --keep N / --min-voxels M / --connectivity {6,26} remove floaters from that grid first (inference.clean_grid, once per video).
+--paste-photo P --landmarks L blends every frame back into the photograph P the latent was inverted from (images.paste_back): the video
+shows the face's bounding box in the photo, with --paste-whole the whole photograph."""
 import argparse
 import os
 import sys
@@ -38,6 +40,9 @@ def main():
     ap.add_argument('--keep', type=int, default=None, help='--shape: keep only the N largest connected components above the level')
     ap.add_argument('--min-voxels', type=int, default=0, help='--shape: drop connected components of fewer voxels')
     ap.add_argument('--connectivity', type=int, default=6, choices=(6, 26))
+    ap.add_argument('--paste-photo', default=None, help='the photograph the latent was inverted from: every frame is blended back into it')
+    ap.add_argument('--landmarks', default=None, help='--paste-photo: a .json / .npz of 68 x 2 landmarks with an entry for the photo')
+    ap.add_argument('--paste-whole', action='store_true', help="--paste-photo: the whole photograph per frame, not the face's bounding box")
     a = ap.parse_args()
     from inv3d_amd import video as V
     dev = torch.device('cuda')
@@ -52,9 +57,19 @@ def main():
     if ws.dim() == 2:
         ws = ws.unsqueeze(0)
     clean = dict(keep=a.keep, min_voxels=a.min_voxels, connectivity=a.connectivity) if (a.keep is not None or a.min_voxels > 0) else {}
+    paste = None
+    if a.paste_photo is not None:
+        from inv3d_amd import images
+        if not a.landmarks:
+            raise SystemExit('--paste-photo needs --landmarks')
+        lms, key = images.load_landmarks(a.landmarks), os.path.basename(a.paste_photo).split('.')[0]
+        if key not in lms:
+            raise SystemExit(f'{a.landmarks} has no entry for {key}')
+        paste = (images.decode_rgb(a.paste_photo, dev), lms[key])
     t0 = time.perf_counter()
     n = V.write_orbit_video(G, ws, a.out, num_frames=a.frames, image_mode='image_depth' if a.depth else 'image', fps=a.fps, quality=a.quality,
-                            batch=a.batch, shape=a.shape, shape_kwargs=dict(level=a.shape_level, grid_res=a.shape_grid, shade=a.shape_shade, **clean))
+                            batch=a.batch, shape=a.shape, shape_kwargs=dict(level=a.shape_level, grid_res=a.shape_grid, shade=a.shape_shade, **clean),
+                            paste=paste, paste_kwargs=dict(region='photo') if a.paste_whole else None)
     dt = time.perf_counter() - t0
     print(f'{a.out}: {n} frames, {os.path.getsize(a.out)} bytes ({dt * 1e3:.1f} ms, {n / dt:.1f} frames/s)')
 

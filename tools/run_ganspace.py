@@ -8,7 +8,8 @@ package (inv3d_amd/ganspace.py, csrc/pca.hip).
 fit   writes the [K, w_dim] float32 components of a PCA of W at the frontal camera; the reference's ganspace/pca_comp/*.npy load the same way.
 edit  takes a pivot as the coach's save_pivot writes it ({name}_ws.npy [1, num_ws, w_dim], {name}_cam.npy [1, 25]) and a named direction of
       ganspace.GANSPACE_DIRECTIONS or its four numbers (component, first layer, layers, power); writes {name}_grid.png and, with --save-images,
-      {name}_inter_{i}.png (i from 1) as the reference names them.
+      {name}_inter_{i}.png (i from 1) as the reference names them.  With --paste-photo P --landmarks L (no reference counterpart) also
+      {name}_pasted.png: every edit blended back into the photograph P (images.paste_back), the face's bounding box of each side by side.
 --weights: a generator archive (inv3d_amd.weights, tools/convert_eg3d_pickle.py); otherwise a synthetic generator (inv3d_amd.synthetic, weights
 seed --seed): 'full' is the full-size one, 'small' the 32-wide one of the tests."""
 import argparse
@@ -65,6 +66,9 @@ def _parser():
     ed.add_argument('--out-dir', required=True)
     ed.add_argument('--name', required=True)
     ed.add_argument('--save-images', action='store_true')
+    ed.add_argument('--paste-photo', default=None, help='the photograph the pivot was inverted from: also write {name}_pasted.png')
+    ed.add_argument('--landmarks', default=None, help='--paste-photo: a .json / .npz of 68 x 2 landmarks with an entry for the photo (or --name)')
+    ed.add_argument('--paste-feather', type=float, default=0.08)
     return ap
 
 
@@ -97,6 +101,21 @@ def main(argv=None):
         for i in range(a.num_imgs):
             Image.fromarray(out['images'][i].cpu().numpy(), 'RGB').save(os.path.join(a.out_dir, f'{a.name}_inter_{i + 1}.png'))
     print(f'{path}: component {idx}, layers {start}..{start + num - 1}, power {power}, {a.num_imgs} images')
+    if a.paste_photo is not None:
+        from inv3d_amd import images
+        from inv3d_amd.video import write_png
+        if not a.landmarks:
+            raise SystemExit('--paste-photo needs --landmarks')
+        lms = images.load_landmarks(a.landmarks)
+        key = os.path.basename(a.paste_photo).split('.')[0]
+        key = key if key in lms else a.name
+        if key not in lms:
+            raise SystemExit(f'{a.landmarks} has no entry for {os.path.basename(a.paste_photo)} or {a.name}')
+        pasted = images.paste_back(images.decode_rgb(a.paste_photo, dev), out['images'], lms[key], feather=a.paste_feather, region='bbox')
+        out['pasted'] = pasted                                                 # [num_imgs, h, w, 3]: the face's bounding box in the photo, per edit
+        ppath = os.path.join(a.out_dir, f'{a.name}_pasted.png')
+        write_png(ppath, torch.cat(list(pasted), dim=1))
+        print(f'{ppath}: {a.num_imgs} edits in the photo, {pasted.shape[2]} x {pasted.shape[1]} each')
     return out
 
 

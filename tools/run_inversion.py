@@ -3,11 +3,13 @@ landmarks are given (inv3d_amd/images.py), then InversionCoach.run -- Phase A, P
 
   python tools/run_inversion.py --in-dir photos --out-dir out [--landmarks landmarks.json] [--weights G.safetensors | --synthetic small|full]
                                 [--steps-a 400] [--steps-b 400] [--optimize-pose] [--graph] [--save-grid] [--gen-video] [--gen-mesh]
-                                [--mesh-format .mrc|.ply] [--mesh-res 512] [--do-evaluation] [--save-pivot]
+                                [--mesh-format .mrc|.ply] [--mesh-res 512] [--do-evaluation] [--save-pivot] [--paste-back]
 
 Images with an entry in --landmarks (a .json {name: 68 x 2} or an .npz) are aligned to the generator's resolution; the others must have it
 already.  --weights: a generator archive (inv3d_amd.weights, tools/convert_eg3d_pickle.py); otherwise a synthetic generator.  Outputs go to
-{out-dir}/media (grids, videos), /mesh, /eval, /pivot; a summary line per image and the totals are printed."""
+{out-dir}/media (grids, videos), /mesh, /eval, /pivot; a summary line per image and the totals are printed.  --paste-back also writes
+{out-dir}/pasted/{name}.png for every image that had landmarks: the tuned reconstruction blended back into the photograph it was aligned
+from (images.paste_back)."""
 import argparse
 import os
 import sys
@@ -59,6 +61,8 @@ def main(argv=None):
     ap.add_argument('--mesh-res', type=int, default=512)
     ap.add_argument('--do-evaluation', action='store_true')
     ap.add_argument('--save-pivot', action='store_true')
+    ap.add_argument('--paste-back', action='store_true', help='write the tuned reconstruction blended into its photograph (needs --landmarks)')
+    ap.add_argument('--paste-feather', type=float, default=0.08, help='--paste-back: blend ramp as a fraction of the aligned side')
     a = ap.parse_args(argv)
     from inv3d_amd import images
     from inv3d_amd.coach import InversionCoach
@@ -69,13 +73,26 @@ def main(argv=None):
     if not targets:
         raise SystemExit(f'no image files in {a.in_dir}')
     sub = lambda d: os.path.join(a.out_dir, d)
+    on_tuned = None
+    if a.paste_back:
+        if not a.landmarks:
+            raise SystemExit('--paste-back needs --landmarks: only an aligned photograph has a place to paste into')
+        from inv3d_amd.video import write_png
+        lms, paths = images.load_landmarks(a.landmarks), dict(images.image_files(a.in_dir))
+
+        def on_tuned(name, img):
+            if name not in lms:
+                return
+            os.makedirs(sub('pasted'), exist_ok=True)
+            pasted = images.paste_back(images.decode_rgb(paths[name], dev), img.float(), lms[name], feather=a.paste_feather)
+            write_png(os.path.join(sub('pasted'), f'{name}.png'), pasted[0])
     samples = a.w_avg_samples if a.w_avg_samples is not None else (10000 if a.weights else 0)
     coach = InversionCoach(G, first_inv_steps=a.steps_a, max_pti_steps=a.steps_b, lpips_threshold=a.lpips_threshold, optimize_pose=a.optimize_pose,
                            use_graph=a.graph, w_avg_samples=samples, save_grid=a.save_grid, gen_video=a.gen_video,
                            media_dir=sub('media') if (a.save_grid or a.gen_video) else None, gen_mesh=a.gen_mesh,
                            mesh_dir=sub('mesh') if a.gen_mesh else None, mesh_format=a.mesh_format, mesh_res=a.mesh_res,
                            do_evaluation=a.do_evaluation, eval_dir=sub('eval') if a.do_evaluation else None, save_pivot=a.save_pivot,
-                           pivot_dir=sub('pivot') if a.save_pivot else None)
+                           pivot_dir=sub('pivot') if a.save_pivot else None, on_tuned=on_tuned)
     results, stats = coach.run(targets)
     for r in results:
         print(f'{r.name}: {r.steps_a} + {r.steps_b} steps, PSNR {r.psnr_pivot:.2f} dB at the pivot, {r.psnr_tuned:.2f} dB tuned')

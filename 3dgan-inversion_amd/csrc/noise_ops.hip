@@ -234,14 +234,44 @@ __global__ void __launch_bounds__(NT) noise_apply_norm_kernel(const NoiseBufs B,
 // on the device (graph replay): every block reads it on entry, the last block to retire writes it back incremented.
 constexpr int ADAM_CHUNK = NT * 4;
 
+// block -> (item, first element).  Lane i reads item i's length and the lanes scan them: one round trip to the kernel arguments instead of one
+// dependent scalar load per item in front of the block's first load.
+static_assert(EG3D_ADAM_ITEMS_MAX <= 64, "one lane per item");
 __device__ __forceinline__ bool adam_locate(const eg3d_adam_list& A, int blk, int& item, int64_t& start) {
-    int b0 = 0;
-    for (item = 0; item < A.n; ++item) {
-        const int nb = (int)((A.items[item].n + ADAM_CHUNK - 1) / ADAM_CHUNK);
-        if (blk < b0 + nb) { start = (int64_t)(blk - b0) * ADAM_CHUNK; return true; }
-        b0 += nb;
+    const int lane = threadIdx.x & 63;
+    const int nb = lane < A.n ? (int)((A.items[lane].n + ADAM_CHUNK - 1) / ADAM_CHUNK) : 0;
+    int inc = nb;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) { const int t = __shfl_up(inc, o); if (lane >= o) inc += t; }
+    const unsigned long long m = __ballot(lane < A.n && blk < inc);
+    if (m == 0) return false;
+    item = __ffsll(m) - 1;
+    start = (int64_t)__builtin_amdgcn_readfirstlane(blk - __shfl(inc - nb, item)) * ADAM_CHUNK;
+    return true;
+}
+
+// A thread owns four consecutive elements of its block's chunk: one 16-byte access per stream where every base of the item is 16-byte aligned and the
+// four lie inside the leaf, four 4-byte ones (at clamped addresses, so that none waits behind a branch) otherwise.
+struct Quad { float e[4]; };
+__device__ __forceinline__ Quad load_quad(const float* p, int64_t i0, int64_t n, bool vec) {
+    Quad q;
+    if (vec) { const float4 t = *reinterpret_cast<const float4*>(p + i0); q.e[0] = t.x; q.e[1] = t.y; q.e[2] = t.z; q.e[3] = t.w; }
+    else {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) q.e[e] = p[i0 + e < n ? i0 + e : n - 1];
     }
-    return false;
+    return q;
+}
+__device__ __forceinline__ void store_quad(float* p, int64_t i0, int64_t n, bool vec, const Quad& q) {
+    if (vec) *reinterpret_cast<float4*>(p + i0) = make_float4(q.e[0], q.e[1], q.e[2], q.e[3]);
+    else {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) if (i0 + e < n) p[i0 + e] = q.e[e];
+    }
+}
+__device__ __forceinline__ bool aligned16(const void* a, const void* b2 = nullptr, const void* c = nullptr, const void* d = nullptr, const void* e = nullptr) {
+    return ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b2) | reinterpret_cast<uintptr_t>(c) | reinterpret_cast<uintptr_t>(d) |
+             reinterpret_cast<uintptr_t>(e)) & 15) == 0;
 }
 
 __global__ void early_stop_flag_kernel(const float* __restrict__ value, float thr, float* __restrict__ done) {
@@ -250,31 +280,40 @@ __global__ void early_stop_flag_kernel(const float* __restrict__ value, float th
 
 __global__ void __launch_bounds__(NT) adam_step_kernel(const eg3d_adam_list A, float* __restrict__ ws) {
     __shared__ float red[32];
-    // the three device scalars are read together (one memory round trip in front of the update instead of three in sequence)
+    int item = 0;
+    int64_t start = 0;
+    const bool mine = adam_locate(A, blockIdx.x, item, start);
+    const eg3d_adam_item& it = A.items[item];
+    const int64_t i0 = start + (int64_t)threadIdx.x * 4;
+    bool vec = false;
+    Quad g, g2, m, v, p;
+    if (mine) {
+        const float* gp = it.g ? it.g : it.m;              // (an absent gradient is read at m's address: no load behind a branch)
+        const float* g2p = it.g2 ? it.g2 : it.m;
+        vec = aligned16(it.p, it.m, it.v, gp, g2p) && i0 + 4 <= it.n;
+        g = load_quad(gp, i0, it.n, vec); g2 = load_quad(g2p, i0, it.n, vec);
+        m = load_quad(it.m, i0, it.n, vec); v = load_quad(it.v, i0, it.n, vec); p = load_quad(it.p, i0, it.n, vec);
+    }
+    // the three device scalars are read together (one round trip, not three in sequence) and AFTER the block's loads went out: only the arithmetic needs
+    // them, and scalar loads return in order -- read first, they would be waited for before the first item pointer could be used
     const float skipv = A.skip != nullptr ? *A.skip : 0.f;
     const float t = *A.step + 1.0f;
     const float lr = *A.lr;
     if (skipv != 0.f) return;                                  // (uniform over the grid: nothing is touched, the step count stays)
-    int item;
-    int64_t start;
-    if (adam_locate(A, blockIdx.x, item, start)) {
-        const eg3d_adam_item& it = A.items[item];
+    if (mine) {
         const float bc1 = 1.0f - powf(A.beta1, t), bc2s = sqrtf(1.0f - powf(A.beta2, t));
         const float step_size = lr / bc1;
         float s = 0.f, q = 0.f;
 #pragma unroll
-        for (int u = 0; u < ADAM_CHUNK / NT; ++u) {
-            const int64_t i = start + threadIdx.x + u * NT;
-            if (i < it.n) {
-                float g = it.g ? it.g[i] : 0.f;
-                if (it.g2) g += it.g2[i];
-                const float m = it.m[i] + (g - it.m[i]) * (1.0f - A.beta1);
-                const float v = it.v[i] * A.beta2 + (1.0f - A.beta2) * g * g;
-                const float x = it.p[i] - step_size * m / (sqrtf(v) / bc2s + A.eps);
-                it.m[i] = m; it.v[i] = v; it.p[i] = x;
-                s += x; q += x * x;
-            }
+        for (int e = 0; e < 4; ++e) {
+            float gg = it.g ? g.e[e] : 0.f;
+            if (it.g2) gg += g2.e[e];
+            m.e[e] = m.e[e] + (gg - m.e[e]) * (1.0f - A.beta1);
+            v.e[e] = v.e[e] * A.beta2 + (1.0f - A.beta2) * gg * gg;
+            p.e[e] = p.e[e] - step_size * m.e[e] / (sqrtf(v.e[e]) / bc2s + A.eps);
+            if (i0 + e < it.n) { s += p.e[e]; q += p.e[e] * p.e[e]; }
         }
+        store_quad(it.m, i0, it.n, vec, m); store_quad(it.v, i0, it.n, vec, v); store_quad(it.p, i0, it.n, vec, p);
         if (it.normalize) {                  // (block-uniform)
             s = block_sum(s, red);
             q = block_sum(q, red);
@@ -289,19 +328,20 @@ __global__ void __launch_bounds__(NT) adam_step_kernel(const eg3d_adam_list A, f
 }
 
 __global__ void __launch_bounds__(NT) adam_apply_norm_kernel(const eg3d_adam_list A, const float* __restrict__ ws) {
-    int item;
-    int64_t start;
-    if (A.skip != nullptr && *A.skip != 0.f) return;
+    int item = 0;
+    int64_t start = 0;
     if (!adam_locate(A, blockIdx.x, item, start)) return;
     const eg3d_adam_item& it = A.items[item];
     if (!it.normalize) return;
+    const int64_t i0 = start + (int64_t)threadIdx.x * 4;
+    const bool vec = aligned16(it.p) && i0 + 4 <= it.n;
+    Quad p = load_quad(it.p, i0, it.n, vec);
+    if (A.skip != nullptr && *A.skip != 0.f) return;
     const float mean = ws[2 * item] / (float)it.n;
     const float inv = 1.0f / sqrtf(ws[2 * item + 1] / (float)it.n - mean * mean);
 #pragma unroll
-    for (int u = 0; u < ADAM_CHUNK / NT; ++u) {
-        const int64_t i = start + threadIdx.x + u * NT;
-        if (i < it.n) it.p[i] = (it.p[i] - mean) * inv;
-    }
+    for (int e = 0; e < 4; ++e) p.e[e] = (p.e[e] - mean) * inv;
+    store_quad(it.p, i0, it.n, vec, p);
 }
 
 int fill(NoiseBufs& B, float* const* x, float* const* g, const int32_t* res, int nbufs) {

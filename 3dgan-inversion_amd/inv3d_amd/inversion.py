@@ -42,9 +42,10 @@ class StubFeatureNet(torch.nn.Module):
             cin = w
 
     def forward(self, img):
-        """Three launches per stage and direction: conv + lrelu (fused epilogue), the 2x2 average, the channel normalisation written
-        straight into the flat feature vector (loss_nets.unit_features).  The features are pixel-major inside a stage's slice -- the
-        projector only ever takes squared distances between two such vectors."""
+        """One launch per stage forward (conv + lrelu + the 2x2 average, eg3d_conv3x3_direct) and two backward (eg3d_pool2_act_bwd, then the data
+        gradient), and one launch per direction for the channel normalisation of all stages, written straight into the flat feature vector
+        (loss_nets.unit_features).  The features are pixel-major inside a stage's slice -- the projector only ever takes squared distances
+        between two such vectors."""
         from . import loss_nets as LN
         x = self.stages(img)
         return LN.unit_features(x, eps=1e-10)

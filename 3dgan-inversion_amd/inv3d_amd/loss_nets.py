@@ -639,7 +639,8 @@ def weighted_objective(terms, group_weights):
 
 
 def unit_features(xs: Sequence[torch.Tensor], eps: float = 1e-10) -> torch.Tensor:
-    """[N, sum H*W*C]: per tap x * rsqrt(sum_c x^2 + eps) / sqrt(H*W), pixel-major inside a tap's slice (one launch per tap and direction)."""
+    """[N, sum H*W*C]: per tap x * rsqrt(sum_c x^2 + eps) / sqrt(H*W), pixel-major inside a tap's slice (one launch per direction for all taps:
+    eg3d_unit_normalize_levels with eps inside the root)."""
     return _LpipsHeadFn.apply((eps, 1), len(xs), *xs, *([None] * len(xs)))
 
 

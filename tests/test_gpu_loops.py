@@ -610,21 +610,25 @@ def test_warp_projection_kernel_vs_aten_chain():
     d = torch.nn.functional.normalize(-cams[1, :16].reshape(4, 4)[:3, 3] + 0.25 * torch.randn(P, 3, generator=g), dim=-1).to(DEV).requires_grad_(True)
     depth = (2.2 + torch.rand(P, generator=g)).to(DEV).requires_grad_(True)
 
-    def chain(o, d, depth):
+    def chain(o, d, depth, ext, K):
         xyz = o + d * depth[:, None]
-        cam_o = init_ext[:, :3, 3].expand(P, 3)
-        plane_pt, w2c = INV._warp_constants(init_ext)
+        cam_o = ext[:, :3, 3].expand(P, 3)
+        plane_pt = (ext.reshape(4, 4) @ torch.tensor([0., 0., 1., 1.], device=DEV, dtype=ext.dtype))[None, :3]       # (INV._warp_constants in ext's own precision)
+        w2c = torch.linalg.inv(ext.reshape(4, 4))
         hit = INV.line_plane_intersection(-cam_o, plane_pt.expand_as(cam_o), xyz - cam_o, cam_o)
-        hit1 = torch.cat([hit, torch.ones(P, 1, device=DEV)], -1).t()
+        hit1 = torch.cat([hit, torch.ones(P, 1, device=DEV, dtype=hit.dtype)], -1).t()
         uv = (w2c @ hit1)[:3].t()
         uv = uv / uv[:, 2:]
-        uv = (intrinsic.reshape(3, 3) @ uv.t())[:2].t()
+        uv = (K.reshape(3, 3) @ uv.t())[:2].t()
         return (uv - 0.5) * 2
-    ref = chain(o.double(), d.double(), depth.double()) if False else chain(o, d, depth)
+    # the reference chain in float64 (the fp32 chain it replaces differed from the kernel by its own rounding); the per-pixel running-error bound of the same
+    # projection is in tests/test_gpu_loss_ops.py
+    o64, d64, t64 = (t.detach().double().requires_grad_(True) for t in (o, d, depth))
+    ref = chain(o64, d64, t64, init_ext.double(), intrinsic.double())
     got = INV.warp_project(o, d, depth, init_ext, intrinsic)
     assert float((got - ref).abs().max()) <= 2e-5 * max(1.0, float(ref.abs().max()))
     w = torch.randn(P, 2, generator=g).to(DEV)
-    gr = torch.autograd.grad((ref * w).sum(), [o, d, depth])
+    gr = torch.autograd.grad((ref * w.double()).sum(), [o64, d64, t64])
     gg = torch.autograd.grad((got * w).sum(), [o, d, depth])
     for a, b, name in zip(gg, gr, ('origins', 'dirs', 'depth')):
         assert float((a - b).abs().max()) <= 2e-4 * float(b.abs().max()), name

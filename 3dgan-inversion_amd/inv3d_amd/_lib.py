@@ -262,6 +262,20 @@ class MeshTextureParams(C.Structure):
                 ('power', C.c_int32)]
 
 
+class MeshRasterParams(C.Structure):
+    """eg3d_mesh_raster_params: the z-buffer rasteriser of the mesh previews (eg3d_mesh_raster_query_workspace / eg3d_mesh_raster)."""
+    _fields_ = [('points', C.c_void_p), ('faces', C.c_void_p), ('cams', C.c_void_p), ('uv', C.c_void_p), ('texture', C.c_void_p),
+                ('colors', C.c_void_p), ('normals', C.c_void_p), ('face', C.c_void_p), ('z', C.c_void_p), ('depth', C.c_void_p),
+                ('mask', C.c_void_p), ('bary', C.c_void_p), ('image', C.c_void_p), ('bad_faces', C.c_void_p), ('stats', C.c_void_p),
+                ('workspace', C.c_void_p), ('workspace_bytes', C.c_int64), ('V', C.c_int64), ('F', C.c_int64), ('N', C.c_int32),
+                ('res', C.c_int32), ('Ht', C.c_int32), ('Wt', C.c_int32), ('mode', C.c_int32), ('cull', C.c_int32), ('near', C.c_float),
+                ('background', C.c_float), ('ambient', C.c_float)]
+
+
+RASTER_TEXTURE, RASTER_VERTEX, RASTER_LAMBERT = 0, 1, 2
+RASTER_SMALL = 8                 # EG3D_RASTER_SMALL: the widest pixel range a lane draws alone
+
+
 class CcParams(C.Structure):
     """eg3d_cc_params: connected components of {vol > level} (eg3d_cc_query_workspace / eg3d_cc_label / eg3d_cc_finish / eg3d_cc_keep)."""
     _fields_ = [('vol', C.c_void_p), ('labels', C.c_void_p), ('D0', C.c_int32), ('D1', C.c_int32), ('D2', C.c_int32), ('level', C.c_float),
@@ -482,6 +496,8 @@ _SIGS = {
     'eg3d_mesh_bake': (C.c_int, [C.POINTER(MeshBakeParams), C.c_void_p]),
     'eg3d_mesh_texture_size': (C.c_int, [C.c_int64, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     'eg3d_mesh_texture': (C.c_int, [C.POINTER(MeshTextureParams), C.c_void_p]),
+    'eg3d_mesh_raster_query_workspace': (C.c_int, [C.POINTER(MeshRasterParams), C.POINTER(C.c_int64)]),
+    'eg3d_mesh_raster': (C.c_int, [C.POINTER(MeshRasterParams), C.c_void_p]),
     'eg3d_cc_query_workspace': (C.c_int, [C.POINTER(CcParams), C.POINTER(C.c_int64)]),
     'eg3d_cc_label': (C.c_int, [C.POINTER(CcParams), C.c_void_p]),
     'eg3d_cc_finish': (C.c_int, [C.POINTER(CcParams), C.c_void_p]),

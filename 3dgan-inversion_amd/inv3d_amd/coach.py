@@ -66,7 +66,7 @@ class InversionCoach:
                  start_w_fn: Optional[Callable[[torch.Tensor], torch.Tensor]] = None, sr_fp16: bool = True, gen_mesh: bool = False,
                  mesh_dir: Optional[str] = None, mesh_res: int = 512, mesh_level: float = 10.0, mesh_format: str = '.mrc', mesh_colors: bool = False,
                  mesh_keep: Optional[int] = None, mesh_min_voxels: int = 0, mesh_simplify: Optional[float] = None, mesh_smooth: int = 0,
-                 mesh_texture_tile: int = 8,
+                 mesh_texture_tile: int = 8, mesh_preview: bool = False,
                  do_evaluation: bool = False, eval_dir: Optional[str] = None, lpips_eval_net: Optional[Callable] = None,
                  id_net: Optional[Callable] = None, save_pivot: bool = False, pivot_dir: Optional[str] = None, shape_views: bool = False,
                  on_tuned: Optional[Callable[[str, torch.Tensor], None]] = None,
@@ -90,6 +90,9 @@ class InversionCoach:
         mesh_format='.obj' (no reference counterpart): {name}_pti.obj, {name}_pti.mtl and {name}_pti.png -- the mesh with normals and a
         texture atlas baked from the same views (inference.texture_mesh with `mesh_texture_tile` texels per block side, then
         inference.write_obj); mesh_colors is implied, and mesh_keep / mesh_min_voxels / mesh_simplify / mesh_smooth compose as for '.ply'.
+        `mesh_preview` (no reference counterpart; '.obj' only: it shows the texture): beside the mesh, {name}_pti_preview.png -- the generator's
+        images from the bake views above the textured mesh from the same cameras (inference.mesh_preview_grid) -- and {name}_pti_fidelity.json,
+        inference.mesh_fidelity's dict.  Off by default: a run then writes what it wrote before.
         `do_evaluation` (global_config.do_evaluation): after Phase B render G.synthesis(w_pivot[:, :14], cam[:, :25]) with the tuned generator and
         write metrics.reconstruction_metrics to {eval_dir}/{name}metrics.txt; `lpips_eval_net` (LPIPSAlex) and `id_net` (IDLoss) are built
         once per coach when None.  `save_pivot` writes {pivot_dir}/{name}_ws.npy and {name}_cam.npy; in the reference it only takes effect
@@ -122,6 +125,9 @@ class InversionCoach:
         if int(mesh_texture_tile) != 8 and mesh_format != '.obj':
             raise ValueError("mesh_texture_tile needs mesh_format='.obj': only an '.obj' file carries a texture")
         self.mesh_texture_tile = int(mesh_texture_tile)
+        if mesh_preview and not (gen_mesh and mesh_format == '.obj'):
+            raise ValueError("mesh_preview needs gen_mesh and mesh_format='.obj': the preview shows the textured mesh")
+        self.mesh_preview = bool(mesh_preview)
         if mesh_keep is not None and int(mesh_keep) < 0:
             raise ValueError(f'mesh_keep must be >= 0 or None, got {mesh_keep!r}')
         self.mesh_keep, self.mesh_min_voxels = (None if mesh_keep is None else int(mesh_keep)), int(mesh_min_voxels)
@@ -299,6 +305,8 @@ class InversionCoach:
                     att = texture_mesh(self.G, w_pivot, verts, faces, self.mesh_res, level=self.mesh_level, grid=grid, cameras=self.mesh_cameras(cam),
                                        tile=self.mesh_texture_tile, **self.synth_kwargs)
                     write_obj(path, verts, faces, att['uv'], att['texture'], normals=att['normals'])
+                    if self.mesh_preview:
+                        self.write_mesh_preview(path, w_pivot, verts, faces, att, grid)
                     return path
                 att = color_mesh(self.G, w_pivot, verts, self.mesh_res, level=self.mesh_level, grid=grid, cameras=self.mesh_cameras(cam),
                                  **self.synth_kwargs)
@@ -311,6 +319,18 @@ class InversionCoach:
             grid = density_grid(self.G, w_pivot, res=self.mesh_res)
             write_mrc(path, clean_grid(grid, self.mesh_level, **clean)[0] if clean else grid)
         return path
+
+    def write_mesh_preview(self, path: str, w_pivot: torch.Tensor, verts, faces, att: dict, grid: torch.Tensor) -> Tuple[str, str]:
+        """The preview grid and the fidelity numbers of the textured mesh just written to `path`: ({stem}_preview.png, {stem}_fidelity.json)."""
+        import json
+        from .inference import mesh_fidelity, mesh_preview_grid
+        stem = os.path.splitext(path)[0]
+        png, js = stem + '_preview.png', stem + '_fidelity.json'
+        write_png(png, mesh_preview_grid(self.G, w_pivot, verts, faces, att['uv'], att['texture'], self.mesh_res, **self.synth_kwargs))
+        fid = mesh_fidelity(self.G, w_pivot, verts, faces, att['uv'], att['texture'], grid=grid, level=self.mesh_level, **self.synth_kwargs)
+        with open(js, 'w') as f:
+            f.write(json.dumps(fid) + '\n')
+        return png, js
 
     @staticmethod
     def mesh_cameras(cam: Optional[torch.Tensor]) -> torch.Tensor:

@@ -1998,6 +1998,84 @@ def mesh_texture(points: torch.Tensor, normals: torch.Tensor, faces: torch.Tenso
     return out
 
 
+RASTER_MODES = dict(texture=L.RASTER_TEXTURE, vertex=L.RASTER_VERTEX, lambert=L.RASTER_LAMBERT)
+RASTER_CULL = dict(none=0, back=1)
+
+
+def mesh_raster(points: torch.Tensor, faces: torch.Tensor, cams: torch.Tensor, res: int, mode: str = 'texture', uv: Optional[torch.Tensor] = None,
+                texture: Optional[torch.Tensor] = None, colors: Optional[torch.Tensor] = None, normals: Optional[torch.Tensor] = None,
+                cull: str = 'back', near: float = 0.1, background: float = 1.0, ambient: float = 0.2) -> dict:
+    """Views of the mesh (points fp32 [V,3] in world coordinates, faces int32 [F,3]) from the cameras cams [N,25] at res x res pixels, through
+    a z-buffer (eg3d_mesh_raster; specified operation by operation in include/eg3d_hip.h "Mesh previews").  The pixels are iso_render's and
+    G.synthesis's: pixel (y, x) looks along the same ray.  Perspective-correct interpolation; nothing is clipped: a face with a vertex no further
+    than `near` in front of the camera plane is dropped.  cull='back' drops faces whose right-hand normal points away from the camera.
+      mode='texture'  uv fp32 [F,3,2] and texture uint8 [Ht,Wt,3] as mesh_texture returns them: a bilinear fetch at the interpolated uv
+      mode='vertex'   colors fp32 [V,3] in [-1,1] (mesh_bake's 'color'), interpolated
+      mode='lambert'  normals fp32 [V,3] (mesh_normals), interpolated and normalised: grey v * 2 - 1, v = ambient + (1 - ambient) * max(0, n . -d)
+    Returns a dict:
+      image fp32 [N,3,res,res]  in [-1,1]; a miss takes `background`
+      face  int32 [N,res,res]   the face seen, -1 on a miss
+      z     fp32 [N,res,res]    camera-space depth, 0 on a miss
+      depth fp32 [N,res,res]    distance along the unit ray (iso_render's depth), 0 on a miss
+      mask  uint8 [N,res,res]
+      bary  fp32 [N,res,res,3]  perspective-correct barycentrics of the face's corners
+      small_faces, large_faces  ints: (view, face) pairs drawn one per lane, and by a whole workgroup (more than 8 pixels wide or high)
+    The bytes are a function of the inputs alone.  A face index outside [0, V) raises (no such vertex is read).  Five launches; one host
+    synchronise (the counters)."""
+    points = _mesh_rows(points, 'mesh_raster: points')
+    dev, V = points.device, points.shape[0]
+    faces = _mesh_faces(faces, 'mesh_raster: faces', dev)
+    F, res = faces.shape[0], int(res)
+    L.require_cuda(cams)
+    if cams.dim() != 2 or cams.shape[1] != 25 or cams.shape[0] < 1 or cams.device != dev:
+        raise L.Eg3dHipError(f'mesh_raster: cameras [N >= 1, 25] on {dev}, got {tuple(cams.shape)} on {cams.device}')
+    cams = cams.to(dtype=torch.float32).contiguous()
+    N = cams.shape[0]
+    if mode not in RASTER_MODES or cull not in RASTER_CULL:
+        raise L.Eg3dHipError(f'mesh_raster: mode {sorted(RASTER_MODES)} and cull {sorted(RASTER_CULL)}, got {mode!r}, {cull!r}')
+    if res < 1 or not float(near) > 0.0 or not 0.0 <= float(ambient) <= 1.0:
+        raise L.Eg3dHipError(f'mesh_raster: res >= 1, near > 0 and ambient in [0, 1], got {res}, {near!r}, {ambient!r}')
+    p = L.MeshRasterParams(points=points.data_ptr(), faces=faces.data_ptr(), cams=cams.data_ptr(), V=V, F=F, N=N, res=res, mode=RASTER_MODES[mode],
+                           cull=RASTER_CULL[cull], near=float(near), background=float(background), ambient=float(ambient))
+    if mode == 'texture':
+        if uv is None or texture is None:
+            raise L.Eg3dHipError("mesh_raster: mode='texture' needs uv and texture")
+        L.require_cuda(uv, texture)
+        if tuple(uv.shape) != (F, 3, 2) or uv.dtype != torch.float32 or not uv.is_contiguous() or uv.device != dev:
+            raise L.Eg3dHipError(f'mesh_raster: uv must be contiguous fp32 [{F}, 3, 2] on {dev}, got {tuple(uv.shape)} {uv.dtype} on {uv.device}')
+        if texture.dim() != 3 or texture.shape[2] != 3 or min(texture.shape[:2]) < 2 or texture.dtype != torch.uint8 or not texture.is_contiguous() \
+                or texture.device != dev:
+            raise L.Eg3dHipError(f'mesh_raster: texture must be contiguous uint8 [Ht >= 2, Wt >= 2, 3] on {dev}, got {tuple(texture.shape)} '
+                                 f'{texture.dtype} on {texture.device}')
+        p.uv, p.texture, p.Ht, p.Wt = uv.data_ptr(), texture.data_ptr(), texture.shape[0], texture.shape[1]
+    elif mode == 'vertex':
+        if colors is None:
+            raise L.Eg3dHipError("mesh_raster: mode='vertex' needs colors")
+        p.colors = _mesh_rows(colors, 'mesh_raster: colors', dev, V).data_ptr()
+    else:
+        if normals is None:
+            raise L.Eg3dHipError("mesh_raster: mode='lambert' needs normals")
+        p.normals = _mesh_rows(normals, 'mesh_raster: normals', dev, V).data_ptr()
+    lib = L.lib()
+    nbytes = C.c_int64(0)
+    L.check(lib.eg3d_mesh_raster_query_workspace(C.byref(p), C.byref(nbytes)), 'mesh_raster_query_workspace')
+    ws = torch.empty(nbytes.value, dtype=torch.uint8, device=dev)
+    out = dict(image=torch.empty((N, 3, res, res), dtype=torch.float32, device=dev), face=torch.empty((N, res, res), dtype=torch.int32, device=dev),
+               z=torch.empty((N, res, res), dtype=torch.float32, device=dev), depth=torch.empty((N, res, res), dtype=torch.float32, device=dev),
+               mask=torch.empty((N, res, res), dtype=torch.uint8, device=dev), bary=torch.empty((N, res, res, 3), dtype=torch.float32, device=dev))
+    counts = torch.empty(3, dtype=torch.int32, device=dev)
+    p.workspace, p.workspace_bytes = ws.data_ptr(), nbytes.value
+    p.bad_faces, p.stats = counts.data_ptr(), counts.data_ptr() + 4
+    for k, t in out.items():
+        setattr(p, k, t.data_ptr())
+    L.check(lib.eg3d_mesh_raster(C.byref(p), L.stream_ptr()), 'mesh_raster')
+    n_bad, n_small, n_large = counts.tolist()
+    if n_bad:
+        raise L.Eg3dHipError(f'mesh_raster: {n_bad} face(s) with an index outside [0, {V})')
+    out['small_faces'], out['large_faces'] = n_small, n_large
+    return out
+
+
 def _cc_grid(vol: torch.Tensor, what: str) -> torch.Tensor:
     L.require_cuda(vol)
     if vol.dim() != 3 or vol.dtype != torch.float32:

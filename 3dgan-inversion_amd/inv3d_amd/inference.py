@@ -21,6 +21,9 @@ G.mapping / ImportanceRenderer.run_model on the gfx950 kernels.
                                   smoothing of the extracted mesh (hipops.mesh_simplify / mesh_smooth), between marching cubes and the attributes
   texture_mesh, write_obj      no reference counterpart: a per-face texture atlas baked from color_mesh's views (hipops.mesh_texture), so that
                                   colour resolution no longer follows the vertex count, and the OBJ + MTL + image that carry it
+  render_mesh, render_mesh_orbit, no reference counterpart: views of the exported mesh itself from the generator's cameras (hipops.mesh_raster,
+  mesh_fidelity, mesh_preview_grid  a z-buffer rasteriser), registered pixel for pixel with G.synthesis and render_shape; the PSNR of the
+                                  textured mesh against the generator's views and its silhouette agreement with the iso-surface marcher
 
 Differences from the reference that do not change results: the tri-planes of a fixed latent are synthesised once per orbit / per grid
 instead of once per frame / per chunk (the reference re-runs the backbone every time), and grid coordinates are generated per chunk on
@@ -455,6 +458,147 @@ def texture_mesh(G, ws: torch.Tensor, verts: torch.Tensor, faces: torch.Tensor, 
     uv = tex['uv'] if wfaces is faces else tex['uv'][:, [0, 2, 1]].contiguous()
     out.update(color=baked['color'], colors=baked['rgb'], views=baked['views'], texture=tex['texture'], uv=uv, texture_views=tex['views'])
     return out
+
+
+def normals_to_world(G, normals: torch.Tensor, res: int) -> torch.Tensor:
+    """The inverse of normals_to_mesh: normals [V,3] in the frame of the mesh vertices (what a PLY or an OBJ carries) in world coordinates."""
+    cols, _ = _mesh_axes(G, res)
+    world = torch.empty_like(normals, dtype=torch.float32)
+    for k, (w, _, s) in enumerate(cols):
+        world[:, w] = -normals[:, k].float() if s < 0 else normals[:, k].float()
+    return world
+
+
+RENDER_MESH_MODES = dict(texture=('uv', 'texture'), vertex=('colors',), lambert=('normals',))
+
+
+@torch.no_grad()
+def render_mesh(G, verts: torch.Tensor, faces: torch.Tensor, cameras: torch.Tensor, res: Optional[int] = None, mode: str = 'texture',
+                uv: Optional[torch.Tensor] = None, texture: Optional[torch.Tensor] = None, colors: Optional[torch.Tensor] = None,
+                normals: Optional[torch.Tensor] = None, grid_res: Optional[int] = None, supersample: int = 1, **kw) -> dict:
+    """Views of an extracted mesh from `cameras` [N,25] through the rasteriser (hipops.mesh_raster; no reference counterpart): the mesh as the
+    exporters hold it -- verts [V,3] and faces int32 [F,3] in the frame of extract_mesh / write_ply at grid resolution `grid_res` (required: it
+    fixes the map to world coordinates), and per mode
+      'texture'  uv [F,3,2] and texture uint8 [Ht,Wt,3] of texture_mesh (what write_obj writes)
+      'vertex'   colors [V,3]: color_mesh's fp32 'color' in [-1,1], or its uint8 'colors' (shown at the centre of their truncation interval)
+      'lambert'  normals [V,3] in the frame of the vertices (color_mesh's 'normals', what a PLY carries): a grey headlight view
+    The vertices go through mesh_to_world; where that map mirrors, the faces are re-wound and the uv rows re-ordered with them, as texture_mesh
+    does.  res defaults to the generator's image resolution, so a frame registers pixel for pixel with G.synthesis(ws, c)['image'] and with
+    render_shape.  Returns hipops.mesh_raster's dict (image, face, z, depth, mask, bary, small_faces, large_faces; face indexes `faces` as
+    passed, bary follows the re-wound corner order).  supersample = s > 1 renders at s * res and returns only 'image' [N,3,res,res], averaged
+    over s x s blocks (torch's avg_pool2d), and 'coverage' [N,res,res], the blocks' mean of mask.  Further keywords go to hipops.mesh_raster
+    (cull, near, background, ambient)."""
+    from .hipops import mesh_raster
+    if mode not in RENDER_MESH_MODES:
+        raise ValueError(f'render_mesh: mode {sorted(RENDER_MESH_MODES)}, got {mode!r}')
+    given = dict(uv=uv, texture=texture, colors=colors, normals=normals)
+    missing = [k for k in RENDER_MESH_MODES[mode] if given[k] is None]
+    if missing:
+        raise ValueError(f'render_mesh: mode {mode!r} needs {" and ".join(missing)}')
+    if grid_res is None or int(grid_res) < 2:
+        raise ValueError('render_mesh: grid_res, the resolution of the grid the mesh was extracted from, is required')
+    s = int(supersample)
+    if s < 1 or s != supersample:
+        raise ValueError(f'render_mesh: supersample is an integer >= 1, got {supersample!r}')
+    res = int(G.img_resolution if res is None else res)
+    dev = verts.device
+    faces = faces.to(device=dev, dtype=torch.int32).contiguous()
+    world, wfaces = mesh_to_world(G, verts, faces, int(grid_res))
+    rewound = wfaces is not faces
+    args = {}
+    if mode == 'texture':
+        uv = uv.to(device=dev, dtype=torch.float32)
+        args = dict(uv=(uv[:, [0, 2, 1]] if rewound else uv).contiguous(), texture=texture.to(dev).contiguous())
+    elif mode == 'vertex':
+        colors = colors.to(dev)
+        args = dict(colors=((colors.float() + (0.5 - 128.0)) / 127.5 if colors.dtype == torch.uint8 else colors.float()).contiguous())
+    else:
+        args = dict(normals=normals_to_world(G, normals.to(dev), int(grid_res)).contiguous())
+    out = mesh_raster(world.contiguous(), wfaces, cameras.to(dev).float().contiguous(), res * s, mode=mode, **args, **kw)
+    if s == 1:
+        return out
+    pool = torch.nn.functional.avg_pool2d
+    return dict(image=pool(out['image'], s), coverage=pool(out['mask'].float().unsqueeze(1), s)[:, 0])
+
+
+@torch.no_grad()
+def render_mesh_orbit(G, verts: torch.Tensor, faces: torch.Tensor, num_frames: int = 240, cameras: Optional[torch.Tensor] = None,
+                      **kw) -> Iterator[torch.Tensor]:
+    """Yields one [3,res,res] frame of the mesh per camera of orbit_cameras (or `cameras`), the companion of render_shape_orbit: one
+    render_mesh call per frame, so the workspace is that of one view whatever the orbit's length.  Keywords as render_mesh."""
+    dev = verts.device
+    cams = orbit_cameras(num_frames, device=dev) if cameras is None else cameras.to(dev)
+    for i in range(cams.shape[0]):
+        yield render_mesh(G, verts, faces, cams[i:i + 1], **kw)['image'][0]
+
+
+def fidelity_cameras(device='cpu') -> torch.Tensor:
+    """mesh_fidelity's default views: bake_cameras() and three views of the orbit, which no default bake has seen."""
+    return torch.cat([bake_cameras(device=device), orbit_cameras(3, device=device)])
+
+
+@torch.no_grad()
+def mesh_fidelity(G, ws: torch.Tensor, verts: torch.Tensor, faces: torch.Tensor, uv: torch.Tensor, texture: torch.Tensor,
+                  cameras: Optional[torch.Tensor] = None, res: Optional[int] = None, grid_res: Optional[int] = None, level: float = 10.0,
+                  grid: Optional[torch.Tensor] = None, raster_kwargs: Optional[dict] = None, **synthesis_kwargs) -> dict:
+    """How faithful the textured mesh is to the generator it came from (no reference counterpart), per view of `cameras` (default
+    fidelity_cameras()) and as means:
+      psnr            the textured frame (render_mesh, mode 'texture', white background) against G.synthesis's image, both mapped to [0,1]
+                      (inversion.psnr_01); the generator's background counts against the mesh
+      psnr_covered    the same over the pixels the mesh covers
+      silhouette_iou  the rasteriser's mask against render_shape's mask of the density surface at `level`
+    Returns dict(psnr=[...], psnr_covered=[...], silhouette_iou=[...], mean_psnr, mean_psnr_covered, mean_silhouette_iou, views) of floats.
+    grid_res: the grid the mesh was extracted from (default: grid's side); `grid` is built at grid_res unless passed.  A view the mesh does
+    not cover at all has psnr_covered nan and is left out of that mean.  Further keywords go to G.synthesis."""
+    from .inversion import psnr_01
+    dev = ws.device
+    if grid is None:
+        if grid_res is None:
+            raise ValueError('mesh_fidelity: grid or grid_res')
+        grid = density_grid(G, ws, res=int(grid_res))
+    grid_res = int(grid.shape[0] if grid_res is None else grid_res)
+    cams = (fidelity_cameras(dev) if cameras is None else cameras.to(dev)).float().contiguous()
+    kw = dict(noise_mode='const', **synthesis_kwargs)
+    out = dict(psnr=[], psnr_covered=[], silhouette_iou=[])
+    bricks = None
+    for i in range(cams.shape[0]):
+        c = cams[i:i + 1]
+        img = G.synthesis(ws[:1], c, cache_backbone=(i == 0), use_cached_backbone=(i > 0), **kw)['image'].float()
+        r = int(img.shape[-1] if res is None else res)
+        if r != img.shape[-1]:
+            raise ValueError(f'mesh_fidelity: res {r} is not the resolution of the generator\'s images, {img.shape[-1]}')
+        m = render_mesh(G, verts, faces, c, res=r, mode='texture', uv=uv, texture=texture, grid_res=grid_res, **(raster_kwargs or {}))
+        shape = render_shape(G, ws, c, res=r, level=level, grid=grid, bricks=bricks)
+        bricks = shape['bricks']
+        mm, sm = m['mask'][0] > 0, shape['mask'][0] > 0
+        out['psnr'].append(float(psnr_01(m['image'], img)))
+        sel = mm.unsqueeze(0).expand(3, -1, -1)
+        out['psnr_covered'].append(float(psnr_01(m['image'][0][sel], img[0][sel])) if bool(mm.any()) else float('nan'))
+        union = int((mm | sm).sum())
+        out['silhouette_iou'].append(int((mm & sm).sum()) / union if union else 1.0)
+    for k in ('psnr', 'psnr_covered', 'silhouette_iou'):
+        vals = [v for v in out[k] if v == v]
+        out['mean_' + k] = sum(vals) / len(vals) if vals else float('nan')
+    out['views'] = int(cams.shape[0])
+    return out
+
+
+@torch.no_grad()
+def mesh_preview_grid(G, ws: torch.Tensor, verts: torch.Tensor, faces: torch.Tensor, uv: torch.Tensor, texture: torch.Tensor, grid_res: int,
+                      cameras: Optional[torch.Tensor] = None, nrow: int = 5, raster_kwargs: Optional[dict] = None, **synthesis_kwargs) -> torch.Tensor:
+    """uint8 [H',W',3] on the device for video.write_png: the generator's image from every camera of `cameras` (default bake_cameras()) in rows
+    of `nrow`, and under them the textured mesh from the same cameras (hipops.image_grid_u8, padding 2)."""
+    from .hipops import image_grid_u8
+    dev = ws.device
+    cams = (bake_cameras(device=dev) if cameras is None else cameras.to(dev)).float().contiguous()
+    kw = dict(noise_mode='const', **synthesis_kwargs)
+    gen = torch.cat([G.synthesis(ws[:1], cams[i:i + 1], cache_backbone=(i == 0), use_cached_backbone=(i > 0), **kw)['image'].float()
+                     for i in range(cams.shape[0])])
+    mesh = torch.cat([render_mesh(G, verts, faces, cams[i:i + 1], res=gen.shape[-1], mode='texture', uv=uv, texture=texture, grid_res=grid_res,
+                                  **(raster_kwargs or {}))['image'] for i in range(cams.shape[0])])
+    pad = (-cams.shape[0]) % int(nrow)                  # fill the generator's last row, so that the mesh rows start on a row of their own
+    blank = torch.ones((pad, *gen.shape[1:]), device=dev)
+    return image_grid_u8(torch.cat([gen, blank, mesh]).contiguous(), nrow=int(nrow), padding=2, pad_value=128)
 
 
 def _host(a, dtype):

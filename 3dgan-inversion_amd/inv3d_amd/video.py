@@ -7,7 +7,9 @@
                                   'idx1' index) written here, the frames are the GPU encoder's JFIF files
   write_png                    <- PIL.Image.fromarray(...).save(png), single_id_coach.py:60,83 (zlib only)
   write_orbit_video            <- gen_interp_video(G, w_pivot, path), single_id_coach.py:61-62,84-85
-  look_at_small, pivot_grid    <- BaseCoach.forward(ws, needs_img_grid='small', grid_num=5, need_gt_ingrid=(target, cam)) with look_at /
+  write_mesh_video             no reference counterpart: the same orbit of the exported mesh itself (inference.render_mesh), alone or beside the
+                                  generator's frame or the density surface
+  look_at_small, pivot_grid    <-BaseCoach.forward(ws, needs_img_grid='small', grid_num=5, need_gt_ingrid=(target, cam)) with look_at /
                                   gen_eyes(num='small'), base_coach.py:128-159,216-291
 
 Everything but the rendering and hipops.jpeg_encode / image_grid_u8 is host code on the standard library."""
@@ -239,6 +241,73 @@ def write_orbit_video(G, ws: torch.Tensor, path: str, num_frames: int = 240, ima
     try:
         for i, frame in enumerate(render_orbit(G, ws, num_frames=num_frames, image_mode=image_mode, **synthesis_kwargs)):
             pending.append(beside(i, frame.float()) if shape else frame.float().clone())      # (the frame may be a view of a buffer the next render reuses)
+            if len(pending) == batch:
+                flush()
+        if pending:
+            flush()
+    finally:
+        if writer is not None:
+            writer.close()
+    return n
+
+
+@torch.no_grad()
+def write_mesh_video(G, mesh: dict, path: str, num_frames: int = 240, beside: Optional[str] = None, ws: Optional[torch.Tensor] = None, fps: int = 60,
+                     quality: int = 90, batch: int = 16, cameras: Optional[torch.Tensor] = None, shape_kwargs: Optional[dict] = None,
+                     synthesis_kwargs: Optional[dict] = None, **render_kwargs) -> int:
+    """An orbit of the exported mesh as a Motion-JPEG AVI at `path` (no reference counterpart): inference.render_mesh_orbit's frames through
+    the batching, encoder and container of write_orbit_video.  `mesh` holds what render_mesh takes: verts, faces, grid_res, and uv + texture
+    (mode 'texture', the default when both are there), colors or normals; render_kwargs (mode, res, supersample, cull, background, ...) go to
+    render_mesh.  beside='image': every frame is generator | mesh, twice the width (G.synthesis of `ws` from the same camera; the mesh is drawn
+    at the image's resolution);  beside='shape': density surface | mesh (inference.render_shape of `ws`; shape_kwargs: grid, grid_res, level,
+    ...; the grid is built once).  Returns the number of frames written."""
+    from .hipops import jpeg_encode
+    from .inference import density_grid, orbit_cameras, render_mesh, render_shape
+    if beside not in (None, 'image', 'shape'):
+        raise ValueError(f"write_mesh_video: beside None, 'image' or 'shape', got {beside!r}")
+    if int(num_frames) < 1 or batch < 1:
+        raise ValueError('write_mesh_video: num_frames >= 1 and batch >= 1')
+    if beside is not None and ws is None:
+        raise ValueError(f'write_mesh_video: beside={beside!r} needs the latent ws')
+    verts, faces = mesh['verts'], mesh['faces']
+    dev = verts.device
+    kw = dict(render_kwargs)
+    kw.setdefault('mode', 'texture' if mesh.get('uv') is not None and mesh.get('texture') is not None else ('vertex' if mesh.get('colors') is not None else 'lambert'))
+    for k in ('uv', 'texture', 'colors', 'normals', 'grid_res'):
+        if mesh.get(k) is not None:
+            kw.setdefault(k, mesh[k])
+    cams = orbit_cameras(int(num_frames), device=dev) if cameras is None else cameras.to(dev)
+    skw, state = dict(shape_kwargs or {}), {}
+    if beside == 'shape':
+        grid = skw.pop('grid', None)
+        state = dict(grid=density_grid(G, ws, res=skw.pop('grid_res', 512)) if grid is None else grid, bricks=skw.pop('bricks', None))
+    gkw = dict(noise_mode='const', **(synthesis_kwargs or {}))
+    writer, pending, n = None, [], 0
+
+    def flush():
+        nonlocal writer, n
+        frames = torch.stack(pending)
+        data, offsets = jpeg_encode(frames, quality=quality)
+        host, off = data.cpu().numpy(), offsets.tolist()
+        if writer is None:
+            writer = MjpegAviWriter(path, frames.shape[-1], frames.shape[-2], fps=fps)
+        for i in range(len(pending)):
+            writer.write(host[off[i]:off[i + 1]].tobytes())
+        n += len(pending)
+        pending.clear()
+    try:
+        for i in range(cams.shape[0]):
+            c = cams[i:i + 1]
+            left = None
+            if beside == 'image':
+                left = G.synthesis(ws[:1], c, cache_backbone=(i == 0), use_cached_backbone=(i > 0), **gkw)['image'][0].float()
+                kw['res'] = left.shape[-1]
+            frame = render_mesh(G, verts, faces, c, **kw)['image'][0]
+            if beside == 'shape':
+                out = render_shape(G, ws, c, res=frame.shape[-1], grid=state['grid'], bricks=state['bricks'], **skw)
+                state['bricks'] = out['bricks']
+                left = out['shade'][0]
+            pending.append(frame if left is None else torch.cat([left, frame], dim=-1))
             if len(pending) == batch:
                 flush()
         if pending:

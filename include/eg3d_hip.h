@@ -1210,6 +1210,94 @@ int eg3d_mesh_texture_size(int64_t F, int32_t tile, int32_t* Ht, int32_t* Wt);
 int eg3d_mesh_texture(const eg3d_mesh_texture_params* p, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Mesh previews: a z-buffer rasteriser for the exported meshes (csrc/mesh_raster.hip).  No reference counterpart (the reference has no
+ *   mesh renderer).  It takes the mesh as the exporters hold it (world points, int32 faces, eg3d_mesh_texture's uv and atlas, eg3d_mesh_bake's
+ *   colours, eg3d_mesh_normals' normals) and the generator's cameras, and its frames register pixel for pixel with eg3d_iso_render's and with
+ *   the generator's images.  Exactly these fp32 and integer operations in this order, no contraction; tests/support/raster_ref.py restates them
+ *   in numpy and the outputs are compared bit for bit.  The only atomics are integer ones (a 64-bit unsigned minimum per covered pixel, and
+ *   integer adds on counters and a queue no output depends on): every output is a function of the inputs alone, bit-identical between runs and
+ *   between the two builds.  V vertices, F faces, N views, res x res pixels; camera c[25] named as in "Shape views".
+ *
+ * Vertex stage, per view and vertex p:
+ *   q_i = p_i - o_i;  c_j = (m_0j q_0 + m_1j q_1) + m_2j q_2;  xl = c_0 / c_2, yl = c_1 / c_2;  yc = yl * fy + cy;
+ *   xc = ((xl * fx + cx) - (cy * sk) / fy) + (sk * yc) / fy   (steps 1-2 of eg3d_mesh_bake without t);
+ *   px = xc * float(res) - 0.5, py = yc * float(res) - 0.5   (pixel (y, x) has its centre at px = x, py = y).
+ *   valid iff c_2 > near and -32768 <= px <= 32768 and -32768 <= py <= 32768 (explicit comparisons: a NaN is invalid).
+ *   X = int32(floor(px * 256 + 0.5)), Y = int32(floor(py * 256 + 0.5))   (8 sub-pixel bits);  z = c_2.
+ * Face stage, per view and face f with corners S_k = (X_k, Y_k), z_k:
+ *   orient(A, B, P) = (B_x - A_x) * (P_y - A_y) - (B_y - A_y) * (P_x - A_x) in int64 (|coordinate| <= 2^23 + 1: no overflow).
+ *   Dropped: an index outside [0, V) (no vertex of the face is read; counted once per face in *bad_faces, a device int32 that may be NULL);
+ *   a vertex invalid in this view (nothing is clipped);  area2 = orient(S_0, S_1, S_2) = 0;  with cull = 1, area2 > 0.
+ *   Front faces have area2 < 0: with a proper-rotation cam2world the camera frame (x right, y down, z forward) is right-handed and px, py grow
+ *   with x, y (fx, fy > 0), so a face whose right-hand normal (v_1 - v_0) x (v_2 - v_0) points at the camera -- e.g. (0,0,1), (0,1,1), (1,0,1)
+ *   in camera coordinates, normal (0,0,-1) -- has area2 = 0 * 0 - 1 * 1 < 0.
+ *   Pixels x in [max(ceil(min_k X_k / 256), 0), min(floor(max_k X_k / 256), res - 1)], y likewise (an empty range drops the face).  P = (256 x,
+ *   256 y);  E_0 = orient(S_1, S_2, P), E_1 = orient(S_2, S_0, P), E_2 = orient(S_0, S_1, P), each negated when area2 < 0.  Covered iff all
+ *   three are >= 0 (edges inclusive: a shared edge leaves no hole; the depth test settles the doubly covered pixels).
+ *   l_k = float(E_k) / float(|area2|) (int64 to fp32, round to nearest even);  w_k = l_k / z_k;  W = (w_0 + w_1) + w_2;  kept iff 0 < W < inf;
+ *   zp = 1 / W;  key = (uint64(bits(zp)) << 32) | f;  the pixel's uint64, all ones at the start, takes the minimum of the keys: the nearest face
+ *   wins, equal depth goes to the lower face index, in whatever order the faces arrive (one 64-bit unsigned atomic minimum).
+ * Resolve stage, per pixel: all ones is a miss.  Otherwise f = the low 32 bits, w_k and W as above, zp = 1 / W, b_k = w_k / W.
+ *   Ray lift of pixel (y, x) as eg3d_iso_render forms it: xc = (x + 0.5) / res, yc = (y + 0.5) / res;
+ *   xl = (((xc - cx) + (cy * sk) / fy) - (sk * yc) / fy) / fx;  yl = (yc - cy) / fy;  w_i, e_i, d_i as there.
+ *   mix(A) = (b_0 A_0 + b_1 A_1) + b_2 A_2 of the three corners' values, per component.
+ *   Outputs (each may be NULL): face int32 [N][res][res], -1 on a miss;  z fp32 [N][res][res] = zp, 0 on a miss;  depth fp32 [N][res][res] =
+ *   zp * sqrt((xl^2 + yl^2) + 1), the distance along the unit ray that eg3d_iso_render's depth measures, 0 on a miss;  mask uint8 [N][res][res];
+ *   bary fp32 [N][res][res][3] = b, 0 on a miss;  image fp32 [N][3][res][res] in [-1, 1], `background` on a miss:
+ *     EG3D_RASTER_TEXTURE  (u, v) = mix of uv [F][3][2] rows of face f;  tx = clamp(u * float(Wt) - 0.5, 0, Wt - 1) (p > 0 ? p : 0, then p < h ?
+ *                          p : h: NaN gives 0), ty with Ht;  x0 = min(int(floor(tx)), Wt - 2), fx = tx - float(x0), y0, fy likewise;
+ *                          lerp(a, b, f) = a + f * (b - a) (not clamped) over the uint8 texels of texture [Ht][Wt][3] converted to float:
+ *                          colour_j = lerp(lerp(T[y0][x0], T[y0][x0+1], fx), lerp(T[y0+1][x0], T[y0+1][x0+1], fx), fy);
+ *                          image_j = (colour_j - 127.5) / 127.5
+ *     EG3D_RASTER_VERTEX   image_j = mix of colors [V][3], column j
+ *     EG3D_RASTER_LAMBERT  n = mix of normals [V][3];  len = sqrt((n_0^2 + n_1^2) + n_2^2);  n = n / len when 0 < len < inf, else 0;
+ *                          s = -((n_0 d_0 + n_1 d_1) + n_2 d_2);  v = ambient + (1 - ambient) * (s > 0 ? s : 0);  the three channels = v * 2 - 1
+ *   stats (device int32[2], may be NULL): [0] = (view, face) pairs drawn one per lane, [1] = pairs drawn by a workgroup.
+ * Work distribution: a (view, face) pair whose pixel range is at most EG3D_RASTER_SMALL pixels wide and high is drawn by its own lane; a
+ *   larger one is queued and drawn by a workgroup, one lane per pixel of 8 x 8 tiles.  The split changes no output.
+ * Workspace (lent by the caller; the library allocates nothing): eg3d_mesh_raster_query_workspace, host only, from V, F, N, res: the
+ *   z-buffer (8 bytes a pixel), the projected vertices (16 bytes per view and vertex), the queue (8 bytes per view and face), the counters.
+ *   16-byte aligned.  With every output, bad_faces and stats NULL: ok, no launch.  F = 0 is ok: every pixel is a miss.
+ * Errors, before any launch: EG3D_ERR_INVALID (null params / cams / workspace, null points with V > 0, null faces with F > 0, null texture,
+ *   or null uv with F > 0, in texture mode, null colors / normals with V > 0 in their mode, V or F < 0, N or res < 1, near <= 0 or not
+ *   finite, unknown mode or cull, ambient outside [0, 1], a texture side < 2, a short or misaligned workspace), EG3D_ERR_UNSUPPORTED (res >
+ *   16384, N > 65535, a texture side > 16384), EG3D_ERR_TOO_LARGE (V or F >= 2^31, N * F >= 2^31: render the views in batches).
+ */
+#define EG3D_RASTER_TEXTURE 0
+#define EG3D_RASTER_VERTEX 1
+#define EG3D_RASTER_LAMBERT 2
+#define EG3D_RASTER_SMALL 8
+typedef struct eg3d_mesh_raster_params {
+    const float* points;               /* [V][3] world */
+    const int32_t* faces;              /* [F][3] */
+    const float* cams;                 /* [N][25] */
+    const float* uv;                   /* [F][3][2]: texture mode */
+    const uint8_t* texture;            /* [Ht][Wt][3]: texture mode */
+    const float* colors;               /* [V][3]: vertex mode */
+    const float* normals;              /* [V][3] world: lambert mode */
+    int32_t* face;                     /* [N][res][res] or NULL */
+    float* z;                          /* [N][res][res] or NULL */
+    float* depth;                      /* [N][res][res] or NULL */
+    uint8_t* mask;                     /* [N][res][res] or NULL */
+    float* bary;                       /* [N][res][res][3] or NULL */
+    float* image;                      /* [N][3][res][res] or NULL */
+    int32_t* bad_faces;                /* device int32[1] or NULL */
+    int32_t* stats;                    /* device int32[2] or NULL */
+    void* workspace;                   /* eg3d_mesh_raster_query_workspace's bytes */
+    int64_t workspace_bytes;
+    int64_t V, F;
+    int32_t N, res;
+    int32_t Ht, Wt;                    /* texture mode */
+    int32_t mode;                      /* EG3D_RASTER_TEXTURE | _VERTEX | _LAMBERT */
+    int32_t cull;                      /* 0 none, 1 back faces */
+    float near;                        /* camera-space depth a vertex must exceed, > 0 */
+    float background;
+    float ambient;
+} eg3d_mesh_raster_params;
+int eg3d_mesh_raster_query_workspace(const eg3d_mesh_raster_params* p, int64_t* workspace_bytes);
+int eg3d_mesh_raster(const eg3d_mesh_raster_params* p, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Grid components: connected-component labelling of {vol > level} and removal of components (csrc/grid_components.hip).  No reference
  *   counterpart (the reference exports every blob above the level).  tests/support/cc_ref.py restates the result in numpy; the outputs are
  *   compared exactly.

@@ -3,7 +3,7 @@ convert_sdf_samples_to_ply, shape_utils.py:40-100), on the GPU kernels of this p
 
   python tools/extract_mesh.py --ws pivot_ws.npy --out face.ply [--weights G.safetensors] [--res 512] [--level 10] [--mrc face.mrc]
                                [--colors [--views N_YAW N_PITCH] [--radiance]] [--keep N] [--min-voxels M] [--connectivity {6,26}]
-                               [--simplify CELL] [--smooth N] [--obj [--tile T] [--texture-format {png,jpg}]]
+                               [--simplify CELL] [--smooth N] [--obj [--tile T] [--texture-format {png,jpg}]] [--preview PATH]
 
 --weights: a generator archive (inv3d_amd.weights, tools/convert_eg3d_pickle.py); without it, the full-size synthetic generator
 (inv3d_amd.synthetic, seed --seed).  --ws: a [1, num_ws, w_dim] (or [num_ws, w_dim]) .npy latent, e.g. the reference's {image}_ws.npy.
@@ -19,7 +19,11 @@ reference counterpart): CELL 2 leaves about a fifth of the faces.  --smooth N ru
 --obj writes a textured mesh instead of a PLY (inference.texture_mesh / write_obj; no reference counterpart): --out names the .obj, and its
 .mtl and .png (or .jpg) land beside it.  Two faces share a block of T x T texels (--tile, default 8) baked from the same views as --colors;
 a mesh that is too large for a 16384-texel atlas side wants --simplify first.  The atlas size and the share of its texels coloured from
-views are printed."""
+views are printed.
+--preview PATH (with --obj or --colors; no reference counterpart) looks at the mesh just written through the rasteriser (inference.render_mesh):
+a .png is a grid of the bake cameras, the generator's images above and the mesh below; an .avi is an orbit, generator | mesh.  With --obj the
+mesh is drawn with its texture and inference.mesh_fidelity's dict is printed as one JSON line (PSNR against the generator's views, silhouette
+agreement with the density surface); with --colors it is drawn with its vertex colours."""
 import argparse
 import os
 import sys
@@ -52,7 +56,10 @@ def main():
     ap.add_argument('--obj', action='store_true', help='write --out as an OBJ with an MTL and a texture atlas beside it')
     ap.add_argument('--tile', type=int, default=8, metavar='T', help='texels per side of the block two faces share (4..64)')
     ap.add_argument('--texture-format', default='png', choices=('png', 'jpg'))
+    ap.add_argument('--preview', default=None, metavar='PATH', help='a .png grid or an .avi orbit of the written mesh, generator beside mesh (with --obj or --colors)')
     a = ap.parse_args()
+    if a.preview is not None and (not (a.obj or a.colors) or os.path.splitext(a.preview)[1].lower() not in ('.png', '.avi')):
+        ap.error('--preview takes a .png or .avi path and goes with --obj or --colors: a bare mesh has nothing to show')
     if (a.simplify is not None and not a.simplify > 0) or a.smooth < 0:
         ap.error('--simplify takes a positive cell size, --smooth a count >= 0')
     if not 4 <= a.tile <= 64 or (a.obj and a.radiance):
@@ -117,6 +124,24 @@ def main():
         INF.write_ply(a.out, verts, faces)
     if a.mrc:
         INF.write_mrc(a.mrc, grid)
+    if a.preview is not None:
+        import json
+        from inv3d_amd import video as VID
+        how = dict(mode='texture', uv=att['uv'], texture=att['texture']) if a.obj else dict(mode='vertex', colors=att['color'])
+        if a.preview.lower().endswith('.png'):
+            if a.obj:
+                tiles = INF.mesh_preview_grid(G, ws, verts, faces, att['uv'], att['texture'], a.res, cameras=cams, nrow=a.views[0])
+            else:
+                from inv3d_amd.hipops import image_grid_u8
+                gen = torch.cat([G.synthesis(ws[:1], cams[i:i + 1], noise_mode='const')['image'].float() for i in range(cams.shape[0])])
+                mesh = INF.render_mesh(G, verts, faces, cams, res=gen.shape[-1], grid_res=a.res, **how)['image']
+                tiles = image_grid_u8(torch.cat([gen, mesh]).contiguous(), nrow=cams.shape[0], padding=2, pad_value=128)
+            VID.write_png(a.preview, tiles)
+        else:
+            VID.write_mesh_video(G, dict(verts=verts, faces=faces, grid_res=a.res, **{k: v for k, v in how.items() if k != 'mode'}), a.preview,
+                                 beside='image', ws=ws, mode=how['mode'])
+        if a.obj:
+            print(json.dumps(INF.mesh_fidelity(G, ws, verts, faces, att['uv'], att['texture'], grid=grid, level=a.level)))
     print(f'{a.out}: {verts.shape[0]} vertices, {faces.shape[0]} faces ({a.res}^3 grid, level {a.level}; grid + march {dt * 1e3:.1f} ms{note})')
 
 

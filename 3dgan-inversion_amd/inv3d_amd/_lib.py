@@ -335,6 +335,13 @@ JPEG_F32, JPEG_U8 = 0, 1
 JPEG_444, JPEG_420 = 0, 1
 
 
+class PngParams(C.Structure):
+    """eg3d_png_params: PNG encoder (eg3d_png_query_workspace / eg3d_png_encode / eg3d_png_pack)."""
+    _fields_ = [('img', C.c_void_p), ('workspace', C.c_void_p), ('workspace_bytes', C.c_int64), ('offsets', C.c_void_p), ('out', C.c_void_p),
+                ('out_capacity', C.c_int64), ('total_bytes', C.c_int64), ('N', C.c_int32), ('C', C.c_int32), ('H', C.c_int32), ('W', C.c_int32),
+                ('filter', C.c_int32), ('block_bytes', C.c_int32), ('stages', C.c_int32)]
+
+
 class Resample8Params(C.Structure):
     """eg3d_resample8_params: Pillow's 8-bit separable resize (eg3d_resample8_query_workspace / eg3d_resample8)."""
     _fields_ = [('src', C.c_void_p), ('dst', C.c_void_p), ('hbounds', C.c_void_p), ('hcoef', C.c_void_p), ('vbounds', C.c_void_p),
@@ -529,6 +536,9 @@ _SIGS = {
     'eg3d_jpeg_query_workspace': (C.c_int, [C.POINTER(JpegParams), C.POINTER(C.c_int64)]),
     'eg3d_jpeg_encode': (C.c_int, [C.POINTER(JpegParams), C.c_void_p]),
     'eg3d_jpeg_pack': (C.c_int, [C.POINTER(JpegParams), C.c_void_p]),
+    'eg3d_png_query_workspace': (C.c_int, [C.POINTER(PngParams), C.POINTER(C.c_int64)]),
+    'eg3d_png_encode': (C.c_int, [C.POINTER(PngParams), C.c_void_p]),
+    'eg3d_png_pack': (C.c_int, [C.POINTER(PngParams), C.c_void_p]),
     'eg3d_resample8_query_workspace': (C.c_int, [C.POINTER(Resample8Params), C.POINTER(C.c_int64)]),
     'eg3d_resample8': (C.c_int, [C.POINTER(Resample8Params), C.c_void_p]),
     'eg3d_quad_warp8': (C.c_int, [C.POINTER(QuadWarp8Params), C.c_void_p]),

@@ -66,7 +66,7 @@ class InversionCoach:
                  start_w_fn: Optional[Callable[[torch.Tensor], torch.Tensor]] = None, sr_fp16: bool = True, gen_mesh: bool = False,
                  mesh_dir: Optional[str] = None, mesh_res: int = 512, mesh_level: float = 10.0, mesh_format: str = '.mrc', mesh_colors: bool = False,
                  mesh_keep: Optional[int] = None, mesh_min_voxels: int = 0, mesh_simplify: Optional[float] = None, mesh_smooth: int = 0,
-                 mesh_texture_tile: int = 8, mesh_preview: bool = False,
+                 mesh_texture_tile: int = 8, mesh_preview: bool = False, png_encoder: str = 'host',
                  do_evaluation: bool = False, eval_dir: Optional[str] = None, lpips_eval_net: Optional[Callable] = None,
                  id_net: Optional[Callable] = None, save_pivot: bool = False, pivot_dir: Optional[str] = None, shape_views: bool = False,
                  on_tuned: Optional[Callable[[str, torch.Tensor], None]] = None,
@@ -103,8 +103,13 @@ class InversionCoach:
         `shape_views` (no reference counterpart): both get shaded views of the density surface beside the renders (shape=True of
         video.pivot_grid: a second row; of video.write_orbit_video: image | shape, twice the width).
         `on_tuned` (no reference counterpart): called as on_tuned(name, image) after Phase B with the tuned reconstruction, fp32 [1,3,H,W] --
-        what tools/run_inversion.py --paste-back blends into the photograph (images.paste_back)."""
+        what tools/run_inversion.py --paste-back blends into the photograph (images.paste_back).
+        `png_encoder` 'host' | 'gpu': video.write_png's encoder for every PNG the coach writes (the grids, the mesh preview, the OBJ's atlas);
+        'gpu' filters and deflates on the device (hipops.png_encode).  The default writes the files it wrote before."""
         self.on_tuned = on_tuned
+        if png_encoder not in ('host', 'gpu'):
+            raise ValueError(f"png_encoder 'host' or 'gpu', got {png_encoder!r}")
+        self.png_encoder = png_encoder
         if (save_grid or gen_video) and not media_dir:
             raise ValueError('save_grid / gen_video need a media_dir')
         self.save_grid, self.gen_video, self.media_dir, self.video_quality = save_grid, gen_video, media_dir, int(video_quality)
@@ -270,7 +275,7 @@ class InversionCoach:
         if self.save_grid:
             grid_path = os.path.join(d, f'{name}.png')
             write_png(grid_path, pivot_grid(self.G, w_pivot, cam, target, shape=self.shape_views, shape_kwargs=self._clean_kwargs() or None,
-                                            **self.synth_kwargs))
+                                            **self.synth_kwargs), encoder=self.png_encoder)
         if self.gen_video:
             video_path = os.path.join(d, f'{name}_pivot.avi' if pivot else f'{name}.avi')
             write_orbit_video(self.G, w_pivot, video_path, quality=self.video_quality, shape=self.shape_views,
@@ -304,7 +309,7 @@ class InversionCoach:
                 if self.mesh_format == '.obj':
                     att = texture_mesh(self.G, w_pivot, verts, faces, self.mesh_res, level=self.mesh_level, grid=grid, cameras=self.mesh_cameras(cam),
                                        tile=self.mesh_texture_tile, **self.synth_kwargs)
-                    write_obj(path, verts, faces, att['uv'], att['texture'], normals=att['normals'])
+                    write_obj(path, verts, faces, att['uv'], att['texture'], normals=att['normals'], png_encoder=self.png_encoder)
                     if self.mesh_preview:
                         self.write_mesh_preview(path, w_pivot, verts, faces, att, grid)
                     return path
@@ -326,7 +331,8 @@ class InversionCoach:
         from .inference import mesh_fidelity, mesh_preview_grid
         stem = os.path.splitext(path)[0]
         png, js = stem + '_preview.png', stem + '_fidelity.json'
-        write_png(png, mesh_preview_grid(self.G, w_pivot, verts, faces, att['uv'], att['texture'], self.mesh_res, **self.synth_kwargs))
+        write_png(png, mesh_preview_grid(self.G, w_pivot, verts, faces, att['uv'], att['texture'], self.mesh_res, **self.synth_kwargs),
+                  encoder=self.png_encoder)
         fid = mesh_fidelity(self.G, w_pivot, verts, faces, att['uv'], att['texture'], grid=grid, level=self.mesh_level, **self.synth_kwargs)
         with open(js, 'w') as f:
             f.write(json.dumps(fid) + '\n')

@@ -2568,6 +2568,57 @@ def jpeg_encode(img: torch.Tensor, quality: int = 90, subsampling: str = '420', 
     return out, offsets
 
 
+PNG_FILTERS = dict(adaptive=-1, none=0, sub=1, up=2, average=3, paeth=4)
+
+
+def _png_begin(img: torch.Tensor, filter='adaptive', block_bytes: int = 32768, stages: int = 0):
+    """The first two calls of the eg3d_png_* protocol: (params, workspace, offsets on the device).  The workspace must outlive the pack."""
+    L.require_cuda(img)
+    if img.dtype != torch.uint8 or img.dim() not in (2, 3, 4):
+        raise L.Eg3dHipError(f'png_encode: uint8 [N,H,W,C], [H,W,C] or [H,W], got {tuple(img.shape)} {img.dtype}')
+    if img.dim() == 2:
+        img = img[None, :, :, None]
+    elif img.dim() == 3:
+        img = img[None]
+    if img.shape[3] not in (1, 3) or min(img.shape) < 1:
+        raise L.Eg3dHipError(f'png_encode: C = 1 or 3 and N, H, W >= 1, got {tuple(img.shape)}')
+    f = PNG_FILTERS.get(filter, filter) if isinstance(filter, str) else filter
+    if isinstance(f, bool) or not isinstance(f, int) or not -1 <= f <= 4:
+        raise L.Eg3dHipError(f'png_encode: filter one of {sorted(PNG_FILTERS)} or -1..4, got {filter!r}')
+    img = img.contiguous()
+    N, Hh, Ww, Ch = img.shape
+    p = L.PngParams(img=img.data_ptr(), N=N, C=Ch, H=Hh, W=Ww, filter=f, block_bytes=int(block_bytes), stages=int(stages))
+    lib = L.lib()
+    nbytes = C.c_int64(0)
+    L.check(lib.eg3d_png_query_workspace(C.byref(p), C.byref(nbytes)), 'png_query_workspace')
+    ws = torch.empty(nbytes.value, dtype=torch.uint8, device=img.device)
+    offsets = torch.empty(N + 1, dtype=torch.int64, device=img.device)
+    p.workspace, p.workspace_bytes, p.offsets = ws.data_ptr(), nbytes.value, offsets.data_ptr()
+    L.check(lib.eg3d_png_encode(C.byref(p), L.stream_ptr()), 'png_encode')
+    return p, (ws, img), offsets
+
+
+def _png_pack(p, out: torch.Tensor, capacity: int, total: int) -> None:
+    """The third call: the streams into out[:capacity]; capacity < total is refused before any launch."""
+    p.out, p.out_capacity, p.total_bytes = out.data_ptr(), int(capacity), int(total)
+    L.check(L.lib().eg3d_png_pack(C.byref(p), L.stream_ptr()), 'png_pack')
+
+
+def png_encode(img: torch.Tensor, filter='adaptive', block_bytes: int = 32768):
+    """(bytes uint8 [total] on the device, offsets int64 [N+1] on the host): N zlib streams back to back, image n's IDAT payload =
+    bytes[offsets[n]:offsets[n+1]] (eg3d_png_*; include/eg3d_hip.h "PNG encoder"; video.png_container makes the file).  img uint8 [N,H,W,C],
+    C = 1 (grey) or 3 (RGB); [H,W], [H,W,1] and [H,W,3] are one image.  filter 'adaptive' (per row the smallest sum of absolute values) or
+    'none' | 'sub' | 'up' | 'average' | 'paeth' (or -1..4); block_bytes 64..65536 of filtered stream per deflate block, every block coded by
+    its own workgroup with its own Huffman codes.  Five launches, workspace from the caching allocator, one host synchronise (the total)."""
+    p, keep, offsets = _png_begin(img, filter, block_bytes)
+    offsets = offsets.cpu()
+    total = int(offsets[-1])
+    out = torch.empty(total, dtype=torch.uint8, device=img.device)
+    _png_pack(p, out, total, total)
+    del keep
+    return out, offsets
+
+
 # ---- image ingestion (csrc/imgprep.hip; include/eg3d_hip.h "Image ingestion"): Pillow's resize and QUAD warp, align_face's pad, ToTensor ------
 PIL_FILTER_SUPPORT = dict(bilinear=1.0, lanczos=3.0)
 RESAMPLE_TILE = 64                       # EG3D_RESAMPLE_TILE: output pixels of a row one workgroup of the horizontal pass produces

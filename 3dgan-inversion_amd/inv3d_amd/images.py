@@ -243,6 +243,42 @@ def decode_rgb(path: str, device) -> torch.Tensor:
     return torch.from_numpy(arr).to(device)
 
 
+def write_aligned(directory: str, landmarks, out_dir: str, output_size: int = 512, device='cuda', png_encoder: str = 'host', batch: int = 8,
+                  report=None):
+    """{out_dir}/{name}.png for every image file of `directory` whose name has landmarks ({name: 68 x 2}, or the path of a .json / .npz):
+    decoded on the host, aligned by align_face, written by video.write_png.  png_encoder='gpu': the aligned frames -- all output_size squared
+    -- go `batch` at a time through one video.write_pngs (one encode, one copy).  Files without landmarks are passed to `report(path)` and
+    skipped.  Returns the paths written."""
+    from . import video
+    if png_encoder not in video.PNG_ENCODERS or batch < 1:
+        raise ValueError(f'write_aligned: png_encoder one of {video.PNG_ENCODERS} and batch >= 1, got {png_encoder!r}, {batch}')
+    if isinstance(landmarks, str):
+        landmarks = load_landmarks(landmarks)
+    os.makedirs(out_dir, exist_ok=True)
+    written, pending = [], []
+
+    def flush():
+        if pending:
+            video.write_pngs([p for p, _ in pending], torch.stack([f for _, f in pending]))
+            pending.clear()
+    for name, path in image_files(directory):
+        if name not in landmarks:
+            if report is not None:
+                report(path)
+            continue
+        out = os.path.join(out_dir, name + '.png')
+        frame = align_face(decode_rgb(path, device), landmarks[name], output_size)
+        if png_encoder == 'gpu':
+            pending.append((out, frame))
+            if len(pending) == batch:
+                flush()
+        else:
+            video.write_png(out, frame)
+        written.append(out)
+    flush()
+    return written
+
+
 def load_targets(directory: str, landmarks=None, output_size: int = 512, device='cuda'):
     """[(name, target fp32 [1,3,S,S] in [-1,1] on the device, None)] for InversionCoach.run, S = output_size: every image file of `directory` in
     sorted order, decoded to RGB; aligned by align_face where `landmarks` (a {name: 68 x 2} mapping, or the path of a .json / .npz holding

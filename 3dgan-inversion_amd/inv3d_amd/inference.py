@@ -644,15 +644,15 @@ def _obj_rows(tag: str, a: np.ndarray) -> str:
     return ''.join(fmt % tuple(r) + '\n' for r in a.tolist())
 
 
-def write_obj(path: str, verts, faces, uv, texture, normals=None, texture_format: str = 'png') -> tuple:
+def write_obj(path: str, verts, faces, uv, texture, normals=None, texture_format: str = 'png', png_encoder: str = 'host') -> tuple:
     """Wavefront OBJ + MTL + image for a textured mesh (texture_mesh's verts, faces, 'uv' and 'texture').  Three files: `path` (the OBJ),
     and beside it stem.mtl and stem.png / stem.jpg with path's stem.  Returns the three paths.
       OBJ  'mtllib stem.mtl', 'usemtl stem', V lines 'v x y z' (the vertices as given: the frame of write_ply, so the two files overlay),
            V lines 'vn' when normals [V,3] are given, 3 F lines 'vt u v' (three per face, v = 1 - uv's: OBJ's origin is bottom-left), and
            F lines 'f a/ta/na b/tb/nb c/tc/nc' ('f a/ta ...' without normals), indices from 1.
       MTL  'newmtl stem', 'Kd 1 1 1', 'map_Kd' with the image's base name.
-      image  texture uint8 [Ht,Wt,3]: 'png' through video.write_png (lossless: the atlas bytes), 'jpg' through hipops.jpeg_encode on the
-           GPU at 4:4:4 (chroma subsampling would smear neighbouring faces' texels into each other)."""
+      image  texture uint8 [Ht,Wt,3]: 'png' through video.write_png (lossless: the atlas bytes; png_encoder 'host' | 'gpu' is its encoder),
+           'jpg' through hipops.jpeg_encode on the GPU at 4:4:4 (chroma subsampling would smear neighbouring faces' texels into each other)."""
     if texture_format not in ('png', 'jpg'):
         raise ValueError(f"write_obj: texture_format 'png' or 'jpg', got {texture_format!r}")
     v = _host(verts, np.float32).reshape(-1, 3)
@@ -673,7 +673,7 @@ def write_obj(path: str, verts, faces, uv, texture, normals=None, texture_format
     mtl_path, img_path = base + '.mtl', f'{base}.{texture_format}'
     if texture_format == 'png':
         from .video import write_png
-        write_png(img_path, tex)
+        write_png(img_path, tex, encoder=png_encoder)
     else:
         from .hipops import jpeg_encode
         data, offsets = jpeg_encode((tex if tex.is_cuda else tex.cuda()).permute(2, 0, 1).unsqueeze(0).contiguous(), subsampling='444')

@@ -5,14 +5,15 @@
   MjpegAviWriter               <- imageio.get_writer(mp4, mode='I', fps=60, codec='libx264') of gen_interp_video, gen_videos.py:74-146: there
                                   is no video encoder to call, so the container is a Motion-JPEG AVI (RIFF 'AVI ', one 'MJPG' video stream,
                                   'idx1' index) written here, the frames are the GPU encoder's JFIF files
-  write_png                    <- PIL.Image.fromarray(...).save(png), single_id_coach.py:60,83 (zlib only)
+  write_png                    <- PIL.Image.fromarray(...).save(png), single_id_coach.py:60,83 (zlib only; encoder='gpu': hipops.png_encode)
+  png_container, write_pngs    the file around the GPU encoder's zlib streams; N same-size images in one encode
   write_orbit_video            <- gen_interp_video(G, w_pivot, path), single_id_coach.py:61-62,84-85
   write_mesh_video             no reference counterpart: the same orbit of the exported mesh itself (inference.render_mesh), alone or beside the
                                   generator's frame or the density surface
   look_at_small, pivot_grid    <-BaseCoach.forward(ws, needs_img_grid='small', grid_num=5, need_gt_ingrid=(target, cam)) with look_at /
                                   gen_eyes(num='small'), base_coach.py:128-159,216-291
 
-Everything but the rendering and hipops.jpeg_encode / image_grid_u8 is host code on the standard library."""
+Everything but the rendering and hipops.jpeg_encode / png_encode / image_grid_u8 is host code on the standard library."""
 import math
 import struct
 import zlib
@@ -169,8 +170,34 @@ class MjpegAviWriter:
         self.close()
 
 
-def write_png(path: str, u8_hwc) -> None:
-    """8-bit PNG of a uint8 [H,W,3] (RGB) or [H,W] / [H,W,1] (grey) array: IHDR, one IDAT (filter 0 rows, zlib), IEND."""
+def _png_chunk(tag: bytes, payload: bytes) -> bytes:
+    return struct.pack('>I', len(payload)) + tag + payload + struct.pack('>I', zlib.crc32(tag + payload) & 0xFFFFFFFF)
+
+
+def png_container(stream, height: int, width: int, channels: int) -> bytes:
+    """The PNG file around one zlib stream of filtered rows: signature, IHDR (8 bits, colour type 0 grey or 2 RGB, no interlace), one IDAT,
+    IEND; the chunk CRCs are zlib.crc32 on the host."""
+    if channels not in (1, 3) or not (1 <= height < 2 ** 31 and 1 <= width < 2 ** 31):
+        raise ValueError(f'png_container: channels 1 | 3 and sides >= 1, got {height} x {width} x {channels}')
+    return (b'\x89PNG\r\n\x1a\n' + _png_chunk(b'IHDR', struct.pack('>IIBBBBB', width, height, 8, 2 if channels == 3 else 0, 0, 0, 0)) +
+            _png_chunk(b'IDAT', bytes(stream)) + _png_chunk(b'IEND', b''))
+
+
+PNG_ENCODERS = ('host', 'gpu')
+
+
+def write_png(path: str, u8_hwc, encoder: str = 'host') -> None:
+    """8-bit PNG of a uint8 [H,W,3] (RGB) or [H,W] / [H,W,1] (grey) array.  encoder='host': IHDR, one IDAT (filter 0 rows, zlib level 6), IEND.
+    encoder='gpu': the rows are filtered and deflated on the device (hipops.png_encode: adaptive filters, run-length deflate; a CPU tensor or an
+    array is uploaded), the host adds the container."""
+    if encoder not in PNG_ENCODERS:
+        raise ValueError(f'write_png: encoder one of {PNG_ENCODERS}, got {encoder!r}')
+    if encoder == 'gpu':
+        a = u8_hwc if isinstance(u8_hwc, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(u8_hwc))
+        if a.dtype != torch.uint8 or a.dim() not in (2, 3) or (a.dim() == 3 and a.shape[2] not in (1, 3)) or min(a.shape) < 1:
+            raise ValueError(f'write_png: uint8 [H,W,3] or [H,W], got {a.dtype} {tuple(a.shape)}')
+        write_pngs([path], a[None])
+        return
     a = u8_hwc.detach().cpu().numpy() if isinstance(u8_hwc, torch.Tensor) else np.asarray(u8_hwc)
     if a.ndim == 2:
         a = a[:, :, None]
@@ -185,6 +212,24 @@ def write_png(path: str, u8_hwc) -> None:
     with open(path, 'wb') as f:
         f.write(b'\x89PNG\r\n\x1a\n' + chunk(b'IHDR', struct.pack('>IIBBBBB', ww, hh, 8, 2 if ch == 3 else 0, 0, 0, 0)) +
                 chunk(b'IDAT', zlib.compress(rows.tobytes(), 6)) + chunk(b'IEND', b''))
+
+
+def write_pngs(paths, batch, filter='adaptive', block_bytes: int = 32768) -> None:
+    """len(paths) PNG files of a uint8 batch [N,H,W,3], [N,H,W,1] or [N,H,W] (a tensor on any device or an array) through one
+    hipops.png_encode: one encode, one device-to-host copy, then container and file per image."""
+    from .hipops import png_encode
+    a = batch if isinstance(batch, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(batch))
+    if a.dim() == 3:
+        a = a[..., None]
+    if a.dtype != torch.uint8 or a.dim() != 4 or a.shape[3] not in (1, 3) or min(a.shape) < 1 or a.shape[0] != len(paths):
+        raise ValueError(f'write_pngs: uint8 [N,H,W,3] or [N,H,W] with N = {len(paths)} paths, got {a.dtype} {tuple(a.shape)}')
+    if not a.is_cuda:
+        a = a.cuda()
+    data, offsets = png_encode(a.detach(), filter=filter, block_bytes=block_bytes)
+    host, off = data.cpu().numpy(), offsets.tolist()
+    for i, path in enumerate(paths):
+        with open(path, 'wb') as f:
+            f.write(png_container(host[off[i]:off[i + 1]].tobytes(), a.shape[1], a.shape[2], a.shape[3]))
 
 
 # ---- the per-image outputs -----------------------------------------------------------------------------------------------------------------------

@@ -1646,6 +1646,67 @@ int eg3d_jpeg_encode(const eg3d_jpeg_params* p, void* stream);
 int eg3d_jpeg_pack(const eg3d_jpeg_params* p, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * PNG encoder (media export: every lossless image the package writes -- grids, aligned targets, paste-back outputs, mesh previews, the OBJ
+ * exporter's atlas; csrc/png.hip).  Adaptive row filters, then a deflate that only matches runs at distance 1 (what zlib's Z_RLE finds).
+ *   img: contiguous uint8 [N][H][W][C], C = 1 (grey) or 3 (RGB), N >= 1, 1 <= H, W <= 16384.  Output: N complete zlib streams back to back
+ *   (what a PNG's IDAT holds; the container -- signature, IHDR, IDAT, IEND and their CRCs -- is host code, inv3d_amd/video.py png_container).
+ *   Integers only, no atomics on global memory: bit-identical between runs and between the two builds; tests/support/png_ref.py restates it.
+ *   1. Row filters (PNG 1.2 section 6, bpp = C).  With x the raw byte, a the byte bpp to its left, b the byte above, c the byte above a (row -1
+ *      and the bytes left of column 0 are zero), the filtered byte is (x - q) & 255 with q = 0 (type 0 None), a (1 Sub), b (2 Up),
+ *      (a + b) >> 1 (3 Average), Paeth(a, b, c) (4: p = a + b - c; a if |p - a| <= |p - b| and |p - a| <= |p - c|, else b if |p - b| <= |p - c|,
+ *      else c).  filter = 0..4 forces the type; filter = -1 picks per row the type with the smallest sum over the row's W * C bytes of
+ *      |int8(byte)| (v < 128 ? v : 256 - v), a tie going to the lower type (libpng's heuristic).  The image's filtered stream is H records
+ *      [type][W * C bytes], L = H (1 + W C) bytes.
+ *   2. Blocks and tokens.  The stream is cut into blocks of block_bytes (64..65536; the last one may be short).  Inside a block, for every
+ *      maximal run of r equal bytes v (runs end at the block's end): literal v; with m = r - 1, m / 258 matches of length 258 at distance 1;
+ *      with q = m % 258 one more match of length q if q >= 3, else q literals v.  Then end-of-block.
+ *   3. Codes.  Every block is a dynamic-Huffman block (BTYPE = 2).  Literal/length code over symbols 0 .. the highest used (256 always is);
+ *      exactly one distance code (HDIST = 0) of length 1 when the block has a match, 0 when it has none.  Code lengths of an alphabet:
+ *      the used symbols sorted by (count, symbol) ascending; a two-queue Huffman merge (leaves in that order, merged nodes in the order they
+ *      are made; of two equal weights the leaf is taken first); the number of codes per depth, depths above the limit counted at the limit;
+ *      miniz's tdefl_huffman_enforce_max_code_size (while the Kraft sum exceeds 1: one code fewer at the limit, the deepest shorter depth i
+ *      that has a code gives it up for two at i + 1); lengths handed out in increasing length from the most frequent end of the sorted order.
+ *      The limit is 15, and 7 for the code-length alphabet; where the unrestricted tree fits the limit the code is optimal.  Codes are
+ *      canonical (RFC 1951 3.2.2).  The code-length sequence is the HLIT + 257 literal/length lengths and the distance length, one symbol
+ *      0..15 each: the repeat codes 16, 17, 18 are not used (at most ~150 bytes per block), all 19 code-length code lengths are sent (HCLEN = 15).
+ *   4. Stream.  78 01; the blocks; after every block but the last an empty stored block (bits 0, 00, zero bits to the byte, 00 00 FF FF) so
+ *      that every block starts on a byte; the last block has BFINAL = 1 and is padded with zero bits; Adler-32 of the filtered stream, big
+ *      endian, combined on the device from per-block sums (sa = sum d_i, sb = sum (n - i) d_i mod 65521; two strings in a row:
+ *      sa1 + sa2, sb1 + n2 sa1 + sb2; in the end a = 1 + sa, b = n + sb).
+ *   Protocol (as eg3d_jpeg_*):
+ *     eg3d_png_query_workspace  host only: workspace bytes = N (align16(L) + 16) for the filtered streams + one slot per block + per-block
+ *                               lengths, destinations and Adler sums.  A slot holds the worst case of a block of block_bytes bytes:
+ *                               header 17 + 19 * 3 + 287 * 7 bits; a literal is at most 15 bits for one byte and a match at most
+ *                               15 + 5 + 1 bits for at least 3, so at most 15 bits per byte; end-of-block at most 15 bits; 3 bits of the
+ *                               stored block, up to 7 bits of padding and its 4 bytes; + 8 bytes (the slot is written and read in dwords)
+ *     eg3d_png_encode           four launches: fills the workspace and writes offsets[0..N] (device int64: stream n is out[offsets[n] ..
+ *                               offsets[n+1]), offsets[N] = the total)
+ *     (host reads offsets[N]: one synchronise; allocates out; passes the total back as total_bytes)
+ *     eg3d_png_pack             one launch: the streams into out.  out_capacity < total_bytes is EG3D_ERR_INVALID and nothing is launched;
+ *                               the kernel writes nothing at or beyond out_capacity whatever total_bytes says
+ *   Errors, before any launch: EG3D_ERR_INVALID for a NULL pointer, C not 1 or 3, N, H or W < 1, filter outside -1..4, block_bytes outside
+ *   64..65536, a short or misaligned workspace;  EG3D_ERR_UNSUPPORTED for H or W > 16384;  EG3D_ERR_TOO_LARGE when N H or the number of blocks
+ *   leaves int32.
+ */
+#define EG3D_PNG_FILTER_ADAPTIVE (-1)
+typedef struct eg3d_png_params {
+    const uint8_t* img;                /* [N,H,W,C] */
+    void* workspace;                   /* eg3d_png_query_workspace's bytes, 16-byte aligned */
+    int64_t workspace_bytes;
+    int64_t* offsets;                  /* device int64[N+1] */
+    uint8_t* out;                      /* pack: out_capacity bytes */
+    int64_t out_capacity;
+    int64_t total_bytes;               /* pack: offsets[N] as the host read it */
+    int32_t N, C, H, W;
+    int32_t filter;                    /* -1 adaptive, 0..4 forced */
+    int32_t block_bytes;               /* 64..65536 */
+    int32_t stages;                    /* encode: 0 = everything; 1 = the filter pass alone, 2 = the rest on an already filtered workspace (timing) */
+} eg3d_png_params;
+int eg3d_png_query_workspace(const eg3d_png_params* p, int64_t* workspace_bytes);
+int eg3d_png_encode(const eg3d_png_params* p, void* stream);
+int eg3d_png_pack(const eg3d_png_params* p, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Image ingestion (the pixel work of utils/alignment.py::align_face and of ToTensor / Normalize, scripts/run_pti.py:28-30; csrc/imgprep.hip).
  *   Images are contiguous uint8 [N,H,W,C], C = 1 or 3, sides 1..65535, on the device.  No atomics on floats, no floating-point sum whose order
  *   depends on the launch: bit-identical between runs, batch sizes and the two builds.

@@ -5,7 +5,8 @@ package (inv3d_amd/images.py, csrc/imgprep.hip).
 
 Every image file of --in-dir whose name (up to its first dot) is in the landmarks file -- a .json {name: 68 x 2} or an .npz with one array per
 name; there is no landmark detector here, the points come from a file as in EG3D's own preprocessing -- is decoded on the host, aligned on the
-GPU and written as {out-dir}/{name}.png.  Files without landmarks are reported and skipped."""
+GPU and written as {out-dir}/{name}.png (--png-gpu: encoded on the GPU as well, eight frames per batch).  Files without landmarks are
+reported and skipped."""
 import argparse
 import os
 import sys
@@ -22,19 +23,12 @@ def main(argv=None):
     ap.add_argument('--landmarks', required=True, help='.json {name: 68 x 2} or .npz')
     ap.add_argument('--out-dir', required=True)
     ap.add_argument('--output-size', type=int, default=512)
+    ap.add_argument('--png-gpu', action='store_true', help='filter and deflate the PNGs on the GPU, eight frames per encode')
     a = ap.parse_args(argv)
-    from inv3d_amd import images, video
-    dev = torch.device('cuda')
-    lms = images.load_landmarks(a.landmarks)
-    os.makedirs(a.out_dir, exist_ok=True)
-    written = []
-    for name, path in images.image_files(a.in_dir):
-        if name not in lms:
-            print(f'{path}: no landmarks, skipped')
-            continue
-        out = os.path.join(a.out_dir, name + '.png')
-        video.write_png(out, images.align_face(images.decode_rgb(path, dev), lms[name], a.output_size))
-        written.append(out)
+    from inv3d_amd import images
+    written = images.write_aligned(a.in_dir, a.landmarks, a.out_dir, a.output_size, device=torch.device('cuda'),
+                                   png_encoder='gpu' if a.png_gpu else 'host', report=lambda path: print(f'{path}: no landmarks, skipped'))
+    for out in written:
         print(out)
     print(f'{len(written)} aligned images of {a.output_size} x {a.output_size} in {a.out_dir}')
     return written

@@ -56,6 +56,7 @@ def main():
     ap.add_argument('--obj', action='store_true', help='write --out as an OBJ with an MTL and a texture atlas beside it')
     ap.add_argument('--tile', type=int, default=8, metavar='T', help='texels per side of the block two faces share (4..64)')
     ap.add_argument('--texture-format', default='png', choices=('png', 'jpg'))
+    ap.add_argument('--png-gpu', action='store_true', help='encode the PNGs on the GPU (hipops.png_encode: adaptive filters, run-length deflate)')
     ap.add_argument('--preview', default=None, metavar='PATH', help='a .png grid or an .avi orbit of the written mesh, generator beside mesh (with --obj or --colors)')
     a = ap.parse_args()
     if a.preview is not None and (not (a.obj or a.colors) or os.path.splitext(a.preview)[1].lower() not in ('.png', '.avi')):
@@ -105,7 +106,8 @@ def main():
         cams = INF.bake_cameras(a.views[0], a.views[1], device=dev)
         att = INF.texture_mesh(G, ws, verts, faces, a.res, level=a.level, grid=grid, cameras=cams, tile=a.tile)
         torch.cuda.synchronize()
-        paths = INF.write_obj(a.out, verts, faces, att['uv'], att['texture'], normals=att['normals'], texture_format=a.texture_format)
+        paths = INF.write_obj(a.out, verts, faces, att['uv'], att['texture'], normals=att['normals'], texture_format=a.texture_format,
+                              png_encoder='gpu' if a.png_gpu else 'host')
         Ht, Wt = att['texture'].shape[:2]
         nf = faces.shape[0]
         seen, owned = int((att['texture_views'] > 0).sum()), (nf // 2) * a.tile * a.tile + (nf % 2) * a.tile * (a.tile + 1) // 2
@@ -136,7 +138,7 @@ def main():
                 gen = torch.cat([G.synthesis(ws[:1], cams[i:i + 1], noise_mode='const')['image'].float() for i in range(cams.shape[0])])
                 mesh = INF.render_mesh(G, verts, faces, cams, res=gen.shape[-1], grid_res=a.res, **how)['image']
                 tiles = image_grid_u8(torch.cat([gen, mesh]).contiguous(), nrow=cams.shape[0], padding=2, pad_value=128)
-            VID.write_png(a.preview, tiles)
+            VID.write_png(a.preview, tiles, encoder='gpu' if a.png_gpu else 'host')
         else:
             VID.write_mesh_video(G, dict(verts=verts, faces=faces, grid_res=a.res, **{k: v for k, v in how.items() if k != 'mode'}), a.preview,
                                  beside='image', ws=ws, mode=how['mode'])

@@ -26,6 +26,7 @@ def main(argv=None):
     ap.add_argument('--edit', required=True, nargs='+', metavar='FILE')
     ap.add_argument('--out-dir', required=True)
     ap.add_argument('--feather', type=float, default=0.08)
+    ap.add_argument('--png-gpu', action='store_true', help='encode the PNGs on the GPU (hipops.png_encode: adaptive filters, run-length deflate)')
     ap.add_argument('--mask', default=None)
     ap.add_argument('--bbox', action='store_true')
     a = ap.parse_args(argv)
@@ -45,7 +46,8 @@ def main(argv=None):
     for path in a.edit:
         edit = images.decode_rgb(path, dev)
         out = os.path.join(a.out_dir, os.path.basename(path).split('.')[0] + '.png')
-        video.write_png(out, images.paste_back(photo, edit, lms[key], feather=a.feather, mask=mask, region='bbox' if a.bbox else 'photo'))
+        video.write_png(out, images.paste_back(photo, edit, lms[key], feather=a.feather, mask=mask, region='bbox' if a.bbox else 'photo'),
+                        encoder='gpu' if a.png_gpu else 'host')
         written.append(out)
         print(out)
     return written

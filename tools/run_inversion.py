@@ -56,6 +56,7 @@ def main(argv=None):
     ap.add_argument('--graph', action='store_true', help='capture the steps into HIP graphs')
     ap.add_argument('--save-grid', action='store_true')
     ap.add_argument('--gen-video', action='store_true')
+    ap.add_argument('--png-gpu', action='store_true', help='encode the PNGs on the GPU (hipops.png_encode: adaptive filters, run-length deflate)')
     ap.add_argument('--gen-mesh', action='store_true')
     ap.add_argument('--mesh-format', choices=('.mrc', '.ply'), default='.mrc')
     ap.add_argument('--mesh-res', type=int, default=512)
@@ -85,14 +86,15 @@ def main(argv=None):
                 return
             os.makedirs(sub('pasted'), exist_ok=True)
             pasted = images.paste_back(images.decode_rgb(paths[name], dev), img.float(), lms[name], feather=a.paste_feather)
-            write_png(os.path.join(sub('pasted'), f'{name}.png'), pasted[0])
+            write_png(os.path.join(sub('pasted'), f'{name}.png'), pasted[0], encoder='gpu' if a.png_gpu else 'host')
     samples = a.w_avg_samples if a.w_avg_samples is not None else (10000 if a.weights else 0)
     coach = InversionCoach(G, first_inv_steps=a.steps_a, max_pti_steps=a.steps_b, lpips_threshold=a.lpips_threshold, optimize_pose=a.optimize_pose,
                            use_graph=a.graph, w_avg_samples=samples, save_grid=a.save_grid, gen_video=a.gen_video,
                            media_dir=sub('media') if (a.save_grid or a.gen_video) else None, gen_mesh=a.gen_mesh,
                            mesh_dir=sub('mesh') if a.gen_mesh else None, mesh_format=a.mesh_format, mesh_res=a.mesh_res,
                            do_evaluation=a.do_evaluation, eval_dir=sub('eval') if a.do_evaluation else None, save_pivot=a.save_pivot,
-                           pivot_dir=sub('pivot') if a.save_pivot else None, on_tuned=on_tuned)
+                           pivot_dir=sub('pivot') if a.save_pivot else None, on_tuned=on_tuned,
+                           png_encoder='gpu' if a.png_gpu else 'host')
     results, stats = coach.run(targets)
     for r in results:
         print(f'{r.name}: {r.steps_a} + {r.steps_b} steps, PSNR {r.psnr_pivot:.2f} dB at the pivot, {r.psnr_tuned:.2f} dB tuned')

@@ -698,6 +698,7 @@ extern "C" int eg3d_torgb_mid_supported(const eg3d_torgb_small_params* p) {
     return 1;
 }
 
+// (this launch arithmetic is restated in tests/support/torgb_ref.py launch_fwd: the two move together)
 static int launch_torgb_mid(const eg3d_torgb_small_params* p, hipStream_t st) {
     const int T = (int)((int64_t)p->N * p->H * p->W / TS_PIX);
     const int wbytes = 96 * (p->C + 4) * 4;
@@ -725,6 +726,7 @@ extern "C" int eg3d_torgb_small_fwd(const eg3d_torgb_small_params* p, void* stre
     if (eg3d_torgb_mid_supported(p)) return launch_torgb_mid(p, (hipStream_t)stream);
     const dim3 grid(p->N * eg3d_cdiv((int64_t)p->H * p->W, TS_PIX), p->Cp / TS_OUT);
     // (64^2 x 512 = 384 blocks: measured slower with eight waves, 14.9 -> 16.4 us)
+    // (the NW choice is restated in tests/support/torgb_ref.py launch_fwd: the two move together)
     if (p->C / 8 > 4 * TS_BATCH && (int64_t)grid.x * grid.y <= 128) hipLaunchKernelGGL(torgb_small_kernel<8>, grid, dim3(512), 0, (hipStream_t)stream, *p);
     else hipLaunchKernelGGL(torgb_small_kernel<4>, grid, dim3(256), 0, (hipStream_t)stream, *p);
     EG3D_LAUNCH_CHECK();
@@ -763,6 +765,7 @@ extern "C" int eg3d_torgb_small_bwd(const eg3d_torgb_small_bwd_params* p, void* 
     // streaming form: ~two resident blocks per CU in all (a wave walks several tiles with its column sums in registers: one set of atomics per block)
     const int tpi = (int)((int64_t)p->H * p->W / TS_PIX);
     const int planes = (p->C / TS_OUT) * p->N;
+    // (grid_mid is restated in tests/support/torgb_ref.py launch_bwd: the two move together)
     const dim3 grid_mid(std::max(1, std::min((tpi + 3) / 4, 512 / std::max(1, planes))), p->C / TS_OUT, p->N);
     EG3D_DET_SCOPE(det, stream);
     EG3D_DET_BIND(det, p->ds, (int64_t)p->N * p->C);

@@ -1653,7 +1653,9 @@ def torgb_small_bwd(dy, wa, styles, x, dx, ds=None, addend=None, act_bwd=None, o
                               N=n, H=h, W=w, C=c, Cp=dy.shape[1], ldg=dy.shape[1], ldx=c, wa_row=wa.stride(0), act_on=0,
                               no_mid=0 if TORGB_MID_BWD else 1)          # (the library picks the streaming form itself from 4096 pixels: the switch must reach it)
     if addend_scale is not None:          # the addend is an unfinished split-K data gradient: finish it in this launch (PendingDgrad)
-        p.add_scale, p.add_ds = addend_scale.data_ptr(), addend_ds.data_ptr() if addend_ds is not None else None
+        p.add_scale = addend_scale.data_ptr()
+    if addend_ds is not None:             # (without addend_scale the library refuses the launch: an addend_ds dropped here would silently stay unaccumulated)
+        p.add_ds = addend_ds.data_ptr()
     fused = False
     if act_bwd is not None:
         p.act_on = 1

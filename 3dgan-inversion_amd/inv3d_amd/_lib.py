@@ -373,6 +373,23 @@ class PasteBack8Params(C.Structure):
 
 PASTE_HWC, PASTE_CHW = 0, 1
 
+
+class Edt2Params(C.Structure):
+    """eg3d_edt2_params: exact signed squared distance transform with morphology stages (eg3d_edt2_query_workspace / eg3d_edt2)."""
+    _fields_ = [('src', C.c_void_p), ('sd2', C.c_void_p), ('workspace', C.c_void_p), ('workspace_bytes', C.c_int64), ('N', C.c_int32),
+                ('H', C.c_int32), ('W', C.c_int32), ('n_stages', C.c_int32), ('t', C.c_int32 * 4), ('impl', C.c_int32)]
+
+
+class Matte8Params(C.Structure):
+    """eg3d_matte8_params: signed squared distances to the soft uint8 matte at the output resolution (eg3d_matte8)."""
+    _fields_ = [('sd2', C.c_void_p), ('dst', C.c_void_p), ('step', C.c_double), ('inv_step', C.c_double), ('shrink_px', C.c_double),
+                ('inv_feather', C.c_double), ('N', C.c_int32), ('Hs', C.c_int32), ('Ws', C.c_int32), ('Ho', C.c_int32), ('Wo', C.c_int32)]
+
+
+EDT_IMPLS = dict(auto=0, resident=1, tiled=2)
+EDT_MAX_STAGES = 4
+MATTE_MAX_SIDE = 16384
+
 _SIGS = {
     'eg3d_abi_version': (C.c_int, []),
     'eg3d_status_string': (C.c_char_p, [C.c_int]),
@@ -546,6 +563,9 @@ _SIGS = {
     'eg3d_feather_pad': (C.c_int, [C.POINTER(FeatherPadParams), C.c_void_p]),
     'eg3d_u8_to_target': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     'eg3d_paste_back8': (C.c_int, [C.POINTER(PasteBack8Params), C.c_void_p]),
+    'eg3d_edt2_query_workspace': (C.c_int, [C.POINTER(Edt2Params), C.POINTER(C.c_int64)]),
+    'eg3d_edt2': (C.c_int, [C.POINTER(Edt2Params), C.c_void_p]),
+    'eg3d_matte8': (C.c_int, [C.POINTER(Matte8Params), C.c_void_p]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGS)

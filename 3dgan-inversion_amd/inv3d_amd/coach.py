@@ -69,7 +69,7 @@ class InversionCoach:
                  mesh_texture_tile: int = 8, mesh_preview: bool = False, png_encoder: str = 'host',
                  do_evaluation: bool = False, eval_dir: Optional[str] = None, lpips_eval_net: Optional[Callable] = None,
                  id_net: Optional[Callable] = None, save_pivot: bool = False, pivot_dir: Optional[str] = None, shape_views: bool = False,
-                 on_tuned: Optional[Callable[[str, torch.Tensor], None]] = None,
+                 on_tuned: Optional[Callable[[str, torch.Tensor], None]] = None, on_tuned_depth: bool = False,
                  save_grid: bool = False, gen_video: bool = False, media_dir: Optional[str] = None, video_quality: int = 90):
         """Hyper-parameter names and defaults follow configs/hyperparameters.py.  `early_stop_interval` = how often Phase B reads the
         early-stop state back to the host (1 = every step like the reference).  With the library's Adam the TEST itself runs on the device
@@ -103,10 +103,11 @@ class InversionCoach:
         `shape_views` (no reference counterpart): both get shaded views of the density surface beside the renders (shape=True of
         video.pivot_grid: a second row; of video.write_orbit_video: image | shape, twice the width).
         `on_tuned` (no reference counterpart): called as on_tuned(name, image) after Phase B with the tuned reconstruction, fp32 [1,3,H,W] --
-        what tools/run_inversion.py --paste-back blends into the photograph (images.paste_back).
+        what tools/run_inversion.py --paste-back blends into the photograph (images.paste_back).  `on_tuned_depth`: the call is
+        on_tuned(name, image, image_depth) with the same render's raw depth [1,1,h,w] -- what images.head_matte(depth=...) takes.
         `png_encoder` 'host' | 'gpu': video.write_png's encoder for every PNG the coach writes (the grids, the mesh preview, the OBJ's atlas);
         'gpu' filters and deflates on the device (hipops.png_encode).  The default writes the files it wrote before."""
-        self.on_tuned = on_tuned
+        self.on_tuned, self.on_tuned_depth = on_tuned, bool(on_tuned_depth)
         if png_encoder not in ('host', 'gpu'):
             raise ValueError(f"png_encoder 'host' or 'gpu', got {png_encoder!r}")
         self.png_encoder = png_encoder
@@ -235,11 +236,12 @@ class InversionCoach:
         self.last_launch_modes = dict(phase_a='graph' if getattr(proj, '_graph', None) is not None else 'eager',
                                       phase_b='graph' if getattr(tuner, '_graph', None) is not None else 'eager')
         with torch.no_grad():
-            img = G.synthesis(w_pivot, cam_pivot, noise_mode='const', force_fp32=True, **self.synth_kwargs)['image']
+            tuned = G.synthesis(w_pivot, cam_pivot, noise_mode='const', force_fp32=True, **self.synth_kwargs)
+            img = tuned['image']
             psnr_tuned = float(psnr_01(img, target))
             mse = float(((img.clamp(-1, 1) - target) ** 2).mean() / 4.0)
             if self.on_tuned is not None:
-                self.on_tuned(name, img)
+                self.on_tuned(name, img, tuned['image_depth']) if self.on_tuned_depth else self.on_tuned(name, img)
         state = {k: v.detach().clone() for k, v in G.state_dict().items()} if self.keep else None
         G.requires_grad_(False)
         mesh_path = self.write_mesh(name, w_pivot, cam_pivot) if self.gen_mesh else None

@@ -137,17 +137,26 @@ def _edited(G, components, w, idx_comp, start_layer, layer_num, edit_power, num_
 
 @torch.no_grad()
 def edit_ganspace(G, components, w, cam, idx_comp: int, start_layer: int = 0, layer_num: int = 12, edit_power: float = 1.0, num_imgs: int = 5,
-                  synth_kwargs: Optional[dict] = None) -> dict:
+                  synth_kwargs: Optional[dict] = None, with_depth: bool = False) -> dict:
     """run_ganspace.edit_ganspace: dict(images uint8 [num_imgs,H,W,3], grid uint8 [Ht,Wt,3] = make_grid(nrow 8, padding 2) of them, directions
     [num_imgs,num_ws,D], ws [num_imgs,num_ws,D] = w + directions).  One image per synthesis call, as the reference: every call has the signature
-    of an ordinary single-image synthesis."""
+    of an ordinary single-image synthesis.  with_depth=True adds depth [num_imgs,1,h,w], the same renders' raw image_depth (what
+    images.head_matte(depth=...) takes)."""
     directions, ws = _edited(G, components, w, idx_comp, start_layer, layer_num, edit_power, num_imgs)
     cam = torch.as_tensor(cam, dtype=torch.float32).reshape(1, 25).to(ws.device)
     kw = dict(synth_kwargs or {})
-    rendered = [G.synthesis(ws[i:i + 1], cam, **kw)['image'].float() for i in range(num_imgs)]
+    rendered, depths = [], []
+    for i in range(num_imgs):
+        o = G.synthesis(ws[i:i + 1], cam, **kw)
+        rendered.append(o['image'].float())
+        if with_depth:
+            depths.append(o['image_depth'].float())
     images = torch.stack([H.image_grid_u8(img, nrow=1, padding=0) for img in rendered])
     grid = H.image_grid_u8(torch.cat(rendered, 0), nrow=8, padding=2)
-    return dict(images=images, grid=grid, directions=directions, ws=ws)
+    out = dict(images=images, grid=grid, directions=directions, ws=ws)
+    if with_depth:
+        out['depth'] = torch.cat(depths, 0)
+    return out
 
 
 @torch.no_grad()

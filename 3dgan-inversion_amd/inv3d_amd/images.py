@@ -14,6 +14,7 @@
 
 PIL decodes the files on the host (imported lazily, and only in load_targets); everything after the decode runs on the device."""
 import json
+import math
 import os
 from typing import NamedTuple, Optional, Tuple
 
@@ -195,6 +196,69 @@ def paste_back(photo_u8: torch.Tensor, edit: torch.Tensor, landmarks, feather: f
         matrix, feather_px = matrix * (ps / S), feather_px * (ps / S)
     out = hipops.paste_back(photo_u8, frames, matrix, plan.region, feather_px=feather_px, mask=mask, whole=region == 'photo', layout=layout)
     return out[0] if squeeze else out
+
+
+def foreground_mask(depth: torch.Tensor) -> torch.Tensor:
+    """The reference's foreground (training/warping_loss.py:12-16: depth < mean(depth)) per frame: image_depth fp32 [N,1,h,w] -> uint8 [N,h,w],
+    255 where the pixel is nearer than its own frame's mean depth (the reference's batch is 1, so its mean is a frame's)."""
+    if depth.dim() != 4 or depth.shape[1] != 1 or not depth.is_floating_point():
+        raise ValueError(f'foreground_mask: image_depth [N,1,h,w], got {tuple(depth.shape)} {depth.dtype}')
+    d = depth.float()
+    return (d < d.mean(dim=(1, 2, 3), keepdim=True))[:, 0].to(torch.uint8) * 255
+
+
+def matte_thresholds(side: int, open: float = 0.02, close: float = 0.04) -> Tuple[int, ...]:
+    """hipops.edt2's stage thresholds for a mask of `side` rows: open (erode, dilate) then close (dilate, erode), the radii fractions of the
+    side; a zero radius drops its two stages.  r = frac * side in float64; erode by r is floor(r^2), dilate by r is -floor(r^2) - 1."""
+    t = []
+    for name, frac, erode_first in (('open', open, True), ('close', close, False)):
+        r = float(frac) * int(side)
+        if not r >= 0.0:
+            raise ValueError(f'matte_from_mask: {name} >= 0, got {frac}')
+        if r > 0.0:
+            q = int(math.floor(r * r))
+            t += [q, -q - 1] if erode_first else [-q - 1, q]
+    return tuple(t)
+
+
+def matte_from_mask(mask_u8: torch.Tensor, size: int, open: float = 0.02, close: float = 0.04, shrink: float = 0.0, feather: float = 0.03,
+                    impl: str = 'auto') -> torch.Tensor:
+    """A ragged binary mask uint8 [N,s,s] (or [s,s]; foreground = nonzero) in the aligned frame -> the soft matte uint8 [N,size,size] paste_back
+    takes as `mask`, on the device without a host synchronise (hipops.edt2, hipops.matte8; no reference counterpart).  open removes specks
+    (erode, dilate), close fills holes (dilate, erode): disc radii as fractions of the mask's side, 0 drops the pair.  The edge is then placed
+    at sub-pixel precision at `size`, moved inwards by shrink and ramped over feather (smoothstep), both fractions of `size` -- as paste_back's
+    feather is a fraction of its side."""
+    from . import hipops
+    if mask_u8.dim() not in (2, 3) or mask_u8.shape[-1] != mask_u8.shape[-2]:
+        raise ValueError(f'matte_from_mask: a square uint8 mask [N,s,s] or [s,s], got {tuple(mask_u8.shape)}')
+    size = int(size)
+    sd2 = hipops.edt2(mask_u8, matte_thresholds(mask_u8.shape[-2], open, close), impl=impl)
+    return hipops.matte8(sd2, size, shrink_px=float(shrink) * size, feather_px=float(feather) * size)
+
+
+@torch.no_grad()
+def head_matte(G, ws: torch.Tensor, cam: torch.Tensor, size: Optional[int] = None, source: str = 'depth', depth: Optional[torch.Tensor] = None,
+               shape_kwargs: Optional[dict] = None, **matte_kwargs) -> torch.Tensor:
+    """The head's soft matte uint8 [N,size,size] for the frames G.synthesis(ws, cam) renders (size defaults to G.img_resolution), what
+    paste_back(mask=...) takes so that the photograph's own background stays around the head.  No reference counterpart.
+    source='depth' (the default): foreground_mask of image_depth at the neural-rendering resolution -- of `depth` [N,1,h,w] where the caller
+    already has the frame's render (no second one), else of G.synthesis(ws, cam, noise_mode='const').
+    source='shape': inference.render_shape(G, ws, cam, res=size, **shape_kwargs)['mask'], the first-hit mask of the density surface at full
+    resolution (one latent, N cameras).  EG3D's FFHQ density contains the wall behind the head, which this mask then contains too: it is for
+    grids cleaned with shape_kwargs=dict(keep=...), and 'depth' is the default for that reason.
+    matte_kwargs go to matte_from_mask (open, close, shrink, feather, impl)."""
+    size = int(G.img_resolution if size is None else size)
+    if source == 'depth':
+        if depth is None:
+            depth = G.synthesis(ws, cam, noise_mode='const')['image_depth']
+        mask = foreground_mask(depth)
+    elif source == 'shape':
+        from .inference import render_shape
+        m = render_shape(G, ws, cam, res=size, **(shape_kwargs or {}))['mask']
+        mask = (m.reshape(-1, size, size) != 0).to(torch.uint8) * 255
+    else:
+        raise ValueError(f"head_matte: source 'depth' | 'shape', got {source!r}")
+    return matte_from_mask(mask, size, **matte_kwargs)
 
 
 def e4e_image_transform(target: torch.Tensor) -> torch.Tensor:

@@ -68,9 +68,10 @@ def orbit_cameras(num_frames: int = 240, yaw_range: float = 0.35, pitch_range: f
 
 @torch.no_grad()
 def render_orbit(G, ws: torch.Tensor, num_frames: int = 240, image_mode: str = 'image', cameras: Optional[torch.Tensor] = None,
-                 **synthesis_kwargs) -> Iterator[torch.Tensor]:
+                 with_depth: bool = False, **synthesis_kwargs) -> Iterator[torch.Tensor]:
     """Yields one [3,H,W] (or [1,h,w] for image_depth, normalised to [-1,1] as gen_videos.py:143-145) frame per camera for the single
-    latent ws [1,num_ws,w_dim].  The backbone runs once; every frame is rendering + super-resolution."""
+    latent ws [1,num_ws,w_dim].  The backbone runs once; every frame is rendering + super-resolution.  with_depth=True yields
+    (frame, the same render's raw image_depth [1,h,w]) instead -- what images.head_matte(depth=...) takes, without a second render."""
     dev = ws.device
     cams = orbit_cameras(num_frames, device=dev) if cameras is None else cameras.to(dev)
     kw = dict(noise_mode='const', **synthesis_kwargs)
@@ -80,7 +81,7 @@ def render_orbit(G, ws: torch.Tensor, num_frames: int = 240, image_mode: str = '
         if image_mode == 'image_depth':
             img = -img
             img = (img - img.min()) / (img.max() - img.min()) * 2 - 1
-        yield img
+        yield (img, out['image_depth'][0]) if with_depth else img
 
 
 @torch.no_grad()

@@ -245,14 +245,21 @@ def write_orbit_video(G, ws: torch.Tensor, path: str, num_frames: int = 240, ima
     paste=(photo uint8 [H,W,3] on the device, landmarks 68 x 2) (no reference counterpart): every frame is blended back into the photograph
     the latent was inverted from (images.paste_back, `batch` frames per call, planar output straight into the encoder) and the video shows
     the photo, by default the face's bounding box in it (paste_kwargs: region='photo' for the whole photograph, feather, mask).  Colour frames
-    only, and not together with shape.  With paste=None the file is what it was before the option existed."""
+    only, and not together with shape.  With paste=None the file is what it was before the option existed.
+    paste_kwargs=dict(matte=True | {images.matte_from_mask's keywords}): every frame is pasted through its own head matte, made from the
+    depth of the frame's own render (images.head_matte(depth=...): no second render, no host synchronise), so the photograph's background
+    stays around the head.  Without `matte` the file is what it was before that option existed."""
     from .hipops import jpeg_encode
     from .inference import clean_grid, density_grid, orbit_cameras, render_orbit, render_shape
     if batch < 1:
         raise ValueError('write_orbit_video: batch >= 1')
     if paste is not None and (shape or image_mode != 'image'):
         raise ValueError("write_orbit_video: paste takes the colour frames alone (image_mode='image', shape=False)")
-    writer, pending, n = None, [], 0
+    writer, pending, depths, n = None, [], [], 0
+    pkw = dict(paste_kwargs or {})
+    matte = pkw.pop('matte', False) if paste is not None else False       # True | matte_kwargs: one matte per frame from that frame's own depth
+    if matte and 'mask' in pkw:
+        raise ValueError('write_orbit_video: paste_kwargs takes matte or mask, not both')
     if shape:
         skw = dict(shape_kwargs or {})
         cams = synthesis_kwargs.get('cameras')
@@ -273,8 +280,12 @@ def write_orbit_video(G, ws: torch.Tensor, path: str, num_frames: int = 240, ima
         nonlocal writer, n
         frames = torch.stack(pending)
         if paste is not None:
-            from .images import paste_back
-            frames = paste_back(paste[0], frames, paste[1], layout='chw', **dict(dict(region='bbox'), **(paste_kwargs or {})))
+            from .images import head_matte, paste_back
+            kw = dict(dict(region='bbox'), **pkw)
+            if matte:
+                kw['mask'] = head_matte(G, ws, None, size=frames.shape[-1], depth=torch.stack(depths), **(matte if isinstance(matte, dict) else {}))
+                depths.clear()
+            frames = paste_back(paste[0], frames, paste[1], layout='chw', **kw)
         data, offsets = jpeg_encode(frames, quality=quality)
         host, off = data.cpu().numpy(), offsets.tolist()                 # (offsets are already on the host: one copy, the bytes)
         if writer is None:
@@ -284,7 +295,10 @@ def write_orbit_video(G, ws: torch.Tensor, path: str, num_frames: int = 240, ima
         n += len(pending)
         pending.clear()
     try:
-        for i, frame in enumerate(render_orbit(G, ws, num_frames=num_frames, image_mode=image_mode, **synthesis_kwargs)):
+        for i, frame in enumerate(render_orbit(G, ws, num_frames=num_frames, image_mode=image_mode, with_depth=bool(matte), **synthesis_kwargs)):
+            if matte:
+                frame, depth = frame
+                depths.append(depth.float().clone())
             pending.append(beside(i, frame.float()) if shape else frame.float().clone())      # (the frame may be a view of a buffer the next render reuses)
             if len(pending) == batch:
                 flush()

@@ -1813,6 +1813,72 @@ typedef struct eg3d_paste_back8_params {
 } eg3d_paste_back8_params;
 int eg3d_paste_back8(const eg3d_paste_back8_params* p, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Head mattes (csrc/matte.hip; no reference counterpart -- the reference thresholds its depth, training/warping_loss.py:12-16, and never
+ * pastes).  From a ragged binary mask in the aligned frame to the soft uint8 matte eg3d_paste_back8 takes as `mask`: an exact Euclidean
+ * distance transform, applied once per morphology stage and once more for the edge.  Integers and per-thread fp64, no atomics, no sum
+ * across threads: bit-identical between runs, batch sizes and the two builds; tests/support/matte_ref.py restates both entries.
+ *
+ * eg3d_edt2: src uint8 [N,H,W], foreground = src != 0  ->  sd2 int32 [N,H,W], the signed squared Euclidean distance in pixels between
+ *   centres: + the squared distance to the nearest background pixel of the same frame at a foreground pixel, - the squared distance to
+ *   the nearest foreground pixel at a background pixel; never 0.  Pixels outside the frame belong to neither class.
+ *   1. Columns.  For every pixel, by a down and an up sweep of its column: g_bg = the distance |y - y'| to the nearest background pixel of
+ *      the column, g_fg = to its nearest foreground pixel; a column without the class gives the sentinel 2^14.  One of the two is 0 at every
+ *      pixel (the pixel itself), so one signed int16 holds both: g = +g_bg at a foreground pixel, -g_fg at a background pixel.
+ *   2. Rows.  Foreground (y, x): sd2 = min over x' of (x - x')^2 + g_bg(y, x')^2; background: -min over x' of (x - x')^2 + g_fg(y, x')^2.
+ *      A frame without the other class therefore gives exactly 2^28 (x' = x, the sentinel squared) -- every real distance is below 2^25.
+ *      Each lane scans x' = x -/+ k from best = g(x)^2 and stops at k^2 >= best: the minimum is exact whatever the stop cuts.
+ *   3. Stages.  n_stages = 0..EG3D_EDT_MAX_STAGES thresholds t[i]: for each in order the binary image becomes sd2 > t[i] and the transform
+ *      runs again; sd2 is the transform of the last binary image.  Erosion by a disc of radius r (the outside counting as foreground) is
+ *      t = floor(r^2); dilation is t = -floor(r^2) - 1.
+ *   impl: EG3D_EDT_TILED -- any size; two launches per transform (one thread per column; then one workgroup per row, or several rows where
+ *   they fit one, the row's g in LDS), g in the workspace (int16 [N,H,W]), an intermediate binary image written over g as +/-1.
+ *   EG3D_EDT_RESIDENT -- frames of H W <= 16384 pixels: one workgroup per frame keeps g in LDS (32 KB) and runs every stage and the final
+ *   transform in ONE launch; no workspace.  EG3D_EDT_AUTO -- TILED at every size: measured on MI355X, RESIDENT's one launch takes twice
+ *   the time of TILED's ten on the default chain of a 128 x 128 frame (DESIGN.md 3.4 "Head mattes").  All three give the same integers.
+ *   Errors, before any GPU work: EG3D_ERR_INVALID for a NULL pointer, N, H or W < 1, n_stages outside 0..4, an unknown impl, a short
+ *   workspace; EG3D_ERR_UNSUPPORTED for H or W > 4096, N H W >= 2^31, or EG3D_EDT_RESIDENT with H W > 16384.
+ *   eg3d_edt2_query_workspace is host only (0 bytes for the RESIDENT path). */
+#define EG3D_EDT_AUTO 0
+#define EG3D_EDT_RESIDENT 1
+#define EG3D_EDT_TILED 2
+#define EG3D_EDT_MAX_STAGES 4
+typedef struct eg3d_edt2_params {
+    const uint8_t* src;                /* [N,H,W] */
+    int32_t* sd2;                      /* [N,H,W] */
+    void* workspace;                   /* eg3d_edt2_query_workspace's bytes (may be 0: then unused) */
+    int64_t workspace_bytes;
+    int32_t N, H, W;
+    int32_t n_stages;
+    int32_t t[EG3D_EDT_MAX_STAGES];
+    int32_t impl;
+} eg3d_edt2_params;
+int eg3d_edt2_query_workspace(const eg3d_edt2_params* p, int64_t* workspace_bytes);
+int eg3d_edt2(const eg3d_edt2_params* p, void* stream);
+
+/* eg3d_matte8: sd2 int32 [N,Hs,Ws] (eg3d_edt2's) -> the soft matte uint8 [N,Ho,Wo], Ho Ws == Wo Hs (one scale for both axes).  Host doubles:
+ *   step = Ws / Wo, inv_step = Wo / Ws, shrink_px (output pixels the edge moves inwards; negative: outwards), inv_feather = 1 / the ramp's
+ *   width in output pixels (0: a hard edge).  For every output pixel (X, Y), in fp64, every operation rounded on its own, in this order (no
+ *   FMA contraction, no division on the device):
+ *     1. u = (X + 0.5) step - 0.5,  v = (Y + 0.5) step - 0.5
+ *     2. fx = floor(u), dx = u - fx, taps xa = clamp(fx, 0, Ws - 1), xb = clamp(fx + 1, 0, Ws - 1); y likewise
+ *     3. a tap's value d = s > 0 ? sqrt(s) - 0.5 : -(sqrt(-s) - 0.5)     (the contour lies half-way between centres; sqrt correctly rounded)
+ *     4. r0 = p00 + (p01 - p00) dx,  r1 = p10 + (p11 - p10) dx,  val = r0 + (r1 - r0) dy          (eg3d_paste_back8's order)
+ *     5. e = val inv_step - shrink_px
+ *     6. t = inv_feather > 0 ? min(max(e inv_feather, 0), 1) : (e > 0 ? 1 : 0)
+ *     7. a = (t t) (3 - 2 t)
+ *     8. out = uint8(rint(255 a)), ties to even
+ *   An all-foreground frame gives 255 everywhere, an all-background frame 0 (the 2^28 sentinel).  One launch, one thread per output pixel.
+ *   Errors, before any GPU work: EG3D_ERR_INVALID for a NULL pointer, a size < 1, Ho Ws != Wo Hs, step or inv_step <= 0, inv_feather < 0 or
+ *   a NaN; EG3D_ERR_UNSUPPORTED for Hs or Ws > 4096, Ho or Wo > 16384, N Hs Ws or N Ho Wo >= 2^31. */
+typedef struct eg3d_matte8_params {
+    const int32_t* sd2;                /* [N,Hs,Ws] */
+    uint8_t* dst;                      /* [N,Ho,Wo] */
+    double step, inv_step, shrink_px, inv_feather;
+    int32_t N, Hs, Ws, Ho, Wo;
+} eg3d_matte8_params;
+int eg3d_matte8(const eg3d_matte8_params* p, void* stream);
+
 /* Measurement aid (bench.py): a register-only v_mfma_f32_32x32x16_f16 loop on caller-supplied fp16 data -- what the matrix pipe sustains on
  * this chip at its current power / clock state, timed inside the benchmark run.  in: 4096 x 8 fp16 (64 KiB); out: blocks x 256 floats;
  * executes blocks x 4 waves x iters x 24 MFMAs of 32 x 32 x 16.  No reference counterpart. */

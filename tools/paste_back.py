@@ -2,12 +2,13 @@
 this package (inv3d_amd/images.py paste_back, csrc/imgprep.hip).  No reference counterpart: the reference's alignment goes one way only.
 
   python tools/paste_back.py --photo photo.jpg --landmarks landmarks.json --edit a_inter_1.png a_inter_2.png --out-dir pasted
-                             [--feather 0.08] [--mask mask.png] [--bbox]
+                             [--feather 0.08] [--mask mask.png [--mask-binary [--matte-feather 0.03] [--matte-shrink 0]]] [--bbox]
 
 --landmarks: a .json {name: 68 x 2} or an .npz with an entry for the photo (its file name up to the first dot) -- the points align_face took.
 --edit: square RGB images in the aligned frame (any side); each is written as {out-dir}/{edit name}.png, the whole photograph with the edit in
 it, or with --bbox only the face's bounding box in the photo.  --feather: the blend ramp from the frame's edge as a fraction of the side.
---mask: a grey image of the edits' side in the aligned frame, 255 = all of the edit."""
+--mask: a grey image of the edits' side in the aligned frame, 255 = all of the edit.  --mask-binary: the file is a raw binary mask instead
+(nonzero = head, e.g. a segmentation): it goes through images.matte_from_mask first (specks removed, holes closed, the edge feathered)."""
 import argparse
 import os
 import sys
@@ -28,6 +29,9 @@ def main(argv=None):
     ap.add_argument('--feather', type=float, default=0.08)
     ap.add_argument('--png-gpu', action='store_true', help='encode the PNGs on the GPU (hipops.png_encode: adaptive filters, run-length deflate)')
     ap.add_argument('--mask', default=None)
+    ap.add_argument('--mask-binary', action='store_true', help='--mask is a raw binary mask (nonzero = head): clean and feather it first')
+    ap.add_argument('--matte-feather', type=float, default=0.03, help="--mask-binary: the matte edge's ramp as a fraction of the side")
+    ap.add_argument('--matte-shrink', type=float, default=0.0, help='--mask-binary: move the matte edge inwards by this fraction of the side')
     ap.add_argument('--bbox', action='store_true')
     a = ap.parse_args(argv)
     from inv3d_amd import images, video
@@ -41,6 +45,12 @@ def main(argv=None):
         from PIL import Image
         with Image.open(a.mask) as im:
             mask = torch.from_numpy(np.array(im.convert('L'), dtype=np.uint8)).to(dev)
+        if a.mask_binary:
+            if mask.shape[0] != mask.shape[1]:
+                raise SystemExit(f'--mask-binary: a square mask, got {mask.shape[1]} x {mask.shape[0]}')
+            mask = images.matte_from_mask(mask, mask.shape[0], feather=a.matte_feather, shrink=a.matte_shrink)
+    elif a.mask_binary:
+        raise SystemExit('--mask-binary belongs to --mask')
     os.makedirs(a.out_dir, exist_ok=True)
     written = []
     for path in a.edit:

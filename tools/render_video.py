@@ -9,20 +9,24 @@ single_id_coach.py:61-62,84-85 calls it), frames encoded by the GPU JPEG encoder
 (--shape-level, --shape-grid, --shape-shade lambert | normal) beside every frame: twice the width, one density grid per video.
 With --shape, --keep N / --min-voxels M / --connectivity {6,26} remove floaters from that grid first (inference.clean_grid, once per video).
 --paste-photo P --landmarks L blends every frame back into the photograph P the latent was inverted from (images.paste_back): the video
-shows the face's bounding box in the photo, with --paste-whole the whole photograph."""
+shows the face's bounding box in the photo, with --paste-whole the whole photograph.  --paste-matte [--matte-feather F] [--matte-shrink F]
+pastes every frame through its own head matte (images.head_matte, from the depth of the frame's render): the photograph's background stays
+around the head.  --synthetic small: the 32-wide synthetic generator of the tests instead of the full-size one."""
 import argparse
 import os
 import sys
 import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, '3dgan-inversion_amd'))
+for _p in (ROOT, os.path.join(ROOT, '3dgan-inversion_amd')):
+    if _p not in sys.path:
+        sys.path.insert(0, _p)
 
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
 
-def main():
+def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.splitlines()[0])
     ap.add_argument('--ws', required=True, help='latent .npy, [1, num_ws, w_dim] or [num_ws, w_dim]')
     ap.add_argument('--out', required=True, help='output .avi')
@@ -43,7 +47,13 @@ def main():
     ap.add_argument('--paste-photo', default=None, help='the photograph the latent was inverted from: every frame is blended back into it')
     ap.add_argument('--landmarks', default=None, help='--paste-photo: a .json / .npz of 68 x 2 landmarks with an entry for the photo')
     ap.add_argument('--paste-whole', action='store_true', help="--paste-photo: the whole photograph per frame, not the face's bounding box")
-    a = ap.parse_args()
+    ap.add_argument('--paste-matte', action='store_true', help="--paste-photo: paste every frame through its head's matte (images.head_matte)")
+    ap.add_argument('--matte-feather', type=float, default=0.03, help="--paste-matte: the matte edge's ramp as a fraction of the side")
+    ap.add_argument('--matte-shrink', type=float, default=0.0, help='--paste-matte: move the matte edge inwards by this fraction of the side')
+    ap.add_argument('--synthetic', choices=('full', 'small'), default='full', help='without --weights: which synthetic generator')
+    a = ap.parse_args(argv)
+    if a.paste_matte and a.paste_photo is None:
+        raise SystemExit('--paste-matte belongs to --paste-photo')
     from inv3d_amd import video as V
     dev = torch.device('cuda')
     if a.weights:
@@ -51,7 +61,12 @@ def main():
         G = load_generator(a.weights, device=dev)
     else:
         from inv3d_amd import synthetic as S
-        G = S.make_generator(device=dev)
+        if a.synthetic == 'small':
+            from oracle import eg3d_oracle as O
+            G = S.make_generator(w_dim=32, z_dim=32, plane_res=32, channel_base=256, channel_max=16, nrr=16, sr_in_res=16, sr_widths=(16, 8),
+                                 rendering_kwargs=O.small_config().rendering, device=dev)
+        else:
+            G = S.make_generator(device=dev)
         S.load_synthetic_weights(G, seed=a.seed)
     ws = torch.from_numpy(np.load(a.ws)).float().to(dev)
     if ws.dim() == 2:
@@ -66,12 +81,16 @@ def main():
         if key not in lms:
             raise SystemExit(f'{a.landmarks} has no entry for {key}')
         paste = (images.decode_rgb(a.paste_photo, dev), lms[key])
+    pkw = dict(region='photo') if a.paste_whole else {}
+    if a.paste_matte:
+        pkw['matte'] = dict(feather=a.matte_feather, shrink=a.matte_shrink)
     t0 = time.perf_counter()
     n = V.write_orbit_video(G, ws, a.out, num_frames=a.frames, image_mode='image_depth' if a.depth else 'image', fps=a.fps, quality=a.quality,
                             batch=a.batch, shape=a.shape, shape_kwargs=dict(level=a.shape_level, grid_res=a.shape_grid, shade=a.shape_shade, **clean),
-                            paste=paste, paste_kwargs=dict(region='photo') if a.paste_whole else None)
+                            paste=paste, paste_kwargs=pkw or None)
     dt = time.perf_counter() - t0
     print(f'{a.out}: {n} frames, {os.path.getsize(a.out)} bytes ({dt * 1e3:.1f} ms, {n / dt:.1f} frames/s)')
+    return n
 
 
 if __name__ == '__main__':

@@ -9,7 +9,8 @@ fit   writes the [K, w_dim] float32 components of a PCA of W at the frontal came
 edit  takes a pivot as the coach's save_pivot writes it ({name}_ws.npy [1, num_ws, w_dim], {name}_cam.npy [1, 25]) and a named direction of
       ganspace.GANSPACE_DIRECTIONS or its four numbers (component, first layer, layers, power); writes {name}_grid.png and, with --save-images,
       {name}_inter_{i}.png (i from 1) as the reference names them.  With --paste-photo P --landmarks L (no reference counterpart) also
-      {name}_pasted.png: every edit blended back into the photograph P (images.paste_back), the face's bounding box of each side by side.
+      {name}_pasted.png: every edit blended back into the photograph P (images.paste_back), the face's bounding box of each side by side;
+      with --paste-matte [--matte-feather F] [--matte-shrink F] each through its own head matte (images.head_matte, from the edit's depth).
 --weights: a generator archive (inv3d_amd.weights, tools/convert_eg3d_pickle.py); otherwise a synthetic generator (inv3d_amd.synthetic, weights
 seed --seed): 'full' is the full-size one, 'small' the 32-wide one of the tests."""
 import argparse
@@ -69,6 +70,9 @@ def _parser():
     ed.add_argument('--paste-photo', default=None, help='the photograph the pivot was inverted from: also write {name}_pasted.png')
     ed.add_argument('--landmarks', default=None, help='--paste-photo: a .json / .npz of 68 x 2 landmarks with an entry for the photo (or --name)')
     ed.add_argument('--paste-feather', type=float, default=0.08)
+    ed.add_argument('--paste-matte', action='store_true', help="--paste-photo: paste every edit through its head's matte (images.head_matte)")
+    ed.add_argument('--matte-feather', type=float, default=0.03, help="--paste-matte: the matte edge's ramp as a fraction of the side")
+    ed.add_argument('--matte-shrink', type=float, default=0.0, help='--paste-matte: move the matte edge inwards by this fraction of the side')
     return ap
 
 
@@ -93,7 +97,10 @@ def main(argv=None):
     comp = GS.load_components(a.components)
     w = torch.from_numpy(np.load(a.ws)).float().to(dev)
     cam = torch.from_numpy(np.load(a.cam)).float().to(dev)
-    out = GS.edit_ganspace(G, comp, w, cam, idx, start_layer=start, layer_num=num, edit_power=power, num_imgs=a.num_imgs)
+    if a.paste_matte and a.paste_photo is None:
+        raise SystemExit('--paste-matte belongs to --paste-photo')
+    out = GS.edit_ganspace(G, comp, w, cam, idx, start_layer=start, layer_num=num, edit_power=power, num_imgs=a.num_imgs,
+                           **(dict(with_depth=True) if a.paste_matte else {}))
     os.makedirs(a.out_dir, exist_ok=True)
     path = os.path.join(a.out_dir, f'{a.name}_grid.png')
     Image.fromarray(out['grid'].cpu().numpy(), 'RGB').save(path)
@@ -111,7 +118,11 @@ def main(argv=None):
         key = key if key in lms else a.name
         if key not in lms:
             raise SystemExit(f'{a.landmarks} has no entry for {os.path.basename(a.paste_photo)} or {a.name}')
-        pasted = images.paste_back(images.decode_rgb(a.paste_photo, dev), out['images'], lms[key], feather=a.paste_feather, region='bbox')
+        kw = {}
+        if a.paste_matte:                                                      # one matte per edit, from the depth of the edit's own render
+            kw['mask'] = images.head_matte(G, None, None, size=out['images'].shape[1], depth=out['depth'], feather=a.matte_feather,
+                                           shrink=a.matte_shrink)
+        pasted = images.paste_back(images.decode_rgb(a.paste_photo, dev), out['images'], lms[key], feather=a.paste_feather, region='bbox', **kw)
         out['pasted'] = pasted                                                 # [num_imgs, h, w, 3]: the face's bounding box in the photo, per edit
         ppath = os.path.join(a.out_dir, f'{a.name}_pasted.png')
         write_png(ppath, torch.cat(list(pasted), dim=1))

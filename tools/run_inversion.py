@@ -9,7 +9,8 @@ Images with an entry in --landmarks (a .json {name: 68 x 2} or an .npz) are alig
 already.  --weights: a generator archive (inv3d_amd.weights, tools/convert_eg3d_pickle.py); otherwise a synthetic generator.  Outputs go to
 {out-dir}/media (grids, videos), /mesh, /eval, /pivot; a summary line per image and the totals are printed.  --paste-back also writes
 {out-dir}/pasted/{name}.png for every image that had landmarks: the tuned reconstruction blended back into the photograph it was aligned
-from (images.paste_back)."""
+from (images.paste_back); with --paste-matte [--matte-feather F] [--matte-shrink F] through the head's own matte (images.head_matte, from the
+depth of the same render), so the photograph's background stays around the head."""
 import argparse
 import os
 import sys
@@ -64,7 +65,12 @@ def main(argv=None):
     ap.add_argument('--save-pivot', action='store_true')
     ap.add_argument('--paste-back', action='store_true', help='write the tuned reconstruction blended into its photograph (needs --landmarks)')
     ap.add_argument('--paste-feather', type=float, default=0.08, help='--paste-back: blend ramp as a fraction of the aligned side')
+    ap.add_argument('--paste-matte', action='store_true', help="--paste-back: paste through the head's matte (images.head_matte), not the whole square")
+    ap.add_argument('--matte-feather', type=float, default=0.03, help="--paste-matte: the matte edge's ramp as a fraction of the aligned side")
+    ap.add_argument('--matte-shrink', type=float, default=0.0, help='--paste-matte: move the matte edge inwards by this fraction of the aligned side')
     a = ap.parse_args(argv)
+    if a.paste_matte and not a.paste_back:
+        raise SystemExit('--paste-matte belongs to --paste-back')
     from inv3d_amd import images
     from inv3d_amd.coach import InversionCoach
     dev = torch.device('cuda')
@@ -81,11 +87,14 @@ def main(argv=None):
         from inv3d_amd.video import write_png
         lms, paths = images.load_landmarks(a.landmarks), dict(images.image_files(a.in_dir))
 
-        def on_tuned(name, img):
+        def on_tuned(name, img, depth=None):
             if name not in lms:
                 return
             os.makedirs(sub('pasted'), exist_ok=True)
-            pasted = images.paste_back(images.decode_rgb(paths[name], dev), img.float(), lms[name], feather=a.paste_feather)
+            kw = {}
+            if a.paste_matte:                                                  # the head's own matte, from the depth of the same render
+                kw['mask'] = images.head_matte(G, None, None, size=img.shape[-1], depth=depth, feather=a.matte_feather, shrink=a.matte_shrink)
+            pasted = images.paste_back(images.decode_rgb(paths[name], dev), img.float(), lms[name], feather=a.paste_feather, **kw)
             write_png(os.path.join(sub('pasted'), f'{name}.png'), pasted[0], encoder='gpu' if a.png_gpu else 'host')
     samples = a.w_avg_samples if a.w_avg_samples is not None else (10000 if a.weights else 0)
     coach = InversionCoach(G, first_inv_steps=a.steps_a, max_pti_steps=a.steps_b, lpips_threshold=a.lpips_threshold, optimize_pose=a.optimize_pose,
@@ -93,7 +102,7 @@ def main(argv=None):
                            media_dir=sub('media') if (a.save_grid or a.gen_video) else None, gen_mesh=a.gen_mesh,
                            mesh_dir=sub('mesh') if a.gen_mesh else None, mesh_format=a.mesh_format, mesh_res=a.mesh_res,
                            do_evaluation=a.do_evaluation, eval_dir=sub('eval') if a.do_evaluation else None, save_pivot=a.save_pivot,
-                           pivot_dir=sub('pivot') if a.save_pivot else None, on_tuned=on_tuned,
+                           pivot_dir=sub('pivot') if a.save_pivot else None, on_tuned=on_tuned, on_tuned_depth=a.paste_matte,
                            png_encoder='gpu' if a.png_gpu else 'host')
     results, stats = coach.run(targets)
     for r in results:

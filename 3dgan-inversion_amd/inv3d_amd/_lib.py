@@ -374,6 +374,17 @@ class PasteBack8Params(C.Structure):
 PASTE_HWC, PASTE_CHW = 0, 1
 
 
+class PasteBlend8Params(C.Structure):
+    """eg3d_paste_blend8_params: eg3d_paste_back8's fields, then the bands and the workspace of the multi-band blend
+    (eg3d_paste_blend8_query_workspace / eg3d_paste_blend8)."""
+    _fields_ = PasteBack8Params._fields_ + [('bands', C.c_int32), ('workspace', C.c_void_p), ('workspace_bytes', C.c_int64)]
+
+
+BLEND_MAX_BANDS = 6
+BLEND_L1_TILE = (64, 32)                   # (width, height) in level-0 pixels of a blend_level1 workgroup, EG3D_BLEND_L1_TILE_W / _H
+BLEND_COMPOSE_TILE = (64, 16)             # of a blend_compose workgroup, EG3D_BLEND_COMPOSE_TILE_W / _H
+
+
 class Edt2Params(C.Structure):
     """eg3d_edt2_params: exact signed squared distance transform with morphology stages (eg3d_edt2_query_workspace / eg3d_edt2)."""
     _fields_ = [('src', C.c_void_p), ('sd2', C.c_void_p), ('workspace', C.c_void_p), ('workspace_bytes', C.c_int64), ('N', C.c_int32),
@@ -563,6 +574,8 @@ _SIGS = {
     'eg3d_feather_pad': (C.c_int, [C.POINTER(FeatherPadParams), C.c_void_p]),
     'eg3d_u8_to_target': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     'eg3d_paste_back8': (C.c_int, [C.POINTER(PasteBack8Params), C.c_void_p]),
+    'eg3d_paste_blend8_query_workspace': (C.c_int, [C.POINTER(PasteBlend8Params), C.POINTER(C.c_int64)]),
+    'eg3d_paste_blend8': (C.c_int, [C.POINTER(PasteBlend8Params), C.c_void_p]),
     'eg3d_edt2_query_workspace': (C.c_int, [C.POINTER(Edt2Params), C.POINTER(C.c_int64)]),
     'eg3d_edt2': (C.c_int, [C.POINTER(Edt2Params), C.c_void_p]),
     'eg3d_matte8': (C.c_int, [C.POINTER(Matte8Params), C.c_void_p]),

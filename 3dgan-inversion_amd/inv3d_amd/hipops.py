@@ -2807,6 +2807,33 @@ def u8_to_target(img: torch.Tensor) -> torch.Tensor:
     return out
 
 
+def _paste_inputs(what: str, photo, edits, matrix, region, feather_px, mask, layout):
+    """The checks paste_back and paste_blend share: (photo [1,Hp,Wp,C], edits [N,S,S,C], squeeze, m, (x0, y0, x1, y1), feather_px, mask)."""
+    ph, _ = _u8_images(photo, what + ' (photo)')
+    x, squeeze = _u8_images(edits, what + ' (edits)')
+    if photo.dim() != 3 or x.shape[-1] != ph.shape[-1] or x.shape[1] != x.shape[2] or x.device != ph.device:
+        raise L.Eg3dHipError(f'{what}: one photo [Hp,Wp,C] and square edits [N,S,S,C] of the same C and device, got {tuple(photo.shape)} and '
+                             f'{tuple(edits.shape)}')
+    if layout not in ('hwc', 'chw'):
+        raise L.Eg3dHipError(f"{what}: layout 'hwc' | 'chw', got {layout!r}")
+    N, S, _, Ch = x.shape
+    _, Hp, Wp, _ = ph.shape
+    m = [float(v) for v in np.asarray(matrix, dtype=np.float64).reshape(-1)]
+    x0, y0, x1, y1 = (int(v) for v in region)
+    if len(m) != 6 or not (0 <= x0 <= x1 <= Wp and 0 <= y0 <= y1 <= Hp):
+        raise L.Eg3dHipError(f'{what}: six matrix numbers and a region inside the {Wp} x {Hp} photo, got {len(m)} and {tuple(region)}')
+    feather_px = float(feather_px)
+    if not feather_px >= 0.0:
+        raise L.Eg3dHipError(f'{what}: feather_px >= 0, got {feather_px}')
+    mk = None
+    if mask is not None:
+        L.require_cuda(mask)
+        if mask.dtype != torch.uint8 or tuple(mask.shape) not in ((S, S), (N, S, S)) or mask.device != ph.device:
+            raise L.Eg3dHipError(f'{what}: mask uint8 [{S},{S}] or [{N},{S},{S}], got {tuple(mask.shape)} {mask.dtype}')
+        mk = mask.contiguous()
+    return ph, x, squeeze, m, (x0, y0, x1, y1), feather_px, mk
+
+
 def paste_back(photo: torch.Tensor, edits: torch.Tensor, matrix, region, feather_px: float = 0.0, mask: Optional[torch.Tensor] = None,
                whole: bool = True, layout: str = 'hwc') -> torch.Tensor:
     """Edited aligned frames blended into their photograph on the device (eg3d_paste_back8; include/eg3d_hip.h states the arithmetic): photo
@@ -2816,28 +2843,9 @@ def paste_back(photo: torch.Tensor, edits: torch.Tensor, matrix, region, feather
     mask = uint8 [S,S] or [N,S,S] in the aligned frame, 255 = all of the edit.  whole=True gives the whole photograph per frame, [N,Hp,Wp,C]
     (two launches: the photo into every frame, then the region); whole=False the region alone, [N, y1 - y0, x1 - x0, C] (one launch).
     layout='chw' gives [N,C,H,W] instead, what jpeg_encode takes."""
-    ph, _ = _u8_images(photo, 'paste_back (photo)')
-    x, squeeze = _u8_images(edits, 'paste_back (edits)')
-    if photo.dim() != 3 or x.shape[-1] != ph.shape[-1] or x.shape[1] != x.shape[2] or x.device != ph.device:
-        raise L.Eg3dHipError(f'paste_back: one photo [Hp,Wp,C] and square edits [N,S,S,C] of the same C and device, got {tuple(photo.shape)} and '
-                             f'{tuple(edits.shape)}')
-    if layout not in ('hwc', 'chw'):
-        raise L.Eg3dHipError(f"paste_back: layout 'hwc' | 'chw', got {layout!r}")
+    ph, x, squeeze, m, (x0, y0, x1, y1), feather_px, mk = _paste_inputs('paste_back', photo, edits, matrix, region, feather_px, mask, layout)
     N, S, _, Ch = x.shape
     _, Hp, Wp, _ = ph.shape
-    m = [float(v) for v in np.asarray(matrix, dtype=np.float64).reshape(-1)]
-    x0, y0, x1, y1 = (int(v) for v in region)
-    if len(m) != 6 or not (0 <= x0 <= x1 <= Wp and 0 <= y0 <= y1 <= Hp):
-        raise L.Eg3dHipError(f'paste_back: six matrix numbers and a region inside the {Wp} x {Hp} photo, got {len(m)} and {tuple(region)}')
-    feather_px = float(feather_px)
-    if not feather_px >= 0.0:
-        raise L.Eg3dHipError(f'paste_back: feather_px >= 0, got {feather_px}')
-    mk = None
-    if mask is not None:
-        L.require_cuda(mask)
-        if mask.dtype != torch.uint8 or tuple(mask.shape) not in ((S, S), (N, S, S)) or mask.device != ph.device:
-            raise L.Eg3dHipError(f'paste_back: mask uint8 [{S},{S}] or [{N},{S},{S}], got {tuple(mask.shape)} {mask.dtype}')
-        mk = mask.contiguous()
     Ho, Wo = (Hp, Wp) if whole else (y1 - y0, x1 - x0)
     out = torch.empty((N, Ch, Ho, Wo) if layout == 'chw' else (N, Ho, Wo, Ch), dtype=torch.uint8, device=ph.device)
     if out.numel() > 0:
@@ -2848,6 +2856,63 @@ def paste_back(photo: torch.Tensor, edits: torch.Tensor, matrix, region, feather
         p.m[:] = m
         L.check(L.lib().eg3d_paste_back8(C.byref(p), L.stream_ptr()), 'paste_back8')
     return out[0] if squeeze else out
+
+
+def paste_blend_window(region, bands: int, Hp: int, Wp: int):
+    """(wx0, wy0, wx1, wy1): the window eg3d_paste_blend8 works on -- the box grown by 2^(bands + 2) pixels and clamped to the photo."""
+    x0, y0, x1, y1 = (int(v) for v in region)
+    M = 1 << (int(bands) + 2)
+    return max(x0 - M, 0), max(y0 - M, 0), min(x1 + M, Wp), min(y1 + M, Hp)
+
+
+def paste_blend(photo: torch.Tensor, edits: torch.Tensor, matrix, region, bands: int, feather_px: float = 0.0,
+                mask: Optional[torch.Tensor] = None, whole: bool = True, layout: str = 'hwc', return_levels: bool = False):
+    """paste_back with a multi-band blend (eg3d_paste_blend8, csrc/blend.hip; include/eg3d_hip.h states the arithmetic): the difference
+    edit - photo goes through a Laplacian pyramid of `bands` = 1..6 levels and every level is weighted by the blend weight reduced to it,
+    over the window paste_blend_window gives.  The arguments and the result are paste_back's: whole=True writes the whole window into each
+    photo copy; whole=False gives the region (the bounding box) alone and drops what the blend changes in the margin around it.
+    An empty region gives what paste_back gives.  return_levels=True also returns the pyramid the kernels left in the workspace, a dict of
+    fp32 tensors 'D' / 'alpha' (levels 1..bands: [N,C,h,w] / [N,h,w]) and 'R' (levels 1..bands - 1), each a list indexed by level - 1.
+    The workspace is a torch allocation; no host synchronise."""
+    ph, x, squeeze, m, (x0, y0, x1, y1), feather_px, mk = _paste_inputs('paste_blend', photo, edits, matrix, region, feather_px, mask, layout)
+    if isinstance(bands, bool) or not isinstance(bands, (int, np.integer)) or not 1 <= int(bands) <= L.BLEND_MAX_BANDS:
+        raise L.Eg3dHipError(f'paste_blend: bands an int in 1..{L.BLEND_MAX_BANDS}, got {bands!r}')
+    bands = int(bands)
+    N, S, _, Ch = x.shape
+    _, Hp, Wp, _ = ph.shape
+    Ho, Wo = (Hp, Wp) if whole else (y1 - y0, x1 - x0)
+    out = torch.empty((N, Ch, Ho, Wo) if layout == 'chw' else (N, Ho, Wo, Ch), dtype=torch.uint8, device=ph.device)
+    levels = dict(D=[], alpha=[], R=[])
+    if out.numel() > 0:
+        with torch.cuda.device(ph.device):
+            p = L.PasteBlend8Params(photo=ph.data_ptr(), edits=x.data_ptr(), mask=mk.data_ptr() if mk is not None else None, dst=out.data_ptr(),
+                                    inv_feather=1.0 / feather_px if feather_px > 0.0 else 0.0, N=N, Hp=Hp, Wp=Wp, C=Ch, S=S, x0=x0, y0=y0, x1=x1,
+                                    y1=y1, mask_frames=N if (mk is not None and mk.dim() == 3) else 1, whole=int(bool(whole)),
+                                    layout=L.PASTE_CHW if layout == 'chw' else L.PASTE_HWC, bands=bands)
+            p.m[:] = m
+            lib = L.lib()
+            nbytes = C.c_int64(0)
+            L.check(lib.eg3d_paste_blend8_query_workspace(C.byref(p), C.byref(nbytes)), 'paste_blend8_query_workspace')
+            ws = torch.empty(max(nbytes.value // 4, 4), dtype=torch.float32, device=ph.device)
+            p.workspace, p.workspace_bytes = ws.data_ptr(), nbytes.value
+            L.check(lib.eg3d_paste_blend8(C.byref(p), L.stream_ptr()), 'paste_blend8')
+        if return_levels and nbytes.value > 0:
+            wx0, wy0, wx1, wy1 = paste_blend_window((x0, y0, x1, y1), bands, Hp, Wp)
+            sizes, h, w = [], wy1 - wy0, wx1 - wx0
+            for _ in range(bands):
+                h, w = (h + 1) // 2, (w + 1) // 2
+                sizes.append((h, w))
+            at = 0
+            for h, w in sizes:
+                da = ws[at:at + N * (Ch + 1) * h * w].view(N, Ch + 1, h, w)
+                levels['D'].append(da[:, :Ch])
+                levels['alpha'].append(da[:, Ch])
+                at += N * (Ch + 1) * h * w
+            for h, w in sizes[:-1]:
+                levels['R'].append(ws[at:at + N * Ch * h * w].view(N, Ch, h, w))
+                at += N * Ch * h * w
+    out = out[0] if squeeze else out
+    return (out, levels) if return_levels else out
 
 
 def edt2(mask_u8: torch.Tensor, thresholds=(), impl: str = 'auto') -> torch.Tensor:

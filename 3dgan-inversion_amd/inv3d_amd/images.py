@@ -7,7 +7,8 @@
   paste_plan, paste_back   <- no reference counterpart (its alignment goes one way only): the inverse geometry of align_plan as one affine map
                               photo -> aligned frame in host float64, and the edited frame(s) blended back into the photograph by
                               hipops.paste_back (csrc/imgprep.hip): what tools/paste_back.py, video.write_orbit_video(paste=...),
-                              tools/run_ganspace.py --paste-photo and tools/run_inversion.py --paste-back write
+                              tools/run_ganspace.py --paste-photo and tools/run_inversion.py --paste-back write; bands=1..6 | 'auto'
+                              (paste_bands) blends through a Laplacian pyramid instead of the one alpha (hipops.paste_blend, csrc/blend.hip)
   e4e_image_transform      <- training/coaches/base_coach.py:41-45: ToPILImage, Resize((256, 256)), ToTensor, Normalize
   load_landmarks           <- a .json ({name: 68 x 2}) or .npz (one array per name) mapping
   load_targets             <- ImagesDataset / make_dataset + ToTensor / Normalize: the (name, target, None) tuples InversionCoach.run takes
@@ -164,8 +165,25 @@ def _edit_frames(edit: torch.Tensor):
     raise ValueError(f'paste_back: edit uint8 [S,S,3] or [N,S,S,3], or fp32 [N,3,S,S] in [-1,1], got {tuple(edit.shape)} {edit.dtype}')
 
 
+def paste_bands(plan: PastePlan, S: int, feather: float) -> int:
+    """The bands paste_back(bands='auto') uses: clamp(floor(log2(max(2, feather S / scale))) - 1, 1, 5) -- the broadest band's transition
+    (about 2^(bands + 1) photo pixels) is about the feather's width in photo pixels.  A geometric choice, not tuned on real heads."""
+    width = max(2.0, float(feather) * float(S) / float(plan.scale))
+    return int(min(max(int(np.floor(np.log2(width))) - 1, 1), 5))
+
+
+def bands_arg(text: str):
+    """The text of the tools' --paste-bands as paste_back's bands: 0 (the one-alpha blend), 1..6, or 'auto' (paste_bands); else ValueError."""
+    if text == 'auto':
+        return text
+    n = int(text)
+    if not 0 <= n <= 6:
+        raise ValueError(f"bands 0..6 or 'auto', got {text!r}")
+    return n
+
+
 def paste_back(photo_u8: torch.Tensor, edit: torch.Tensor, landmarks, feather: float = 0.08, mask: Optional[torch.Tensor] = None,
-               region: str = 'photo', layout: str = 'hwc') -> torch.Tensor:
+               region: str = 'photo', layout: str = 'hwc', bands=0) -> torch.Tensor:
     """The closing step of an edit: the aligned S x S result(s) blended back into the photograph they were aligned from, on the device
     (hipops.paste_back).  photo_u8 uint8 [H,W,3] and the landmarks align_face took; edit uint8 [S,S,3] or [N,S,S,3], or the generator's fp32
     [N,3,S,S] in [-1,1] (quantised as hipops.image_grid_u8 does) -- S is the edit's own side, whatever side the photo was aligned at.
@@ -173,10 +191,15 @@ def paste_back(photo_u8: torch.Tensor, edit: torch.Tensor, landmarks, feather: f
     region='photo': the whole photograph per frame ([H,W,3] for one [S,S,3] edit, else [N,H,W,3]); a face wholly outside the photo gives the
     photo unchanged.  region='bbox': only the aligned square's bounding box in the photo (PastePlan.region); ValueError if that is empty.
     Where the face is smaller in the photo than in the frame (PastePlan.scale > 1) the edit and the mask are first shrunk to presize with
-    Pillow's LANCZOS (hipops.pil_resize), so the bilinear taps do not alias.  layout='chw' gives [N,3,H,W] for the JPEG encoder."""
+    Pillow's LANCZOS (hipops.pil_resize), so the bilinear taps do not alias.  layout='chw' gives [N,3,H,W] for the JPEG encoder.
+    bands=0: the one-alpha blend (hipops.paste_back).  bands=1..6: the multi-band blend (hipops.paste_blend) after the same presize -- the
+    coarse part of edit - photo fades over a wide transition, the detail over a narrow one, which hides the tone seam a render leaves around
+    the head; the result has the same shape (region='bbox' drops what the blend changes outside the box).  bands='auto': paste_bands."""
     from . import hipops
     if region not in ('photo', 'bbox'):
         raise ValueError(f"paste_back: region 'photo' | 'bbox', got {region!r}")
+    if not (bands == 'auto' or (isinstance(bands, (int, np.integer)) and not isinstance(bands, bool) and 0 <= int(bands) <= 6)):
+        raise ValueError(f"paste_back: bands 0..6 or 'auto', got {bands!r}")
     if photo_u8.dim() != 3:
         raise ValueError(f'paste_back: one uint8 [H,W,3] photo, got {tuple(photo_u8.shape)}')
     frames, squeeze = _edit_frames(edit)
@@ -194,7 +217,12 @@ def paste_back(photo_u8: torch.Tensor, edit: torch.Tensor, landmarks, feather: f
         if mask is not None:
             mask = hipops.pil_resize(mask[..., None], (ps, ps), 'lanczos')[..., 0]
         matrix, feather_px = matrix * (ps / S), feather_px * (ps / S)
-    out = hipops.paste_back(photo_u8, frames, matrix, plan.region, feather_px=feather_px, mask=mask, whole=region == 'photo', layout=layout)
+    bands = paste_bands(plan, S, feather) if bands == 'auto' else int(bands)
+    if bands == 0:
+        out = hipops.paste_back(photo_u8, frames, matrix, plan.region, feather_px=feather_px, mask=mask, whole=region == 'photo', layout=layout)
+    else:
+        out = hipops.paste_blend(photo_u8, frames, matrix, plan.region, bands, feather_px=feather_px, mask=mask, whole=region == 'photo',
+                                 layout=layout)
     return out[0] if squeeze else out
 
 

@@ -244,7 +244,8 @@ def write_orbit_video(G, ws: torch.Tensor, path: str, num_frames: int = 240, ima
     min_voxels, connectivity, ...).  The density grid and its brick maxima are built once per video, and so is inference.clean_grid's pass.  With shape=False the file is what it was before the option existed.
     paste=(photo uint8 [H,W,3] on the device, landmarks 68 x 2) (no reference counterpart): every frame is blended back into the photograph
     the latent was inverted from (images.paste_back, `batch` frames per call, planar output straight into the encoder) and the video shows
-    the photo, by default the face's bounding box in it (paste_kwargs: region='photo' for the whole photograph, feather, mask).  Colour frames
+    the photo, by default the face's bounding box in it (paste_kwargs: region='photo' for the whole photograph, feather, mask, bands=1..6 |
+    'auto' for the multi-band blend -- with the matte too).  Colour frames
     only, and not together with shape.  With paste=None the file is what it was before the option existed.
     paste_kwargs=dict(matte=True | {images.matte_from_mask's keywords}): every frame is pasted through its own head matte, made from the
     depth of the frame's own render (images.head_matte(depth=...): no second render, no host synchronise), so the photograph's background

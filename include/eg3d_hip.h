@@ -1813,6 +1813,60 @@ typedef struct eg3d_paste_back8_params {
 } eg3d_paste_back8_params;
 int eg3d_paste_back8(const eg3d_paste_back8_params* p, void* stream);
 
+/* eg3d_paste_blend8 (csrc/blend.hip): eg3d_paste_back8 with a multi-band blend (Burt-Adelson) in place of the one alpha -- the difference
+ *   edit - photo is split into L = bands Laplacian levels and every level is weighted by the blend weight reduced to that level, so the
+ *   coarse part of the difference (exposure, colour) fades over a wide transition and the detail over a narrow one.  tests/support/blend_ref.py
+ *   restates it in numpy; the kernels give its bytes.
+ *   The window = the box x0..y1 (the aligned square's bounding box, as for eg3d_paste_back8) grown by M = 2^(L + 2) pixels on every side
+ *   and clamped to the photo.  With D and alpha supported in the box, R_0 below is exactly 0 further than 4 2^L - 4 pixels outside it, so
+ *   the window truncates nothing unless the photo's border clamps it (there the pyramid sees zeros beyond the border).
+ *   Level 0, per frame and window pixel: u, v, val_c and a exactly as eg3d_paste_back8's steps above give them (fp64, the same taps and
+ *     order; a = feather x mask).  !(u >= 0 && u < S && v >= 0 && v < S): D_c = 0, alpha = 0; else D_c = (float)(val_c - photo_c),
+ *     alpha = (float)a.  From here on fp32, every operation rounded on its own in the order written; fp32 subnormals are KEPT (the tails
+ *     of alpha reach them: a small feather value times 16^-2L), as numpy keeps them.
+ *   Reduce, level k -> k + 1, applied to every D_c and to alpha: size ceil(n / 2) per axis, taps outside the array read 0, rows first, then
+ *     columns; 1-D  r[i] = (((x[2i-2] + x[2i+2]) + 4 (x[2i-1] + x[2i+1])) + 6 x[2i]) (1/16).
+ *   Expand E to an h x w level: taps outside read 0, rows first, then columns; 1-D  even i = 2j: ((x[j-1] + x[j+1]) + 6 x[j]) (1/8),
+ *     odd i = 2j + 1: (x[j] + x[j+1]) 0.5.
+ *   Collapse: R_L = D_L alpha_L;  for k = L - 1 .. 0:  R_k = (D_k - E(D_k+1)) alpha_k + E(R_k+1).
+ *   out = uint8(min(max(rintf((float)photo_c + R_0), 0), 255)), ties to even.
+ *   alpha == 0 everywhere gives R == 0 exactly (the photo); alpha == 1 returns D only in the interior (zero extension makes alpha_k < 1
+ *   near the window's border).  With a mask, D is NOT premultiplied: the coarse bands carry some of the edit's colour from outside the
+ *   mask into a halo of at most M pixels.
+ *   whole = 1: dst holds the photograph per frame (eg3d_paste_back8's copy launch), and the whole window is written into it.  whole = 0: dst
+ *   holds the box only, the shape eg3d_paste_back8 gives; what the blend changes in the margin outside the box is dropped.  An empty box:
+ *   as eg3d_paste_back8 (needs no workspace).
+ *   workspace: fp32, [N][C + 1][h_k][w_k] (the planes of D_k, then alpha_k) for k = 1..L, then [N][C][h_k][w_k] (R_k) for k = 1..L - 1;
+ *   level 0 is never stored: blend_level1 samples it into LDS under each tile of level 1 (EG3D_BLEND_L1_TILE_W x _H level-0 pixels + a
+ *   2-pixel halo) and blend_compose samples it again per pixel (a workgroup writes EG3D_BLEND_COMPOSE_TILE_W x _H window pixels).
+ *   1 + (L - 1) + (L - 1) + 1 launches (+ the copy); no allocation, no synchronise: capturable.  No atomics, no sum across threads: both
+ *   builds give the same bytes.
+ *   Errors, before any launch: EG3D_ERR_INVALID for bands outside 1..EG3D_BLEND_MAX_BANDS, a NULL, short or misaligned (4 bytes) workspace
+ *   where one is needed, and everything eg3d_paste_back8 refuses.  eg3d_paste_blend8_query_workspace is host only. */
+#define EG3D_BLEND_MAX_BANDS 6
+#define EG3D_BLEND_L1_TILE_W 64
+#define EG3D_BLEND_L1_TILE_H 32
+#define EG3D_BLEND_COMPOSE_TILE_W 64
+#define EG3D_BLEND_COMPOSE_TILE_H 16
+typedef struct eg3d_paste_blend8_params {
+    const uint8_t* photo;              /* [Hp,Wp,C] */
+    const uint8_t* edits;              /* [N,S,S,C] */
+    const uint8_t* mask;               /* NULL, [S,S] (mask_frames = 1) or [N,S,S] (mask_frames = N) */
+    uint8_t* dst;
+    double m[6];
+    double inv_feather;                /* 1 / feather width in aligned pixels; 0: a hard edge */
+    int32_t N, Hp, Wp, C, S;
+    int32_t x0, y0, x1, y1;            /* the bounding box; the entry derives the window */
+    int32_t mask_frames;               /* 1 or N; ignored without a mask */
+    int32_t whole;
+    int32_t layout;
+    int32_t bands;                     /* L = 1..EG3D_BLEND_MAX_BANDS */
+    void* workspace;                   /* eg3d_paste_blend8_query_workspace's bytes */
+    int64_t workspace_bytes;
+} eg3d_paste_blend8_params;
+int eg3d_paste_blend8_query_workspace(const eg3d_paste_blend8_params* p, int64_t* workspace_bytes);
+int eg3d_paste_blend8(const eg3d_paste_blend8_params* p, void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Head mattes (csrc/matte.hip; no reference counterpart -- the reference thresholds its depth, training/warping_loss.py:12-16, and never
  * pastes).  From a ragged binary mask in the aligned frame to the soft uint8 matte eg3d_paste_back8 takes as `mask`: an exact Euclidean

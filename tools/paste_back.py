@@ -3,12 +3,15 @@ this package (inv3d_amd/images.py paste_back, csrc/imgprep.hip).  No reference c
 
   python tools/paste_back.py --photo photo.jpg --landmarks landmarks.json --edit a_inter_1.png a_inter_2.png --out-dir pasted
                              [--feather 0.08] [--mask mask.png [--mask-binary [--matte-feather 0.03] [--matte-shrink 0]]] [--bbox]
+                             [--paste-bands N|auto]
 
 --landmarks: a .json {name: 68 x 2} or an .npz with an entry for the photo (its file name up to the first dot) -- the points align_face took.
 --edit: square RGB images in the aligned frame (any side); each is written as {out-dir}/{edit name}.png, the whole photograph with the edit in
 it, or with --bbox only the face's bounding box in the photo.  --feather: the blend ramp from the frame's edge as a fraction of the side.
 --mask: a grey image of the edits' side in the aligned frame, 255 = all of the edit.  --mask-binary: the file is a raw binary mask instead
-(nonzero = head, e.g. a segmentation): it goes through images.matte_from_mask first (specks removed, holes closed, the edge feathered)."""
+(nonzero = head, e.g. a segmentation): it goes through images.matte_from_mask first (specks removed, holes closed, the edge feathered).
+--paste-bands: 1..6 or auto -- the multi-band blend (images.paste_back(bands=...), csrc/blend.hip) instead of the one alpha; 0, the default,
+writes what the tool wrote before the option existed."""
 import argparse
 import os
 import sys
@@ -33,8 +36,14 @@ def main(argv=None):
     ap.add_argument('--matte-feather', type=float, default=0.03, help="--mask-binary: the matte edge's ramp as a fraction of the side")
     ap.add_argument('--matte-shrink', type=float, default=0.0, help='--mask-binary: move the matte edge inwards by this fraction of the side')
     ap.add_argument('--bbox', action='store_true')
+    ap.add_argument('--paste-bands', default='0', metavar='N|auto', help='multi-band blend of 1..6 levels, or auto (images.paste_bands); 0: one alpha')
     a = ap.parse_args(argv)
     from inv3d_amd import images, video
+    try:
+        bands = images.bands_arg(a.paste_bands)
+    except ValueError as e:
+        raise SystemExit(f'--paste-bands: {e}')
+    bkw = dict(bands=bands) if bands != 0 else {}
     dev = torch.device('cuda')
     lms, key = images.load_landmarks(a.landmarks), os.path.basename(a.photo).split('.')[0]
     if key not in lms:
@@ -56,7 +65,7 @@ def main(argv=None):
     for path in a.edit:
         edit = images.decode_rgb(path, dev)
         out = os.path.join(a.out_dir, os.path.basename(path).split('.')[0] + '.png')
-        video.write_png(out, images.paste_back(photo, edit, lms[key], feather=a.feather, mask=mask, region='bbox' if a.bbox else 'photo'),
+        video.write_png(out, images.paste_back(photo, edit, lms[key], feather=a.feather, mask=mask, region='bbox' if a.bbox else 'photo', **bkw),
                         encoder='gpu' if a.png_gpu else 'host')
         written.append(out)
         print(out)

@@ -11,7 +11,8 @@ With --shape, --keep N / --min-voxels M / --connectivity {6,26} remove floaters 
 --paste-photo P --landmarks L blends every frame back into the photograph P the latent was inverted from (images.paste_back): the video
 shows the face's bounding box in the photo, with --paste-whole the whole photograph.  --paste-matte [--matte-feather F] [--matte-shrink F]
 pastes every frame through its own head matte (images.head_matte, from the depth of the frame's render): the photograph's background stays
-around the head.  --synthetic small: the 32-wide synthetic generator of the tests instead of the full-size one."""
+around the head.  --paste-bands N|auto: the multi-band blend of images.paste_back(bands=...) instead of the one alpha (with the matte too).
+--synthetic small: the 32-wide synthetic generator of the tests instead of the full-size one."""
 import argparse
 import os
 import sys
@@ -50,10 +51,13 @@ def main(argv=None):
     ap.add_argument('--paste-matte', action='store_true', help="--paste-photo: paste every frame through its head's matte (images.head_matte)")
     ap.add_argument('--matte-feather', type=float, default=0.03, help="--paste-matte: the matte edge's ramp as a fraction of the side")
     ap.add_argument('--matte-shrink', type=float, default=0.0, help='--paste-matte: move the matte edge inwards by this fraction of the side')
+    ap.add_argument('--paste-bands', default='0', metavar='N|auto', help='--paste-photo: multi-band blend of 1..6 levels, or auto (images.paste_bands); 0: one alpha')
     ap.add_argument('--synthetic', choices=('full', 'small'), default='full', help='without --weights: which synthetic generator')
     a = ap.parse_args(argv)
     if a.paste_matte and a.paste_photo is None:
         raise SystemExit('--paste-matte belongs to --paste-photo')
+    if a.paste_bands != '0' and a.paste_photo is None:
+        raise SystemExit('--paste-bands belongs to --paste-photo')
     from inv3d_amd import video as V
     dev = torch.device('cuda')
     if a.weights:
@@ -84,6 +88,11 @@ def main(argv=None):
     pkw = dict(region='photo') if a.paste_whole else {}
     if a.paste_matte:
         pkw['matte'] = dict(feather=a.matte_feather, shrink=a.matte_shrink)
+    if a.paste_bands != '0':
+        try:
+            pkw['bands'] = images.bands_arg(a.paste_bands)
+        except ValueError as e:
+            raise SystemExit(f'--paste-bands: {e}')
     t0 = time.perf_counter()
     n = V.write_orbit_video(G, ws, a.out, num_frames=a.frames, image_mode='image_depth' if a.depth else 'image', fps=a.fps, quality=a.quality,
                             batch=a.batch, shape=a.shape, shape_kwargs=dict(level=a.shape_level, grid_res=a.shape_grid, shade=a.shape_shade, **clean),

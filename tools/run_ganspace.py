@@ -10,7 +10,8 @@ edit  takes a pivot as the coach's save_pivot writes it ({name}_ws.npy [1, num_w
       ganspace.GANSPACE_DIRECTIONS or its four numbers (component, first layer, layers, power); writes {name}_grid.png and, with --save-images,
       {name}_inter_{i}.png (i from 1) as the reference names them.  With --paste-photo P --landmarks L (no reference counterpart) also
       {name}_pasted.png: every edit blended back into the photograph P (images.paste_back), the face's bounding box of each side by side;
-      with --paste-matte [--matte-feather F] [--matte-shrink F] each through its own head matte (images.head_matte, from the edit's depth).
+      with --paste-matte [--matte-feather F] [--matte-shrink F] each through its own head matte (images.head_matte, from the edit's depth);
+      with --paste-bands N|auto through the multi-band blend (images.paste_back(bands=...)) instead of the one alpha.
 --weights: a generator archive (inv3d_amd.weights, tools/convert_eg3d_pickle.py); otherwise a synthetic generator (inv3d_amd.synthetic, weights
 seed --seed): 'full' is the full-size one, 'small' the 32-wide one of the tests."""
 import argparse
@@ -71,6 +72,7 @@ def _parser():
     ed.add_argument('--landmarks', default=None, help='--paste-photo: a .json / .npz of 68 x 2 landmarks with an entry for the photo (or --name)')
     ed.add_argument('--paste-feather', type=float, default=0.08)
     ed.add_argument('--paste-matte', action='store_true', help="--paste-photo: paste every edit through its head's matte (images.head_matte)")
+    ed.add_argument('--paste-bands', default='0', metavar='N|auto', help='--paste-photo: multi-band blend of 1..6 levels, or auto (images.paste_bands); 0: one alpha')
     ed.add_argument('--matte-feather', type=float, default=0.03, help="--paste-matte: the matte edge's ramp as a fraction of the side")
     ed.add_argument('--matte-shrink', type=float, default=0.0, help='--paste-matte: move the matte edge inwards by this fraction of the side')
     return ap
@@ -118,7 +120,11 @@ def main(argv=None):
         key = key if key in lms else a.name
         if key not in lms:
             raise SystemExit(f'{a.landmarks} has no entry for {os.path.basename(a.paste_photo)} or {a.name}')
-        kw = {}
+        try:
+            bands = images.bands_arg(a.paste_bands)
+        except ValueError as e:
+            raise SystemExit(f'--paste-bands: {e}')
+        kw = dict(bands=bands) if bands != 0 else {}
         if a.paste_matte:                                                      # one matte per edit, from the depth of the edit's own render
             kw['mask'] = images.head_matte(G, None, None, size=out['images'].shape[1], depth=out['depth'], feather=a.matte_feather,
                                            shrink=a.matte_shrink)

@@ -4,13 +4,15 @@ landmarks are given (inv3d_amd/images.py), then InversionCoach.run -- Phase A, P
   python tools/run_inversion.py --in-dir photos --out-dir out [--landmarks landmarks.json] [--weights G.safetensors | --synthetic small|full]
                                 [--steps-a 400] [--steps-b 400] [--optimize-pose] [--graph] [--save-grid] [--gen-video] [--gen-mesh]
                                 [--mesh-format .mrc|.ply] [--mesh-res 512] [--do-evaluation] [--save-pivot] [--paste-back]
+                                [--paste-bands N|auto]
 
 Images with an entry in --landmarks (a .json {name: 68 x 2} or an .npz) are aligned to the generator's resolution; the others must have it
 already.  --weights: a generator archive (inv3d_amd.weights, tools/convert_eg3d_pickle.py); otherwise a synthetic generator.  Outputs go to
 {out-dir}/media (grids, videos), /mesh, /eval, /pivot; a summary line per image and the totals are printed.  --paste-back also writes
 {out-dir}/pasted/{name}.png for every image that had landmarks: the tuned reconstruction blended back into the photograph it was aligned
 from (images.paste_back); with --paste-matte [--matte-feather F] [--matte-shrink F] through the head's own matte (images.head_matte, from the
-depth of the same render), so the photograph's background stays around the head."""
+depth of the same render), so the photograph's background stays around the head; with --paste-bands N|auto blended through a Laplacian
+pyramid of N levels (images.paste_back(bands=...)) instead of the one alpha."""
 import argparse
 import os
 import sys
@@ -68,10 +70,17 @@ def main(argv=None):
     ap.add_argument('--paste-matte', action='store_true', help="--paste-back: paste through the head's matte (images.head_matte), not the whole square")
     ap.add_argument('--matte-feather', type=float, default=0.03, help="--paste-matte: the matte edge's ramp as a fraction of the aligned side")
     ap.add_argument('--matte-shrink', type=float, default=0.0, help='--paste-matte: move the matte edge inwards by this fraction of the aligned side')
+    ap.add_argument('--paste-bands', default='0', metavar='N|auto', help='--paste-back: multi-band blend of 1..6 levels, or auto (images.paste_bands); 0: one alpha')
     a = ap.parse_args(argv)
     if a.paste_matte and not a.paste_back:
         raise SystemExit('--paste-matte belongs to --paste-back')
     from inv3d_amd import images
+    try:
+        bands = images.bands_arg(a.paste_bands)
+    except ValueError as e:
+        raise SystemExit(f'--paste-bands: {e}')
+    if bands != 0 and not a.paste_back:
+        raise SystemExit('--paste-bands belongs to --paste-back')
     from inv3d_amd.coach import InversionCoach
     dev = torch.device('cuda')
     G = _generator(a, dev)
@@ -91,7 +100,7 @@ def main(argv=None):
             if name not in lms:
                 return
             os.makedirs(sub('pasted'), exist_ok=True)
-            kw = {}
+            kw = dict(bands=bands) if bands != 0 else {}
             if a.paste_matte:                                                  # the head's own matte, from the depth of the same render
                 kw['mask'] = images.head_matte(G, None, None, size=img.shape[-1], depth=depth, feather=a.matte_feather, shrink=a.matte_shrink)
             pasted = images.paste_back(images.decode_rgb(paths[name], dev), img.float(), lms[name], feather=a.paste_feather, **kw)

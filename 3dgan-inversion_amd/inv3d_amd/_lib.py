@@ -335,6 +335,21 @@ JPEG_F32, JPEG_U8 = 0, 1
 JPEG_444, JPEG_420 = 0, 1
 
 
+class JpegDecParams(C.Structure):
+    """eg3d_jpegdec_params: baseline JPEG decoder (eg3d_jpegdec_query_workspace / eg3d_jpegdec_decode)."""
+    _fields_ = [('data', C.c_void_p), ('data_bytes', C.c_int64), ('tables', C.c_void_p), ('workspace', C.c_void_p), ('workspace_bytes', C.c_int64),
+                ('out', C.c_void_p), ('result', C.c_void_p), ('H', C.c_int32), ('W', C.c_int32), ('ncomp', C.c_int32), ('hsamp', C.c_int32),
+                ('vsamp', C.c_int32), ('tq', C.c_int32 * 3), ('td', C.c_int32 * 3), ('ta', C.c_int32 * 3), ('restart_interval', C.c_int32),
+                ('subseq_bytes', C.c_int32), ('stages', C.c_int32)]
+
+
+JPEGDEC_TABLE_BYTES = 256 + 4 * 272      # EG3D_JPEGDEC_TABLE_BYTES
+JPEGDEC_RESULT_WORDS = 8                 # EG3D_JPEGDEC_RESULT_WORDS
+JPEGDEC_STAGES = dict(markers=1, sync=2, write=4, idct=8, colour=16)      # EG3D_JPEGDEC_STAGE_*
+JPEGDEC_ERRORS = {1: 'a marker inside the entropy-coded data', 2: 'restart markers missing, surplus or out of sequence',
+                  4: 'a restart segment with another number of blocks than the geometry has', 8: 'bits that are no Huffman code, or a run past coefficient 63'}
+
+
 class PngParams(C.Structure):
     """eg3d_png_params: PNG encoder (eg3d_png_query_workspace / eg3d_png_encode / eg3d_png_pack)."""
     _fields_ = [('img', C.c_void_p), ('workspace', C.c_void_p), ('workspace_bytes', C.c_int64), ('offsets', C.c_void_p), ('out', C.c_void_p),
@@ -564,6 +579,8 @@ _SIGS = {
     'eg3d_jpeg_query_workspace': (C.c_int, [C.POINTER(JpegParams), C.POINTER(C.c_int64)]),
     'eg3d_jpeg_encode': (C.c_int, [C.POINTER(JpegParams), C.c_void_p]),
     'eg3d_jpeg_pack': (C.c_int, [C.POINTER(JpegParams), C.c_void_p]),
+    'eg3d_jpegdec_query_workspace': (C.c_int, [C.POINTER(JpegDecParams), C.POINTER(C.c_int64)]),
+    'eg3d_jpegdec_decode': (C.c_int, [C.POINTER(JpegDecParams), C.c_void_p]),
     'eg3d_png_query_workspace': (C.c_int, [C.POINTER(PngParams), C.POINTER(C.c_int64)]),
     'eg3d_png_encode': (C.c_int, [C.POINTER(PngParams), C.c_void_p]),
     'eg3d_png_pack': (C.c_int, [C.POINTER(PngParams), C.c_void_p]),

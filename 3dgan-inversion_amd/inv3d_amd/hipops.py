@@ -2570,6 +2570,84 @@ def jpeg_encode(img: torch.Tensor, quality: int = 90, subsampling: str = '420', 
     return out, offsets
 
 
+class JpegDecodeRefused(L.Eg3dHipError):
+    """hipops.jpeg_decode: the device ended in a non-zero status (a damaged or unusual entropy-coded stream); .status holds the bits."""
+
+    def __init__(self, status: int):
+        why = '; '.join(text for bit, text in L.JPEGDEC_ERRORS.items() if status & bit)
+        super().__init__(f'jpeg_decode: the device refused the entropy-coded data: status {status} ({why})')
+        self.status = status
+
+
+def jpeg_decode_tables(plan) -> bytes:
+    """eg3d_jpegdec_params.tables for a video.JpegScanPlan: the quantisation tables 0..3 (natural order, zeros where the file has none), then
+    the Huffman tables DC 0, DC 1, AC 0, AC 1 as BITS[16] HUFFVAL[256] (zeros where the file has none)."""
+    blob = bytearray()
+    for q in plan.quant:
+        blob += bytes(q) if q is not None else bytes(64)
+    for key in ((0, 0), (0, 1), (1, 0), (1, 1)):
+        bits, vals = plan.huffman.get(key, ((0,) * 16, ()))
+        blob += bytes(bits) + bytes(vals) + bytes(256 - len(vals))
+    assert len(blob) == L.JPEGDEC_TABLE_BYTES
+    return bytes(blob)
+
+
+def _jpegdec_begin(raw: bytes, subseq_bytes: int, device=None):
+    """Parse, upload and allocate for one eg3d_jpegdec_decode: (params, tensors the params point into, out, result)."""
+    from . import video as V
+    B = int(subseq_bytes)
+    if not (16 <= B <= 1024 and B & (B - 1) == 0):
+        raise L.Eg3dHipError(f'jpeg_decode: subseq_bytes a power of two in 16..1024, got {subseq_bytes}')
+    plan = V.jpeg_scan_plan(raw)
+    if not torch.cuda.is_available():
+        raise L.Eg3dHipError('jpeg_decode: no GPU (there is no fallback path)')
+    dev = torch.device('cuda' if device is None else device)
+    n = plan.scan_end - plan.scan_start
+    head = (L.JPEGDEC_TABLE_BYTES + 15) // 16 * 16
+    host = torch.zeros(head + (n + 15) // 16 * 16, dtype=torch.uint8)             # tables, then the entropy-coded segment, both 16-byte aligned
+    view = host.numpy()
+    view[:L.JPEGDEC_TABLE_BYTES] = np.frombuffer(jpeg_decode_tables(plan), dtype=np.uint8)
+    view[head:head + n] = np.frombuffer(raw, dtype=np.uint8, count=n, offset=plan.scan_start)
+    blob = host.to(dev)
+    comps = plan.components
+    p = L.JpegDecParams(data=blob.data_ptr() + head, data_bytes=n, tables=blob.data_ptr(), H=plan.height, W=plan.width, ncomp=len(comps),
+                        hsamp=comps[0].h, vsamp=comps[0].v, restart_interval=plan.restart_interval, subseq_bytes=B)
+    for c, comp in enumerate(comps):
+        p.tq[c], p.td[c], p.ta[c] = comp.tq, comp.td, comp.ta
+    nbytes = C.c_int64(0)
+    L.check(L.lib().eg3d_jpegdec_query_workspace(C.byref(p), C.byref(nbytes)), 'jpegdec_query_workspace')
+    ws = torch.empty(nbytes.value, dtype=torch.uint8, device=dev)
+    out = torch.empty((plan.height, plan.width, 3), dtype=torch.uint8, device=dev)
+    result = torch.empty(L.JPEGDEC_RESULT_WORDS, dtype=torch.int32, device=dev)
+    p.workspace, p.workspace_bytes, p.out, p.result = ws.data_ptr(), nbytes.value, out.data_ptr(), result.data_ptr()
+    return p, (blob, ws), out, result
+
+
+def jpeg_decode(data, subseq_bytes: int = 128, device=None, stats: Optional[dict] = None) -> torch.Tensor:
+    """uint8 [H,W,3] on the device: the pixels PIL.Image.open(file).convert('RGB') gives for a baseline JPEG file, byte for byte (eg3d_jpegdec_*;
+    include/eg3d_hip.h "Baseline JPEG decoder").  data: the file as bytes or as a host uint8 tensor.  The markers are parsed on the host
+    (video.jpeg_scan_plan: video.JpegUnsupported for what the decoder does not take -- progressive, CMYK, other sampling factors, ...); the
+    tables and the entropy-coded bytes go up in one copy; the device does the rest.  subseq_bytes (a power of two, 16..1024): the stretch of
+    the stream one lane of the self-synchronising Huffman decode owns.  A stream the device refuses (a stray marker, restart markers that do
+    not fit the geometry, a truncated or surplus segment, bits that are no code) raises JpegDecodeRefused (an Eg3dHipError) with the status: there is no fallback
+    here.  One host synchronise (the status).  stats, if given, receives status, rounds (of the synchronisation: inside the workgroups +
+    across them), lanes, unstuffed_bytes and restart_markers."""
+    if isinstance(data, torch.Tensor) and (data.is_cuda or data.dtype != torch.uint8 or data.dim() != 1):
+        raise L.Eg3dHipError(f'jpeg_decode: the file as bytes or a host uint8 [n] tensor, got {data.dtype} {tuple(data.shape)} on {data.device}')
+    raw = data.contiguous().numpy().tobytes() if isinstance(data, torch.Tensor) else bytes(data)
+    p, keep, out, result = _jpegdec_begin(raw, subseq_bytes, device)
+    with torch.cuda.device(out.device):
+        L.check(L.lib().eg3d_jpegdec_decode(C.byref(p), L.stream_ptr()), 'jpegdec_decode')
+        res = result.tolist()                                                      # the one synchronise
+    del keep
+    if stats is not None:
+        stats.update(status=res[0], rounds=res[1] + res[2], rounds_workgroup=res[1], rounds_across=res[2], lanes=res[3], unstuffed_bytes=res[4],
+                     restart_markers=res[5])
+    if res[0] != 0:
+        raise JpegDecodeRefused(res[0])
+    return out
+
+
 PNG_FILTERS = dict(adaptive=-1, none=0, sub=1, up=2, average=3, paeth=4)
 
 

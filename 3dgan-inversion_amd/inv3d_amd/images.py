@@ -13,7 +13,8 @@
   load_landmarks           <- a .json ({name: 68 x 2}) or .npz (one array per name) mapping
   load_targets             <- ImagesDataset / make_dataset + ToTensor / Normalize: the (name, target, None) tuples InversionCoach.run takes
 
-PIL decodes the files on the host (imported lazily, and only in load_targets); everything after the decode runs on the device."""
+PIL decodes the files on the host (imported lazily, and only in decode_rgb); decoder='gpu' moves the decode of baseline JPEG files to the
+device as well (hipops.jpeg_decode, csrc/jpeg_decode.hip: the same bytes); everything after the decode runs on the device."""
 import json
 import math
 import os
@@ -327,8 +328,27 @@ def image_files(directory: str):
     return sorted(out)
 
 
-def decode_rgb(path: str, device) -> torch.Tensor:
-    """uint8 [H,W,3] on the device: PIL.Image.open(path).convert('RGB') -- the decode is host work."""
+DECODERS = ('pil', 'gpu')
+JPEG_EXTENSIONS = ('.jpg', '.jpeg')
+
+
+def decode_rgb(path: str, device, decoder: str = 'pil', report=None) -> torch.Tensor:
+    """uint8 [H,W,3] on the device: PIL.Image.open(path).convert('RGB').  decoder='pil': the decode is host work.  decoder='gpu': a file
+    whose name ends in .jpg / .jpeg (any case) is decoded on the device by hipops.jpeg_decode, to the same bytes; a JPEG the device decoder
+    does not take (video.JpegUnsupported: progressive, CMYK, ...) or refuses (a damaged stream: hipops.JpegDecodeRefused) and every other format take the
+    PIL path, so a bad file behaves as it does with decoder='pil'.  report(path, reason), if given, is told about every such JPEG."""
+    if decoder not in DECODERS:
+        raise ValueError(f'decode_rgb: decoder one of {DECODERS}, got {decoder!r}')
+    if decoder == 'gpu' and path.lower().endswith(JPEG_EXTENSIONS):
+        from . import hipops
+        from .video import JpegUnsupported
+        try:
+            with open(path, 'rb') as f:
+                data = f.read()
+            return hipops.jpeg_decode(data, device=device)
+        except (JpegUnsupported, hipops.JpegDecodeRefused) as e:                   # (any other error -- a failed launch, no GPU -- is the caller's)
+            if report is not None:
+                report(path, str(e))
     from PIL import Image
     with Image.open(path) as im:
         arr = np.array(im.convert('RGB'), dtype=np.uint8)
@@ -336,12 +356,15 @@ def decode_rgb(path: str, device) -> torch.Tensor:
 
 
 def write_aligned(directory: str, landmarks, out_dir: str, output_size: int = 512, device='cuda', png_encoder: str = 'host', batch: int = 8,
-                  report=None):
+                  report=None, decoder: str = 'pil', decode_report=None):
     """{out_dir}/{name}.png for every image file of `directory` whose name has landmarks ({name: 68 x 2}, or the path of a .json / .npz):
     decoded on the host, aligned by align_face, written by video.write_png.  png_encoder='gpu': the aligned frames -- all output_size squared
     -- go `batch` at a time through one video.write_pngs (one encode, one copy).  Files without landmarks are passed to `report(path)` and
-    skipped.  Returns the paths written."""
+    skipped.  decoder='gpu': JPEG files are decoded on the device too (decode_rgb; decode_report(path, reason) hears of every JPEG that took
+    the PIL path instead); the files written are the same.  Returns the paths written."""
     from . import video
+    if decoder not in DECODERS:
+        raise ValueError(f'write_aligned: decoder one of {DECODERS}, got {decoder!r}')
     if png_encoder not in video.PNG_ENCODERS or batch < 1:
         raise ValueError(f'write_aligned: png_encoder one of {video.PNG_ENCODERS} and batch >= 1, got {png_encoder!r}, {batch}')
     if isinstance(landmarks, str):
@@ -359,7 +382,7 @@ def write_aligned(directory: str, landmarks, out_dir: str, output_size: int = 51
                 report(path)
             continue
         out = os.path.join(out_dir, name + '.png')
-        frame = align_face(decode_rgb(path, device), landmarks[name], output_size)
+        frame = align_face(decode_rgb(path, device, decoder, decode_report), landmarks[name], output_size)
         if png_encoder == 'gpu':
             pending.append((out, frame))
             if len(pending) == batch:
@@ -371,17 +394,20 @@ def write_aligned(directory: str, landmarks, out_dir: str, output_size: int = 51
     return written
 
 
-def load_targets(directory: str, landmarks=None, output_size: int = 512, device='cuda'):
+def load_targets(directory: str, landmarks=None, output_size: int = 512, device='cuda', decoder: str = 'pil', decode_report=None):
     """[(name, target fp32 [1,3,S,S] in [-1,1] on the device, None)] for InversionCoach.run, S = output_size: every image file of `directory` in
     sorted order, decoded to RGB; aligned by align_face where `landmarks` (a {name: 68 x 2} mapping, or the path of a .json / .npz holding
-    one) has its name, otherwise required to be S x S already; then ToTensor + Normalize(0.5, 0.5) (hipops.u8_to_target)."""
+    one) has its name, otherwise required to be S x S already; then ToTensor + Normalize(0.5, 0.5) (hipops.u8_to_target).  decoder='gpu':
+    JPEG files are decoded on the device (decode_rgb), to the same targets."""
     from . import hipops
+    if decoder not in DECODERS:
+        raise ValueError(f'load_targets: decoder one of {DECODERS}, got {decoder!r}')
     if isinstance(landmarks, str):
         landmarks = load_landmarks(landmarks)
     landmarks = landmarks or {}
     out = []
     for name, path in image_files(directory):
-        img = decode_rgb(path, device)
+        img = decode_rgb(path, device, decoder, decode_report)
         if name in landmarks:
             img = align_face(img, landmarks[name], output_size)
         elif tuple(img.shape[:2]) != (output_size, output_size):

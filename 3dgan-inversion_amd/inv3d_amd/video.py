@@ -2,6 +2,9 @@
 
   jpeg_tables, jpeg_header     <- the constant part of a baseline JFIF file: what hipops.jpeg_encode (csrc/jpeg.hip) puts in front of every
                                   frame's entropy-coded scan; quantisation tables scaled as libjpeg's jpeg_quality_scaling, Annex K Huffman tables
+  jpeg_scan_plan               the decoder's side of the format (no reference counterpart): a file's markers parsed into what hipops.jpeg_decode
+                                  (csrc/jpeg_decode.hip) needs -- geometry, tables, restart interval, the entropy-coded byte range -- or
+                                  JpegUnsupported with the reason
   MjpegAviWriter               <- imageio.get_writer(mp4, mode='I', fps=60, codec='libx264') of gen_interp_video, gen_videos.py:74-146: there
                                   is no video encoder to call, so the container is a Motion-JPEG AVI (RIFF 'AVI ', one 'MJPG' video stream,
                                   'idx1' index) written here, the frames are the GPU encoder's JFIF files
@@ -17,7 +20,7 @@ Everything but the rendering and hipops.jpeg_encode / png_encode / image_grid_u8
 import math
 import struct
 import zlib
-from typing import List, Optional, Tuple
+from typing import List, NamedTuple, Optional, Tuple
 
 import numpy as np
 import torch
@@ -105,6 +108,181 @@ def jpeg_header(height: int, width: int, quality: int = 90, subsampling: str = '
     h += _segment(0xDD, struct.pack('>H', R))
     h += _segment(0xDA, bytes([len(comps)]) + b''.join(bytes([cid, 0x00 if cid == 1 else 0x11]) for cid, _, _ in comps) + b'\x00\x3f\x00')
     return h
+
+
+# ---- the decoder's side of the format: what hipops.jpeg_decode (csrc/jpeg_decode.hip) needs to know about a file ---------------------------------
+class JpegUnsupported(ValueError):
+    """A JPEG file outside what the GPU decoder takes (jpeg_scan_plan); the message is the reason."""
+
+
+class JpegComponent(NamedTuple):
+    id: int
+    h: int                               # sampling factors
+    v: int
+    tq: int                              # quantisation table
+    td: int                              # DC Huffman table
+    ta: int                              # AC Huffman table
+
+
+class JpegScanPlan(NamedTuple):
+    height: int
+    width: int
+    components: Tuple[JpegComponent, ...]
+    quant: Tuple[Optional[Tuple[int, ...]], ...]          # the four tables Tq = 0..3 in natural order, None where the file defines none
+    huffman: dict                                         # {(tc, th): (BITS[1..16], HUFFVAL)}, tc 0 = DC, 1 = AC
+    restart_interval: int                                 # MCUs, 0 = none
+    scan_start: int                                       # data[scan_start:scan_end]: the entropy-coded segment (stuffing and RSTm included),
+    scan_end: int                                         # scan_end = the position of EOI's FF
+
+    @property
+    def subsampling(self) -> str:
+        return {(1, 1): '444', (2, 1): '422', (2, 2): '420'}[(self.components[0].h, self.components[0].v)] if len(self.components) == 3 else 'grey'
+
+
+JPEG_SAMPLINGS = ((1, 1), (2, 1), (2, 2))               # luma h x v beside 1 x 1 chroma: 4:4:4, 4:2:2, 4:2:0
+_SOF_NAMES = {0xC1: 'extended sequential', 0xC2: 'progressive', 0xC3: 'lossless', 0xC5: 'differential sequential', 0xC6: 'differential progressive',
+              0xC7: 'differential lossless', 0xC9: 'arithmetic-coded sequential', 0xCA: 'arithmetic-coded progressive', 0xCB: 'arithmetic-coded lossless',
+              0xCD: 'arithmetic-coded differential sequential', 0xCE: 'arithmetic-coded differential progressive', 0xCF: 'arithmetic-coded differential lossless'}
+
+
+def jpeg_scan_plan(data) -> JpegScanPlan:
+    """Parse a JPEG file's markers (SOI, APPn / COM skipped, DQT, SOF0, DHT, DRI, SOS, EOI) into what the GPU decoder needs.  Taken: 8-bit
+    baseline (SOF0), Huffman-coded, one interleaved scan of three components sampled 1x1 / 2x1 / 2x2 beside 1x1 chroma, or one component;
+    any legal Huffman tables, any restart interval.  Everything else raises JpegUnsupported with the reason: progressive, extended, 12-bit,
+    arithmetic coding, several scans, four components, other sampling factors, 16-bit quantisation tables, an Adobe APP14 segment with
+    transform 0 (RGB-coded), a truncated header, a missing EOI.  EXIF orientation is ignored, as PIL's open().convert() ignores it."""
+    data = bytes(data)
+    n = len(data)
+    if n < 4 or data[:2] != b'\xff\xd8':
+        raise JpegUnsupported('no SOI marker: not a JPEG file')
+    quant, huff = [None] * 4, {}
+    frame, restart, adobe_transform, pos = None, 0, None, 2
+
+    def truncated(what):
+        return JpegUnsupported(f'truncated header: the file ends inside {what}')
+    while True:
+        if pos + 2 > n:
+            raise truncated('the marker segments (no SOS)')
+        if data[pos] != 0xFF:
+            raise JpegUnsupported(f'byte {pos}: a marker was expected, found 0x{data[pos]:02x}')
+        marker = data[pos + 1]
+        if marker == 0xFF:                               # fill byte
+            pos += 1
+            continue
+        if marker == 0xD9:
+            raise JpegUnsupported('EOI before any scan')
+        if marker == 0x01 or 0xD0 <= marker <= 0xD7:     # stand-alone markers
+            pos += 2
+            continue
+        if pos + 4 > n:
+            raise truncated(f'marker 0x{marker:02x}')
+        length = struct.unpack_from('>H', data, pos + 2)[0]
+        if length < 2 or pos + 2 + length > n:
+            raise truncated(f'the segment of marker 0x{marker:02x}')
+        seg = data[pos + 4:pos + 2 + length]
+        pos += 2 + length
+        if marker == 0xDB:
+            i = 0
+            while i < len(seg):
+                pq, tq = seg[i] >> 4, seg[i] & 15
+                if pq != 0:
+                    raise JpegUnsupported('16-bit quantisation table')
+                if tq > 3 or i + 65 > len(seg):
+                    raise JpegUnsupported('malformed DQT segment')
+                nat = [0] * 64
+                for k in range(64):
+                    nat[ZIGZAG[k]] = seg[i + 1 + k]
+                quant[tq] = tuple(nat)
+                i += 65
+        elif marker == 0xC4:
+            i = 0
+            while i < len(seg):
+                if i + 17 > len(seg):
+                    raise JpegUnsupported('malformed DHT segment')
+                tc, th = seg[i] >> 4, seg[i] & 15
+                bits = tuple(seg[i + 1:i + 17])
+                count = sum(bits)
+                if tc > 1 or th > 3 or count > 256 or i + 17 + count > len(seg):
+                    raise JpegUnsupported('malformed DHT segment')
+                vals = tuple(seg[i + 17:i + 17 + count])
+                code = 0
+                for length_ in range(1, 17):             # the codes of every length must fit it, all-ones excluded (libjpeg: bogus Huffman table)
+                    code = (code + bits[length_ - 1]) << 1
+                    if bits[length_ - 1] and (code >> 1) > (1 << length_) - 1:
+                        raise JpegUnsupported('malformed DHT segment: over-subscribed code lengths')
+                if tc == 0 and any(v > 15 for v in vals):
+                    raise JpegUnsupported('malformed DHT segment: a DC category above 15')
+                huff[(tc, th)] = (bits, vals)
+                i += 17 + count
+        elif marker == 0xC0:
+            if frame is not None:
+                raise JpegUnsupported('more than one frame header')
+            if len(seg) < 6 or len(seg) < 6 + 3 * seg[5]:
+                raise JpegUnsupported('malformed SOF0 segment')
+            prec, hh, ww, nc = struct.unpack_from('>BHHB', seg, 0)
+            if prec != 8:
+                raise JpegUnsupported(f'{prec}-bit samples')
+            if hh == 0 or ww == 0:
+                raise JpegUnsupported('a frame of height or width 0 (DNL)')
+            comps = [(seg[6 + 3 * c], seg[7 + 3 * c] >> 4, seg[7 + 3 * c] & 15, seg[8 + 3 * c]) for c in range(nc)]
+            frame = (hh, ww, comps)
+        elif marker in _SOF_NAMES:
+            raise JpegUnsupported(f'{_SOF_NAMES[marker]} JPEG (SOF{marker - 0xC0}): baseline only')
+        elif marker == 0xCC:
+            raise JpegUnsupported('arithmetic coding (DAC)')
+        elif marker == 0xDD:
+            if len(seg) != 2:
+                raise JpegUnsupported('malformed DRI segment')
+            restart = struct.unpack('>H', seg)[0]
+        elif marker == 0xEE:
+            if len(seg) >= 12 and seg[:5] == b'Adobe':
+                adobe_transform = seg[11]
+        elif marker == 0xDA:
+            break
+        # APPn, COM and anything else with a length: skipped
+    if frame is None:
+        raise JpegUnsupported('SOS before SOF0')
+    hh, ww, comps = frame
+    if len(comps) not in (1, 3):
+        raise JpegUnsupported(f'{len(comps)} components: grey or YCbCr only')
+    if len(seg) < 1 or len(seg) != 4 + 2 * seg[0]:
+        raise JpegUnsupported('malformed SOS segment')
+    if seg[0] != len(comps):
+        raise JpegUnsupported('several scans (a non-interleaved file)')
+    if tuple(seg[1 + 2 * seg[0]:]) != (0, 63, 0):
+        raise JpegUnsupported('a scan that is not the full baseline spectrum')
+    out = []
+    for c, (cid, h, v, tq) in enumerate(comps):
+        if seg[1 + 2 * c] != cid:
+            raise JpegUnsupported('the scan lists the components in another order than the frame')
+        td, ta = seg[2 + 2 * c] >> 4, seg[2 + 2 * c] & 15
+        if tq > 3 or quant[tq] is None:
+            raise JpegUnsupported(f'component {cid} uses quantisation table {tq}, which the file does not define')
+        if td > 1 or ta > 1:
+            raise JpegUnsupported(f'component {cid} uses Huffman table {max(td, ta)}: baseline has tables 0 and 1')
+        if (0, td) not in huff or (1, ta) not in huff:
+            raise JpegUnsupported(f'component {cid} uses a Huffman table the file does not define')
+        out.append(JpegComponent(cid, h, v, tq, td, ta))
+    if len(out) == 3:
+        if adobe_transform == 0:
+            raise JpegUnsupported('Adobe APP14 transform 0: the components are RGB, not YCbCr')
+        if adobe_transform is None and tuple(c.id for c in out) == (0x52, 0x47, 0x42):
+            raise JpegUnsupported("component ids 'R', 'G', 'B': the components are RGB, not YCbCr")
+        if (out[0].h, out[0].v) not in JPEG_SAMPLINGS or (out[1].h, out[1].v, out[2].h, out[2].v) != (1, 1, 1, 1):
+            raise JpegUnsupported('sampling factors ' + ' / '.join(f'{c.h}x{c.v}' for c in out) + ': 4:4:4, 4:2:2 and 4:2:0 only')
+    else:
+        out[0] = out[0]._replace(h=1, v=1)               # one component: the factors mean nothing (T.81 A.2.2), the MCU is one block
+    # the entropy-coded segment ends at the first marker that is neither stuffing (FF 00), a restart (FF D0..D7) nor fill (FF FF)
+    a = np.frombuffer(data, dtype=np.uint8, offset=pos)
+    ff = np.flatnonzero(a[:-1] == 0xFF) if a.size > 1 else np.zeros(0, np.int64)
+    nxt = a[ff + 1]
+    ends = ff[(nxt != 0) & (nxt != 0xFF) & ((nxt < 0xD0) | (nxt > 0xD7))]
+    if ends.size == 0:
+        raise JpegUnsupported('missing EOI: the entropy-coded data runs to the end of the file')
+    end = pos + int(ends[0])
+    if data[end + 1] != 0xD9:
+        raise JpegUnsupported(f'marker 0x{data[end + 1]:02x} after the first scan: several scans or tables between them')
+    return JpegScanPlan(hh, ww, tuple(out), tuple(quant), huff, restart, pos, end)
 
 
 # ---- containers ------------------------------------------------------------------------------------------------------------------------------

@@ -1646,6 +1646,80 @@ int eg3d_jpeg_encode(const eg3d_jpeg_params* p, void* stream);
 int eg3d_jpeg_pack(const eg3d_jpeg_params* p, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Baseline JPEG decoder (target-image ingestion: PIL.Image.open(path).convert('RGB') of utils/ImagesDataset.py and utils/align_data.py for
+ * the files photographs arrive as; csrc/jpeg_decode.hip, csrc/jpeg_decode_core.h).  One image per call.  The output bytes are those of
+ * libjpeg(-turbo)'s default decode; tests/support/jpegdec_ref.py restates it.  Integers only, no floating point anywhere; the only atomics
+ * are ORs into the status word: the output is a function of the input bytes, bit-identical between runs and between the two builds.
+ *   Taken: 8-bit baseline (SOF0) Huffman-coded files with one interleaved scan of three components -- luma sampled hsamp x vsamp = 1 x 1
+ *   (4:4:4), 2 x 1 (4:2:2) or 2 x 2 (4:2:0) beside 1 x 1 chroma -- or of one component; any Huffman tables; any restart interval.  The caller
+ *   parses the markers (inv3d_amd/video.py jpeg_scan_plan) and passes
+ *     data    device, data_bytes: the entropy-coded segment between SOS and EOI as it stands in the file (stuffing and RSTm included),
+ *             16-byte aligned and readable up to the next multiple of 16
+ *     tables  device, EG3D_JPEGDEC_TABLE_BYTES: the quantisation tables Tq = 0..3 as uint8 [4][64] in natural (row-major) order, then the
+ *             Huffman tables DC 0, DC 1, AC 0, AC 1 as BITS[16] HUFFVAL[256] (zero-filled) each
+ *   Stages:
+ *   1. Marker pass.  Every FF xx of `data`: FF 00 is a stuffed FF, FF D0..D7 a restart marker, anything else (a trailing FF too) sets
+ *      EG3D_JPEGDEC_ERR_MARKER.  A scan and compaction give the unstuffed stream and the start of every restart segment in it.  A number of
+ *      restart markers other than the geometry's, or RSTm out of sequence: EG3D_JPEGDEC_ERR_SEGMENTS.
+ *   2. Self-synchronising Huffman decode.  Every restart segment is cut into subsequences of subseq_bytes (a power of two, 16..1024); one lane
+ *      owns one.  A lane's state is (bit position, block of the MCU, zigzag index).  A lane decodes symbols from its entry state until the bit
+ *      position reaches its subsequence's end, or the next symbol does not fit the segment, and records the state it leaves in.  The first lane
+ *      of a segment enters in the known state; every other lane first guesses (its first bit, block 0, index 0).  Then, in rounds, every lane
+ *      re-decodes from its left neighbour's recorded exit state whenever that changed, inside a workgroup of 256 lanes through LDS, then across
+ *      the workgroup borders, until a round changes nothing -- the fixed point, at which every recorded state is the true one.  The number of
+ *      subsequences bounds the rounds.
+ *   3. Coefficients.  Every lane counted the blocks it starts and summed the DC differences per component; an exclusive scan gives its first
+ *      block and its DC predictions (both relative to the segment's first lane: prediction restarts with the segment).  A last decode writes
+ *      the values into a zeroed int16 [blocks][64] in natural order, every store guarded by the segment's block range and index < 64; bits
+ *      beyond a segment's end read as zero.  A segment whose block total differs from the geometry's, or that ends inside a block:
+ *      EG3D_JPEGDEC_ERR_BLOCKS;  bits no code of the table matches, or a run past index 63: EG3D_JPEGDEC_ERR_CODE.
+ *   4. Dequantisation and jidctint.c's jpeg_idct_islow: CONST_BITS 13, PASS1_BITS 2, columns descaled by 11, rows by 18 (32-bit wrap-around
+ *      arithmetic), & 1023, libjpeg's range-limit table (the 10-bit value as signed, + 128, clamped) -> one uint8 plane per component, padded
+ *      to whole MCUs.
+ *   5. jdsample.c's fancy upsampling where the chroma has more than two real columns (h2v1: (3 a + left + 1) >> 2, (3 a + right + 2) >> 2;
+ *      h2v2: s = 3 near row + far row, (3 s + s_left + 8) >> 4, (3 s + s_right + 7) >> 4; neighbours clamped to the real down-sampled size
+ *      ceil(W / hsamp) x ceil(H / vsamp)), replication otherwise; jdcolor.c's YCbCr -> RGB: R = Y + ((91881 Cr' + 32768) >> 16),
+ *      G = Y + ((-22554 Cb' - 46802 Cr' + 32768) >> 16), B = Y + ((116130 Cb' + 32768) >> 16), Cb' = Cb - 128, clamped.  Grey is replicated.
+ *   out: uint8 [H][W][3].  result: int32 [EG3D_JPEGDEC_RESULT_WORDS] on the device, written by the call: [0] status (0, or an OR of
+ *   EG3D_JPEGDEC_ERR_*; `out` means nothing then), [1] rounds of stage 2 inside the workgroups that changed a state (the maximum over the
+ *   workgroups), [2] rounds across the borders, [3] lanes, [4] unstuffed bytes, [5] restart markers.  The caller reads it once.
+ *   Errors before any launch: EG3D_ERR_INVALID (NULL or misaligned pointers, sizes outside 1..65535, ncomp not 1 or 3, table selectors out of
+ *   range, subseq_bytes, a short workspace), EG3D_ERR_UNSUPPORTED (other sampling factors), EG3D_ERR_TOO_LARGE (data_bytes >= 2^28, or
+ *   more than 2^24 lanes).
+ *     eg3d_jpegdec_query_workspace  host only: workspace bytes (unstuffed stream, per-lane records, coefficients, planes)
+ *     eg3d_jpegdec_decode           twelve launches, no host synchronise
+ */
+#define EG3D_JPEGDEC_TABLE_BYTES (256 + 4 * 272)
+#define EG3D_JPEGDEC_RESULT_WORDS 8
+#define EG3D_JPEGDEC_ERR_MARKER 1
+#define EG3D_JPEGDEC_ERR_SEGMENTS 2
+#define EG3D_JPEGDEC_ERR_BLOCKS 4
+#define EG3D_JPEGDEC_ERR_CODE 8
+#define EG3D_JPEGDEC_STAGE_MARKERS 1  /* result zeroed; marker count, scan, apply */
+#define EG3D_JPEGDEC_STAGE_SYNC 2     /* segments, synchronisation inside and across the workgroups, prefix scan and checks */
+#define EG3D_JPEGDEC_STAGE_WRITE 4    /* coefficients zeroed and written */
+#define EG3D_JPEGDEC_STAGE_IDCT 8
+#define EG3D_JPEGDEC_STAGE_COLOUR 16
+typedef struct eg3d_jpegdec_params {
+    const uint8_t* data;               /* device: the entropy-coded segment */
+    int64_t data_bytes;
+    const uint8_t* tables;             /* device, EG3D_JPEGDEC_TABLE_BYTES */
+    void* workspace;                   /* eg3d_jpegdec_query_workspace's bytes, 16-byte aligned */
+    int64_t workspace_bytes;
+    uint8_t* out;                      /* device uint8 [H][W][3] */
+    int32_t* result;                   /* device int32 [EG3D_JPEGDEC_RESULT_WORDS] */
+    int32_t H, W;
+    int32_t ncomp;                     /* 1 | 3 */
+    int32_t hsamp, vsamp;              /* luma sampling factors (ignored for ncomp = 1) */
+    int32_t tq[3], td[3], ta[3];       /* per component: quantisation table 0..3, DC and AC Huffman table 0..1 */
+    int32_t restart_interval;          /* MCUs; 0 = none */
+    int32_t subseq_bytes;              /* 16..1024, a power of two */
+    int32_t stages;                    /* 0 = everything; else an OR of EG3D_JPEGDEC_STAGE_* to run alone on a workspace a full call filled (timing) */
+} eg3d_jpegdec_params;
+int eg3d_jpegdec_query_workspace(const eg3d_jpegdec_params* p, int64_t* workspace_bytes);
+int eg3d_jpegdec_decode(const eg3d_jpegdec_params* p, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * PNG encoder (media export: every lossless image the package writes -- grids, aligned targets, paste-back outputs, mesh previews, the OBJ
  * exporter's atlas; csrc/png.hip).  Adaptive row filters, then a deflate that only matches runs at distance 1 (what zlib's Z_RLE finds).
  *   img: contiguous uint8 [N][H][W][C], C = 1 (grey) or 3 (RGB), N >= 1, 1 <= H, W <= 16384.  Output: N complete zlib streams back to back

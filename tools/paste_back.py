@@ -31,6 +31,7 @@ def main(argv=None):
     ap.add_argument('--out-dir', required=True)
     ap.add_argument('--feather', type=float, default=0.08)
     ap.add_argument('--png-gpu', action='store_true', help='encode the PNGs on the GPU (hipops.png_encode: adaptive filters, run-length deflate)')
+    ap.add_argument('--jpeg-gpu', action='store_true', help='decode baseline JPEG inputs on the GPU (hipops.jpeg_decode: the same pixels as PIL; other files take the PIL path)')
     ap.add_argument('--mask', default=None)
     ap.add_argument('--mask-binary', action='store_true', help='--mask is a raw binary mask (nonzero = head): clean and feather it first')
     ap.add_argument('--matte-feather', type=float, default=0.03, help="--mask-binary: the matte edge's ramp as a fraction of the side")
@@ -48,7 +49,8 @@ def main(argv=None):
     lms, key = images.load_landmarks(a.landmarks), os.path.basename(a.photo).split('.')[0]
     if key not in lms:
         raise SystemExit(f'{a.landmarks} has no entry for {key}')
-    photo = images.decode_rgb(a.photo, dev)
+    decoder = 'gpu' if a.jpeg_gpu else 'pil'
+    photo = images.decode_rgb(a.photo, dev, decoder)
     mask = None
     if a.mask is not None:
         from PIL import Image
@@ -63,7 +65,7 @@ def main(argv=None):
     os.makedirs(a.out_dir, exist_ok=True)
     written = []
     for path in a.edit:
-        edit = images.decode_rgb(path, dev)
+        edit = images.decode_rgb(path, dev, decoder)
         out = os.path.join(a.out_dir, os.path.basename(path).split('.')[0] + '.png')
         video.write_png(out, images.paste_back(photo, edit, lms[key], feather=a.feather, mask=mask, region='bbox' if a.bbox else 'photo', **bkw),
                         encoder='gpu' if a.png_gpu else 'host')

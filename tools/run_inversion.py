@@ -60,6 +60,7 @@ def main(argv=None):
     ap.add_argument('--save-grid', action='store_true')
     ap.add_argument('--gen-video', action='store_true')
     ap.add_argument('--png-gpu', action='store_true', help='encode the PNGs on the GPU (hipops.png_encode: adaptive filters, run-length deflate)')
+    ap.add_argument('--jpeg-gpu', action='store_true', help='decode baseline JPEG inputs on the GPU (hipops.jpeg_decode: the same pixels as PIL; other files take the PIL path)')
     ap.add_argument('--gen-mesh', action='store_true')
     ap.add_argument('--mesh-format', choices=('.mrc', '.ply'), default='.mrc')
     ap.add_argument('--mesh-res', type=int, default=512)
@@ -85,7 +86,8 @@ def main(argv=None):
     dev = torch.device('cuda')
     G = _generator(a, dev)
     size = a.output_size or int(G.img_resolution)
-    targets = images.load_targets(a.in_dir, a.landmarks, output_size=size, device=dev)
+    decoder = 'gpu' if a.jpeg_gpu else 'pil'
+    targets = images.load_targets(a.in_dir, a.landmarks, output_size=size, device=dev, decoder=decoder)
     if not targets:
         raise SystemExit(f'no image files in {a.in_dir}')
     sub = lambda d: os.path.join(a.out_dir, d)
@@ -103,7 +105,7 @@ def main(argv=None):
             kw = dict(bands=bands) if bands != 0 else {}
             if a.paste_matte:                                                  # the head's own matte, from the depth of the same render
                 kw['mask'] = images.head_matte(G, None, None, size=img.shape[-1], depth=depth, feather=a.matte_feather, shrink=a.matte_shrink)
-            pasted = images.paste_back(images.decode_rgb(paths[name], dev), img.float(), lms[name], feather=a.paste_feather, **kw)
+            pasted = images.paste_back(images.decode_rgb(paths[name], dev, decoder), img.float(), lms[name], feather=a.paste_feather, **kw)
             write_png(os.path.join(sub('pasted'), f'{name}.png'), pasted[0], encoder='gpu' if a.png_gpu else 'host')
     samples = a.w_avg_samples if a.w_avg_samples is not None else (10000 if a.weights else 0)
     coach = InversionCoach(G, first_inv_steps=a.steps_a, max_pti_steps=a.steps_b, lpips_threshold=a.lpips_threshold, optimize_pose=a.optimize_pose,

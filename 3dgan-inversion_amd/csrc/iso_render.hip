@@ -6,9 +6,9 @@
 //   iso_render_kernel  one wave per 8x8 pixel tile of one camera (neighbouring rays walk neighbouring cells: their loads share cache lines), one
 //                      lane per ray.  The grid is read with plain global loads (512^3 is larger than every cache; the brick array, 1 MB, is not),
 //                      nothing is shared between lanes and nothing is accumulated: every output is a function of its own ray.
-// The arithmetic is the header's specification operation for operation: tests/support/iso_ref.py restates it and the outputs are compared
-// bit for bit, so nothing here may be reassociated, contracted or replaced by a reciprocal.
-#include "common.h"
+// The field, the frame, the normal and the camera maps are csrc/shape_common.h's; its rule holds here too: the arithmetic is the header's
+// specification operation for operation (tests/support/iso_ref.py restates it, the outputs are compared bit for bit).
+#include "shape_common.h"
 
 namespace {
 
@@ -17,12 +17,8 @@ constexpr int ISO_BRICK_THREADS = 256;
 constexpr int ISO_TILE = 8;
 constexpr int ISO_KMAX = 1 << 24;                     // float(k) is exact up to here
 
-struct IsoGrid {
-    const float* vol;
-    int32_t D0, D1, D2, S;                            // S = D1 * D2
-    int32_t B1, B2;
-    float h0, h1, h2;                                 // D - 1
-};
+using shape::Cell;
+using shape::Grid;
 
 __global__ void __launch_bounds__(ISO_BRICK_THREADS) iso_bricks_kernel(const float* __restrict__ vol, int32_t D0, int32_t D1, int32_t D2, int32_t B1,
                                                                       int32_t B2, float* __restrict__ bricks) {
@@ -54,52 +50,6 @@ __global__ void __launch_bounds__(ISO_BRICK_THREADS) iso_bricks_kernel(const flo
     }
 }
 
-__device__ __forceinline__ float iso_clamp(float p, float h) {
-    p = p > 0.0f ? p : 0.0f;                          // NaN -> 0
-    return p < h ? p : h;
-}
-
-__device__ __forceinline__ float iso_lerp(float a, float b, float f) {
-    float r = a + f * (b - a);
-    const float lo = a < b ? a : b, hi = a < b ? b : a;
-    r = r < lo ? lo : r;
-    r = r > hi ? hi : r;
-    return r;
-}
-
-struct IsoCell {
-    int32_t i0, i1, i2;
-    float f0, f1, f2;
-};
-
-// p already clamped to [0, h]
-__device__ __forceinline__ IsoCell iso_cell(const IsoGrid& g, float p0, float p1, float p2) {
-    IsoCell c;
-    c.i0 = min((int32_t)floorf(p0), g.D0 - 2);
-    c.i1 = min((int32_t)floorf(p1), g.D1 - 2);
-    c.i2 = min((int32_t)floorf(p2), g.D2 - 2);
-    c.f0 = p0 - (float)c.i0;
-    c.f1 = p1 - (float)c.i1;
-    c.f2 = p2 - (float)c.i2;
-    return c;
-}
-
-__device__ __forceinline__ float iso_trilinear(const IsoGrid& g, const IsoCell& c) {
-    const float* __restrict__ q = g.vol + ((int64_t)c.i0 * g.S + (int64_t)c.i1 * g.D2 + c.i2);
-    const float v000 = q[0], v001 = q[1], v010 = q[g.D2], v011 = q[g.D2 + 1];
-    const float v100 = q[g.S], v101 = q[g.S + 1], v110 = q[g.S + g.D2], v111 = q[g.S + g.D2 + 1];
-    const float c00 = iso_lerp(v000, v001, c.f2), c01 = iso_lerp(v010, v011, c.f2);
-    const float c10 = iso_lerp(v100, v101, c.f2), c11 = iso_lerp(v110, v111, c.f2);
-    const float c0 = iso_lerp(c00, c01, c.f1), c1 = iso_lerp(c10, c11, c.f1);
-    return iso_lerp(c0, c1, c.f0);
-}
-
-__device__ __forceinline__ float iso_field(const IsoGrid& g, float p0, float p1, float p2) {
-    return iso_trilinear(g, iso_cell(g, iso_clamp(p0, g.h0), iso_clamp(p1, g.h1), iso_clamp(p2, g.h2)));
-}
-
-__device__ __forceinline__ float iso_sel(float v0, float v1, float v2, int32_t w) { return w == 0 ? v0 : (w == 1 ? v1 : v2); }
-
 // one slab; returns false when the ray cannot meet it
 __device__ __forceinline__ bool iso_slab(float o, float d, float h, float& tn, float& tf) {
     if (d == 0.0f) return o >= 0.0f && o <= h;
@@ -119,8 +69,9 @@ __device__ __forceinline__ void iso_exit(float o, float d, int32_t b, float& te)
 }
 
 struct IsoArgs {
-    IsoGrid g;
+    Grid g;
     const float* bricks;
+    int32_t B1, B2;                                   // bricks per axis 1 and 2
     const float* cams;
     float* depth;
     float* normal;
@@ -128,8 +79,7 @@ struct IsoArgs {
     int32_t* hit_k;
     float* shade;
     int32_t res;
-    int32_t ax0, ax1, ax2;
-    float org0, org1, org2, sp0, sp1, sp2;
+    shape::Frame fr;
     float level, dt;
     int32_t refine, skip, shade_mode;
     float ambient, background;
@@ -140,23 +90,16 @@ __global__ void __launch_bounds__(ISO_TILE* ISO_TILE) iso_render_kernel(IsoArgs 
     const int32_t y = (int32_t)blockIdx.y * ISO_TILE + (int32_t)(threadIdx.x / ISO_TILE);
     const int32_t f = (int32_t)blockIdx.z;
     if (x >= a.res || y >= a.res) return;
-    const IsoGrid& g = a.g;
+    const Grid& g = a.g;
     const float* __restrict__ c = a.cams + (int64_t)f * 25;
-    const float fx = c[16], sk = c[17], cx = c[18], fy = c[20], cy = c[21];
-    const float xc = ((float)x + 0.5f) / (float)a.res, yc = ((float)y + 0.5f) / (float)a.res;
-    const float xl = (((xc - cx) + (cy * sk) / fy) - (sk * yc) / fy) / fx;
-    const float yl = (yc - cy) / fy;
-    float o[3], d[3];
-    for (int i = 0; i < 3; ++i) {
-        const float w = ((c[4 * i] * xl + c[4 * i + 1] * yl) + c[4 * i + 2]) + c[4 * i + 3];
-        o[i] = c[4 * i + 3];
-        d[i] = w - o[i];
-    }
-    const float dn = sqrtf((d[0] * d[0] + d[1] * d[1]) + d[2] * d[2]);
-    for (int i = 0; i < 3; ++i) d[i] = d[i] / dn;
-    const float oi0 = (iso_sel(o[0], o[1], o[2], a.ax0) - a.org0) / a.sp0, di0 = iso_sel(d[0], d[1], d[2], a.ax0) / a.sp0;
-    const float oi1 = (iso_sel(o[0], o[1], o[2], a.ax1) - a.org1) / a.sp1, di1 = iso_sel(d[0], d[1], d[2], a.ax1) / a.sp1;
-    const float oi2 = (iso_sel(o[0], o[1], o[2], a.ax2) - a.org2) / a.sp2, di2 = iso_sel(d[0], d[1], d[2], a.ax2) / a.sp2;
+    float xl, yl, o[3], d[3];
+    shape::pixel_to_local(c, x, y, a.res, xl, yl);
+    shape::local_to_world_dir(c, xl, yl, o, d);
+    float oi0, oi1, oi2;
+    shape::world_to_index(a.fr, o[0], o[1], o[2], oi0, oi1, oi2);
+    const float di0 = shape::sel(d[0], d[1], d[2], a.fr.ax0) / a.fr.sp0;
+    const float di1 = shape::sel(d[0], d[1], d[2], a.fr.ax1) / a.fr.sp1;
+    const float di2 = shape::sel(d[0], d[1], d[2], a.fr.ax2) / a.fr.sp2;
 
     float tn = 0.0f, tf = INFINITY;
     bool live = iso_slab(oi0, di0, g.h0, tn, tf);
@@ -173,10 +116,10 @@ __global__ void __launch_bounds__(ISO_TILE* ISO_TILE) iso_render_kernel(IsoArgs 
     int32_t k = 0;
     while (k <= K) {
         const float t = tn + (float)k * a.dt;
-        const IsoCell cell = iso_cell(g, iso_clamp(oi0 + t * di0, g.h0), iso_clamp(oi1 + t * di1, g.h1), iso_clamp(oi2 + t * di2, g.h2));
+        const Cell cell = shape::cell(g, shape::clamp(oi0 + t * di0, g.h0), shape::clamp(oi1 + t * di1, g.h1), shape::clamp(oi2 + t * di2, g.h2));
         if (a.skip) {
             const int32_t b0 = cell.i0 >> 3, b1 = cell.i1 >> 3, b2 = cell.i2 >> 3;
-            if (a.bricks[((int64_t)b0 * g.B1 + b1) * g.B2 + b2] <= a.level) {
+            if (a.bricks[((int64_t)b0 * a.B1 + b1) * a.B2 + b2] <= a.level) {
                 float te = INFINITY;
                 iso_exit(oi0, di0, b0, te);
                 iso_exit(oi1, di1, b1, te);
@@ -188,7 +131,7 @@ __global__ void __launch_bounds__(ISO_TILE* ISO_TILE) iso_render_kernel(IsoArgs 
                 continue;
             }
         }
-        const float v = iso_trilinear(g, cell);
+        const float v = shape::trilinear(g, cell);
         if (v > a.level) {
             hit = k;
             fb = v;
@@ -202,10 +145,10 @@ __global__ void __launch_bounds__(ISO_TILE* ISO_TILE) iso_render_kernel(IsoArgs 
         th = tn;
         if (hit > 0) {
             float ta = tn + (float)(hit - 1) * a.dt, tb = tn + (float)hit * a.dt;
-            float fa = iso_field(g, oi0 + ta * di0, oi1 + ta * di1, oi2 + ta * di2);
+            float fa = shape::field(g, oi0 + ta * di0, oi1 + ta * di1, oi2 + ta * di2);
             for (int32_t r = 0; r < a.refine; ++r) {
                 const float tm = ta + (tb - ta) * 0.5f;
-                const float fm = iso_field(g, oi0 + tm * di0, oi1 + tm * di1, oi2 + tm * di2);
+                const float fm = shape::field(g, oi0 + tm * di0, oi1 + tm * di1, oi2 + tm * di2);
                 if (fm > a.level) {
                     tb = tm;
                     fb = fm;
@@ -217,14 +160,8 @@ __global__ void __launch_bounds__(ISO_TILE* ISO_TILE) iso_render_kernel(IsoArgs 
             th = ta + (tb - ta) * ((a.level - fa) / (fb - fa));
             if (!(th >= ta && th <= tb)) th = tb;
         }
-        const float p0 = iso_clamp(oi0 + th * di0, g.h0), p1 = iso_clamp(oi1 + th * di1, g.h1), p2 = iso_clamp(oi2 + th * di2, g.h2);
-        const float u0 = iso_clamp(p0 + 1.0f, g.h0), l0 = iso_clamp(p0 - 1.0f, g.h0);
-        const float u1 = iso_clamp(p1 + 1.0f, g.h1), l1 = iso_clamp(p1 - 1.0f, g.h1);
-        const float u2 = iso_clamp(p2 + 1.0f, g.h2), l2 = iso_clamp(p2 - 1.0f, g.h2);
-        const float g0 = (iso_field(g, u0, p1, p2) - iso_field(g, l0, p1, p2)) / ((u0 - l0) * a.sp0);
-        const float g1 = (iso_field(g, p0, u1, p2) - iso_field(g, p0, l1, p2)) / ((u1 - l1) * a.sp1);
-        const float g2 = (iso_field(g, p0, p1, u2) - iso_field(g, p0, p1, l2)) / ((u2 - l2) * a.sp2);
-        for (int w = 0; w < 3; ++w) n[w] = -(a.ax0 == w ? g0 : (a.ax1 == w ? g1 : g2));
+        const float p0 = shape::clamp(oi0 + th * di0, g.h0), p1 = shape::clamp(oi1 + th * di1, g.h1), p2 = shape::clamp(oi2 + th * di2, g.h2);
+        shape::gradient_normal(g, a.fr, p0, p1, p2, n);
         const float len = sqrtf((n[0] * n[0] + n[1] * n[1]) + n[2] * n[2]);
         const bool ok = len > 0.0f;                   // false for a NaN gradient too
         for (int w = 0; w < 3; ++w) n[w] = ok ? n[w] / len : 0.0f;
@@ -243,9 +180,7 @@ __global__ void __launch_bounds__(ISO_TILE* ISO_TILE) iso_render_kernel(IsoArgs 
         float s[3] = {a.background, a.background, a.background};
         if (hit >= 0) {
             if (a.shade_mode == EG3D_ISO_LAMBERT) {
-                float l = -((n[0] * d[0] + n[1] * d[1]) + n[2] * d[2]);
-                l = l > 0.0f ? l : 0.0f;
-                const float v = a.ambient + (1.0f - a.ambient) * l;
+                const float v = shape::headlight(a.ambient, n, d);
                 s[0] = s[1] = s[2] = v * 2.0f - 1.0f;
             } else {
                 for (int j = 0; j < 3; ++j) {
@@ -262,62 +197,48 @@ __global__ void __launch_bounds__(ISO_TILE* ISO_TILE) iso_render_kernel(IsoArgs 
     }
 }
 
-bool iso_finite(float v) { return v == v && v - v == 0.0f; }
-
-// validates what both entries share; fills g
-int iso_grid(const eg3d_iso_params* p, IsoGrid& g, int32_t& B0) {
+// validates what both entries share; fills g and the bricks per axis
+int iso_grid(const eg3d_iso_params* p, Grid& g, int32_t B[3]) {
     if (p == nullptr || p->vol == nullptr) return EG3D_ERR_INVALID;
-    if (p->D0 < 2 || p->D1 < 2 || p->D2 < 2) return EG3D_ERR_INVALID;
-    if ((int64_t)p->D0 * p->D1 * p->D2 > INT32_MAX) return EG3D_ERR_TOO_LARGE;
-    g.vol = p->vol;
-    g.D0 = p->D0;
-    g.D1 = p->D1;
-    g.D2 = p->D2;
-    g.S = p->D1 * p->D2;
-    B0 = (p->D0 + 6) / ISO_BRICK;
-    g.B1 = (p->D1 + 6) / ISO_BRICK;
-    g.B2 = (p->D2 + 6) / ISO_BRICK;
-    g.h0 = (float)(p->D0 - 1);
-    g.h1 = (float)(p->D1 - 1);
-    g.h2 = (float)(p->D2 - 1);
+    const int s = shape::grid_fill(p->vol, p->D0, p->D1, p->D2, g);
+    if (s != EG3D_OK) return s;
+    B[0] = (p->D0 + 6) / ISO_BRICK;
+    B[1] = (p->D1 + 6) / ISO_BRICK;
+    B[2] = (p->D2 + 6) / ISO_BRICK;
     return EG3D_OK;
 }
 
 }  // namespace
 
 extern "C" int eg3d_iso_bricks(const eg3d_iso_params* p, void* stream) {
-    IsoGrid g;
-    int32_t B0;
-    const int s = iso_grid(p, g, B0);
+    Grid g;
+    int32_t B[3];
+    const int s = iso_grid(p, g, B);
     if (s != EG3D_OK) return s;
     if (p->bricks == nullptr) return EG3D_ERR_INVALID;
-    hipLaunchKernelGGL(iso_bricks_kernel, dim3((unsigned)(B0 * g.B1 * g.B2)), dim3(ISO_BRICK_THREADS), 0, (hipStream_t)stream, g.vol, g.D0, g.D1, g.D2,
-                       g.B1, g.B2, p->bricks);
+    hipLaunchKernelGGL(iso_bricks_kernel, dim3((unsigned)(B[0] * B[1] * B[2])), dim3(ISO_BRICK_THREADS), 0, (hipStream_t)stream, g.vol, g.D0, g.D1, g.D2,
+                       B[1], B[2], p->bricks);
     EG3D_LAUNCH_CHECK();
     return EG3D_OK;
 }
 
 extern "C" int eg3d_iso_render(const eg3d_iso_params* p, void* stream) {
     IsoArgs a;
-    int32_t B0;
-    const int s = iso_grid(p, a.g, B0);
+    int32_t B[3];
+    const int s = iso_grid(p, a.g, B);
     if (s != EG3D_OK) return s;
     if (p->cams == nullptr || p->F < 1 || p->res < 1) return EG3D_ERR_INVALID;
     if (p->skip != 0 && p->bricks == nullptr) return EG3D_ERR_INVALID;
-    int seen = 0;
-    for (int i = 0; i < 3; ++i) {
-        if (p->axes[i] < 0 || p->axes[i] > 2) return EG3D_ERR_INVALID;
-        seen |= 1 << p->axes[i];
-        if (!iso_finite(p->spacing[i]) || p->spacing[i] == 0.0f || !iso_finite(p->origin[i])) return EG3D_ERR_INVALID;
-    }
-    if (seen != 7) return EG3D_ERR_INVALID;
-    if (!iso_finite(p->level) || !(p->step >= 1.0f / 64 && p->step <= 64.0f) || p->refine < 0 || p->refine > 32) return EG3D_ERR_INVALID;
-    if (!(p->ambient >= 0.0f && p->ambient <= 1.0f) || !iso_finite(p->background)) return EG3D_ERR_INVALID;
+    if (!shape::frame_fill(p->axes, p->origin, p->spacing, a.fr)) return EG3D_ERR_INVALID;
+    if (!shape::finite(p->level) || !(p->step >= 1.0f / 64 && p->step <= 64.0f) || p->refine < 0 || p->refine > 32) return EG3D_ERR_INVALID;
+    if (!(p->ambient >= 0.0f && p->ambient <= 1.0f) || !shape::finite(p->background)) return EG3D_ERR_INVALID;
     if (p->shade_mode != EG3D_ISO_LAMBERT && p->shade_mode != EG3D_ISO_NORMAL) return EG3D_ERR_INVALID;
     if (p->res > 16384 || p->F > 65535) return EG3D_ERR_UNSUPPORTED;
     float ms = fabsf(p->spacing[0]);
     for (int i = 1; i < 3; ++i) ms = fabsf(p->spacing[i]) < ms ? fabsf(p->spacing[i]) : ms;
     a.bricks = p->bricks;
+    a.B1 = B[1];
+    a.B2 = B[2];
     a.cams = p->cams;
     a.depth = p->depth;
     a.normal = p->normal;
@@ -325,15 +246,6 @@ extern "C" int eg3d_iso_render(const eg3d_iso_params* p, void* stream) {
     a.hit_k = p->hit_k;
     a.shade = p->shade;
     a.res = p->res;
-    a.ax0 = p->axes[0];
-    a.ax1 = p->axes[1];
-    a.ax2 = p->axes[2];
-    a.org0 = p->origin[0];
-    a.org1 = p->origin[1];
-    a.org2 = p->origin[2];
-    a.sp0 = p->spacing[0];
-    a.sp1 = p->spacing[1];
-    a.sp2 = p->spacing[2];
     a.level = p->level;
     a.dt = p->step * ms;
     a.refine = p->refine;
@@ -341,7 +253,7 @@ extern "C" int eg3d_iso_render(const eg3d_iso_params* p, void* stream) {
     a.shade_mode = p->shade_mode;
     a.ambient = p->ambient;
     a.background = p->background;
-    if (!(a.dt > 0.0f) || !iso_finite(a.dt)) return EG3D_ERR_INVALID;
+    if (!(a.dt > 0.0f) || !shape::finite(a.dt)) return EG3D_ERR_INVALID;
     const unsigned tiles = (unsigned)((p->res + ISO_TILE - 1) / ISO_TILE);
     hipLaunchKernelGGL(iso_render_kernel, dim3(tiles, tiles, (unsigned)p->F), dim3(ISO_TILE * ISO_TILE), 0, (hipStream_t)stream, a);
     EG3D_LAUNCH_CHECK();

@@ -2,82 +2,37 @@
 //
 // Two kernels, one thread per vertex, nothing shared between threads and no atomics: every output is a function of its own vertex.
 //   mesh_normals_kernel  the gradient of the trilinear field at the vertex (24 field evaluations of 8 loads each; neighbouring vertices
-//                        read neighbouring cells).  The field functions restate csrc/iso_render.hip's: that file stays as it is.
+//                        read neighbouring cells).
 //   mesh_bake_kernel     walks the views in index order: projection, four depth taps, four image taps per channel.  Vertices arrive ordered
 //                        by owning grid point (mc_emit), so a wave projects to neighbouring pixels and its gathers share cache lines.  The view
 //                        index is uniform over the launch, so the 25 camera floats of a view are uniform loads, not one load per lane.
 //   mesh_texture_kernel  one thread per texel of the per-face atlas ("Mesh texture"): decodes its face and barycentrics, interpolates the
 //                        face's three vertices and runs the same view loop (mesh_blend_views, the one copy).
-// The arithmetic is the header's specification operation for operation: tests/support/mesh_ref.py restates it and the outputs are compared
-// bit for bit, so nothing here may be reassociated, contracted or replaced by a reciprocal.
-#include "common.h"
+// The field, the frame, the normal and the camera maps are csrc/shape_common.h's; its rule holds here too: the arithmetic is the header's
+// specification operation for operation (tests/support/mesh_ref.py restates it, the outputs are compared bit for bit).
+#include "shape_common.h"
 
 namespace {
 
 constexpr int MESH_THREADS = 256;
 
-struct MeshGrid {
-    const float* vol;
-    int32_t D0, D1, D2, S;                            // S = D1 * D2
-    float h0, h1, h2;                                 // D - 1
-};
-
-__device__ __forceinline__ float mesh_clamp(float p, float h) {
-    p = p > 0.0f ? p : 0.0f;                          // NaN -> 0
-    return p < h ? p : h;
-}
-
-__device__ __forceinline__ float mesh_lerp_clamped(float a, float b, float f) {
-    float r = a + f * (b - a);
-    const float lo = a < b ? a : b, hi = a < b ? b : a;
-    r = r < lo ? lo : r;
-    r = r > hi ? hi : r;
-    return r;
-}
-
-__device__ __forceinline__ float mesh_field(const MeshGrid& g, float p0, float p1, float p2) {
-    p0 = mesh_clamp(p0, g.h0);
-    p1 = mesh_clamp(p1, g.h1);
-    p2 = mesh_clamp(p2, g.h2);
-    const int32_t i0 = min((int32_t)floorf(p0), g.D0 - 2), i1 = min((int32_t)floorf(p1), g.D1 - 2), i2 = min((int32_t)floorf(p2), g.D2 - 2);
-    const float f0 = p0 - (float)i0, f1 = p1 - (float)i1, f2 = p2 - (float)i2;
-    const float* __restrict__ q = g.vol + ((int64_t)i0 * g.S + (int64_t)i1 * g.D2 + i2);
-    const float v000 = q[0], v001 = q[1], v010 = q[g.D2], v011 = q[g.D2 + 1];
-    const float v100 = q[g.S], v101 = q[g.S + 1], v110 = q[g.S + g.D2], v111 = q[g.S + g.D2 + 1];
-    const float c00 = mesh_lerp_clamped(v000, v001, f2), c01 = mesh_lerp_clamped(v010, v011, f2);
-    const float c10 = mesh_lerp_clamped(v100, v101, f2), c11 = mesh_lerp_clamped(v110, v111, f2);
-    return mesh_lerp_clamped(mesh_lerp_clamped(c00, c01, f1), mesh_lerp_clamped(c10, c11, f1), f0);
-}
-
-__device__ __forceinline__ float mesh_sel(float v0, float v1, float v2, int32_t w) { return w == 0 ? v0 : (w == 1 ? v1 : v2); }
-
 struct NormalArgs {
-    MeshGrid g;
+    shape::Grid g;
     const float* points;
     float* normals;
     int64_t V;
-    int32_t ax0, ax1, ax2;
-    float org0, org1, org2, sp0, sp1, sp2;
+    shape::Frame fr;
 };
 
 __global__ void __launch_bounds__(MESH_THREADS) mesh_normals_kernel(NormalArgs a) {
     const int64_t v = (int64_t)blockIdx.x * MESH_THREADS + threadIdx.x;
     if (v >= a.V) return;
-    const MeshGrid& g = a.g;
-    const float x0 = a.points[v * 3], x1 = a.points[v * 3 + 1], x2 = a.points[v * 3 + 2];
-    const float r0 = (mesh_sel(x0, x1, x2, a.ax0) - a.org0) / a.sp0;
-    const float r1 = (mesh_sel(x0, x1, x2, a.ax1) - a.org1) / a.sp1;
-    const float r2 = (mesh_sel(x0, x1, x2, a.ax2) - a.org2) / a.sp2;
+    const shape::Grid& g = a.g;
+    float r0, r1, r2;
+    shape::world_to_index(a.fr, a.points[v * 3], a.points[v * 3 + 1], a.points[v * 3 + 2], r0, r1, r2);
     float n[3] = {0.0f, 0.0f, 0.0f};
     if (r0 == r0 && r1 == r1 && r2 == r2) {           // a NaN index coordinate: no normal (the clamp would send it to index 0)
-        const float p0 = mesh_clamp(r0, g.h0), p1 = mesh_clamp(r1, g.h1), p2 = mesh_clamp(r2, g.h2);
-        const float u0 = mesh_clamp(p0 + 1.0f, g.h0), l0 = mesh_clamp(p0 - 1.0f, g.h0);
-        const float u1 = mesh_clamp(p1 + 1.0f, g.h1), l1 = mesh_clamp(p1 - 1.0f, g.h1);
-        const float u2 = mesh_clamp(p2 + 1.0f, g.h2), l2 = mesh_clamp(p2 - 1.0f, g.h2);
-        const float g0 = (mesh_field(g, u0, p1, p2) - mesh_field(g, l0, p1, p2)) / ((u0 - l0) * a.sp0);
-        const float g1 = (mesh_field(g, p0, u1, p2) - mesh_field(g, p0, l1, p2)) / ((u1 - l1) * a.sp1);
-        const float g2 = (mesh_field(g, p0, p1, u2) - mesh_field(g, p0, p1, l2)) / ((u2 - l2) * a.sp2);
-        for (int w = 0; w < 3; ++w) n[w] = -(a.ax0 == w ? g0 : (a.ax1 == w ? g1 : g2));
+        shape::gradient_normal(g, a.fr, shape::clamp(r0, g.h0), shape::clamp(r1, g.h1), shape::clamp(r2, g.h2), n);
         const float len = sqrtf((n[0] * n[0] + n[1] * n[1]) + n[2] * n[2]);
         const bool ok = len > 0.0f && len < INFINITY;  // false for a NaN or infinite component too
         for (int w = 0; w < 3; ++w) n[w] = ok ? n[w] / len : 0.0f;
@@ -115,8 +70,6 @@ struct BakeArgs {
     int64_t V;
 };
 
-__device__ __forceinline__ float mesh_lerp(float a, float b, float f) { return a + f * (b - a); }
-
 __device__ __forceinline__ bool mesh_inside(float p, float hi) { return p >= 0.0f && p <= hi; }      // false for NaN
 
 // Steps 1-5 of the header's "Mesh attributes" bake for one point p with normal n: the one copy of the view loop (mesh_bake_kernel and
@@ -128,16 +81,11 @@ __device__ __forceinline__ MeshBlend mesh_blend_views(const MeshViews& a, float 
     int32_t seen = 0;
     for (int32_t f = 0; f < a.F; ++f) {
         const float* __restrict__ m = a.cams + (int64_t)f * 25;
-        const float q0 = p0 - m[3], q1 = p1 - m[7], q2 = p2 - m[11];
+        float q0, q1, q2, c0, c1, c2, xc, yc;
+        shape::world_to_camera(m, p0, p1, p2, q0, q1, q2, c0, c1, c2);
         const float t = sqrtf((q0 * q0 + q1 * q1) + q2 * q2);
-        const float c0 = (m[0] * q0 + m[4] * q1) + m[8] * q2;
-        const float c1 = (m[1] * q0 + m[5] * q1) + m[9] * q2;
-        const float c2 = (m[2] * q0 + m[6] * q1) + m[10] * q2;
         if (!(t > 0.0f && c2 > 0.0f)) continue;
-        const float fx = m[16], sk = m[17], cx = m[18], fy = m[20], cy = m[21];
-        const float xl = c0 / c2, yl = c1 / c2;
-        const float yc = yl * fy + cy;
-        const float xc = ((xl * fx + cx) - (cy * sk) / fy) + (sk * yc) / fy;
+        shape::camera_to_image(m, c0, c1, c2, xc, yc);
         const float pxH = xc * fH - 0.5f, pyH = yc * fH - 0.5f;
         const float pxR = xc * fR - 0.5f, pyR = yc * fR - 0.5f;
         if (!(mesh_inside(pxH, hiH) && mesh_inside(pyH, hiH) && mesh_inside(pxR, hiR) && mesh_inside(pyR, hiR))) continue;
@@ -160,11 +108,11 @@ __device__ __forceinline__ MeshBlend mesh_blend_views(const MeshViews& a, float 
             const int32_t bx = min((int32_t)floorf(pxH), a.H - 2), by = min((int32_t)floorf(pyH), a.H - 2);
             const float tx = pxH - (float)bx, ty = pyH - (float)by;
             const float* __restrict__ s = ip + (int64_t)by * a.H + bx;
-            col0 = mesh_lerp(mesh_lerp(s[0], s[1], tx), mesh_lerp(s[a.H], s[a.H + 1], tx), ty);
+            col0 = shape::lerp(shape::lerp(s[0], s[1], tx), shape::lerp(s[a.H], s[a.H + 1], tx), ty);
             s += planeH;
-            col1 = mesh_lerp(mesh_lerp(s[0], s[1], tx), mesh_lerp(s[a.H], s[a.H + 1], tx), ty);
+            col1 = shape::lerp(shape::lerp(s[0], s[1], tx), shape::lerp(s[a.H], s[a.H + 1], tx), ty);
             s += planeH;
-            col2 = mesh_lerp(mesh_lerp(s[0], s[1], tx), mesh_lerp(s[a.H], s[a.H + 1], tx), ty);
+            col2 = shape::lerp(shape::lerp(s[0], s[1], tx), shape::lerp(s[a.H], s[a.H + 1], tx), ty);
         } else {
             col0 = ip[0];
             col1 = ip[1];
@@ -178,8 +126,6 @@ __device__ __forceinline__ MeshBlend mesh_blend_views(const MeshViews& a, float 
     }
     return MeshBlend{acc0, acc1, acc2, wsum, seen};
 }
-
-__device__ __forceinline__ uint8_t mesh_u8(float x) { return (uint8_t)(int)fminf(fmaxf(x * 127.5f + 128.f, 0.f), 255.f); }      // truncation, as eg3d_image_grid_u8
 
 __global__ void __launch_bounds__(MESH_THREADS) mesh_bake_kernel(BakeArgs a) {
     const int64_t v = (int64_t)blockIdx.x * MESH_THREADS + threadIdx.x;
@@ -202,9 +148,9 @@ __global__ void __launch_bounds__(MESH_THREADS) mesh_bake_kernel(BakeArgs a) {
         a.color[v * 3 + 2] = out2;
     }
     if (a.rgb) {
-        a.rgb[v * 3] = mesh_u8(out0);
-        a.rgb[v * 3 + 1] = mesh_u8(out1);
-        a.rgb[v * 3 + 2] = mesh_u8(out2);
+        a.rgb[v * 3] = shape::u8(out0);
+        a.rgb[v * 3 + 1] = shape::u8(out1);
+        a.rgb[v * 3 + 2] = shape::u8(out2);
     }
     if (a.weight) a.weight[v] = b.wsum;
     if (a.views) a.views[v] = (uint8_t)b.seen;
@@ -229,10 +175,6 @@ struct TextureArgs {
     int64_t V, F, texels;
     int32_t T, per_row, Ht, Wt, fill;
 };
-
-__device__ __forceinline__ int32_t mesh_seli(int32_t v0, int32_t v1, int32_t v2, int32_t w) { return w == 0 ? v0 : (w == 1 ? v1 : v2); }
-
-__device__ __forceinline__ float mesh_mix(float b0, float b1, float b2, float a0, float a1, float a2) { return (b0 * a0 + b1 * a1) + b2 * a2; }
 
 __global__ void mesh_texture_clear_kernel(int32_t* bad_faces) { *bad_faces = 0; }
 
@@ -280,16 +222,16 @@ __global__ void __launch_bounds__(MESH_THREADS) mesh_texture_kernel(TextureArgs 
                 const float b1 = (float)ii / (float)leg, b2 = (float)jj / (float)leg;
                 const float b0 = (1.0f - b1) - b2;
                 // corner r at the right angle, then the next two in the face's cyclic order
-                const int32_t c0 = mesh_seli(k0, k1, k2, r), c1 = mesh_seli(k1, k2, k0, r), c2 = mesh_seli(k2, k0, k1, r);
+                const int32_t c0 = shape::sel(k0, k1, k2, r), c1 = shape::sel(k1, k2, k0, r), c2 = shape::sel(k2, k0, k1, r);
                 const float* __restrict__ A0 = a.points + (int64_t)c0 * 3;
                 const float* __restrict__ A1 = a.points + (int64_t)c1 * 3;
                 const float* __restrict__ A2 = a.points + (int64_t)c2 * 3;
                 const float* __restrict__ N0 = a.normals + (int64_t)c0 * 3;
                 const float* __restrict__ N1 = a.normals + (int64_t)c1 * 3;
                 const float* __restrict__ N2 = a.normals + (int64_t)c2 * 3;
-                const MeshBlend b = mesh_blend_views(a.s, mesh_mix(b0, b1, b2, A0[0], A1[0], A2[0]), mesh_mix(b0, b1, b2, A0[1], A1[1], A2[1]),
-                                                     mesh_mix(b0, b1, b2, A0[2], A1[2], A2[2]), mesh_mix(b0, b1, b2, N0[0], N1[0], N2[0]),
-                                                     mesh_mix(b0, b1, b2, N0[1], N1[1], N2[1]), mesh_mix(b0, b1, b2, N0[2], N1[2], N2[2]));
+                const MeshBlend b = mesh_blend_views(a.s, shape::mix(b0, b1, b2, A0[0], A1[0], A2[0]), shape::mix(b0, b1, b2, A0[1], A1[1], A2[1]),
+                                                     shape::mix(b0, b1, b2, A0[2], A1[2], A2[2]), shape::mix(b0, b1, b2, N0[0], N1[0], N2[0]),
+                                                     shape::mix(b0, b1, b2, N0[1], N1[1], N2[1]), shape::mix(b0, b1, b2, N0[2], N1[2], N2[2]));
                 float out0 = 0.0f, out1 = 0.0f, out2 = 0.0f;
                 if (b.wsum > 0.0f) {
                     out0 = b.acc0 / b.wsum;
@@ -299,13 +241,13 @@ __global__ void __launch_bounds__(MESH_THREADS) mesh_texture_kernel(TextureArgs 
                     const float* __restrict__ F0 = a.fallback + (int64_t)c0 * 3;
                     const float* __restrict__ F1 = a.fallback + (int64_t)c1 * 3;
                     const float* __restrict__ F2 = a.fallback + (int64_t)c2 * 3;
-                    out0 = mesh_mix(b0, b1, b2, F0[0], F1[0], F2[0]);
-                    out1 = mesh_mix(b0, b1, b2, F0[1], F1[1], F2[1]);
-                    out2 = mesh_mix(b0, b1, b2, F0[2], F1[2], F2[2]);
+                    out0 = shape::mix(b0, b1, b2, F0[0], F1[0], F2[0]);
+                    out1 = shape::mix(b0, b1, b2, F0[1], F1[1], F2[1]);
+                    out2 = shape::mix(b0, b1, b2, F0[2], F1[2], F2[2]);
                 }
-                t0 = mesh_u8(out0);
-                t1 = mesh_u8(out1);
-                t2 = mesh_u8(out2);
+                t0 = shape::u8(out0);
+                t1 = shape::u8(out1);
+                t2 = shape::u8(out2);
                 seen = (uint8_t)b.seen;
             }
         } else if (lead && a.bad_faces) {
@@ -333,7 +275,17 @@ __global__ void __launch_bounds__(MESH_THREADS) mesh_texture_kernel(TextureArgs 
     if (a.views) a.views[o] = seen;
 }
 
-bool mesh_finite(float v) { return v == v && v - v == 0.0f; }
+// what eg3d_mesh_bake (P::F views) and eg3d_mesh_texture (P::N views) ask of their views: `count` is that number; fills s
+template <class P>
+int mesh_views(const P* p, int32_t count, MeshViews& s) {
+    if (count < 1 || p->H < 1 || p->R < 1) return EG3D_ERR_INVALID;
+    if (p->cams == nullptr || p->images == nullptr || p->depth == nullptr || p->mask == nullptr) return EG3D_ERR_INVALID;
+    if (!(p->depth_tol >= 0.0f) || !shape::finite(p->depth_tol) || !(p->cos_min >= 0.0f && p->cos_min < 1.0f)) return EG3D_ERR_INVALID;
+    if (p->power < 1 || p->power > 8) return EG3D_ERR_INVALID;
+    if (count > 255 || p->H > 16384 || p->R > 16384) return EG3D_ERR_UNSUPPORTED;
+    s = MeshViews{p->cams, p->images, p->depth, p->mask, count, p->H, p->R, p->depth_tol, p->cos_min, p->power};
+    return EG3D_OK;
+}
 
 // per_row = ceil(sqrt(nb)) in integers
 int64_t mesh_ceil_sqrt(int64_t nb) {
@@ -357,21 +309,18 @@ extern "C" int eg3d_mesh_texture_size(int64_t F, int32_t tile, int32_t* Ht, int3
 }
 
 extern "C" int eg3d_mesh_texture(const eg3d_mesh_texture_params* p, void* stream) {
-    if (p == nullptr || p->V < 0 || p->F < 0 || p->N < 1 || p->H < 1 || p->R < 1) return EG3D_ERR_INVALID;
-    if (p->cams == nullptr || p->images == nullptr || p->depth == nullptr || p->mask == nullptr) return EG3D_ERR_INVALID;
-    if (!(p->depth_tol >= 0.0f) || !mesh_finite(p->depth_tol) || !(p->cos_min >= 0.0f && p->cos_min < 1.0f)) return EG3D_ERR_INVALID;
-    if (p->power < 1 || p->power > 8) return EG3D_ERR_INVALID;
+    if (p == nullptr || p->V < 0 || p->F < 0) return EG3D_ERR_INVALID;
     if (p->tile < 4 || p->tile > 64 || p->fill < 0 || p->fill > 255) return EG3D_ERR_INVALID;
     if (p->F > 0 && p->faces == nullptr) return EG3D_ERR_INVALID;
     if (p->V > 0 && (p->points == nullptr || p->normals == nullptr)) return EG3D_ERR_INVALID;
-    if (p->N > 255 || p->H > 16384 || p->R > 16384) return EG3D_ERR_UNSUPPORTED;
+    TextureArgs a;
+    int rc = mesh_views(p, p->N, a.s);                // after the entry's own invalid arguments: every EG3D_ERR_INVALID precedes EG3D_ERR_UNSUPPORTED
+    if (rc != EG3D_OK) return rc;
     if (p->V > INT32_MAX) return EG3D_ERR_TOO_LARGE;
     int32_t Ht = 0, Wt = 0;
-    const int rc = eg3d_mesh_texture_size(p->F, p->tile, &Ht, &Wt);
+    rc = eg3d_mesh_texture_size(p->F, p->tile, &Ht, &Wt);
     if (rc != EG3D_OK) return rc;
     if (p->texture == nullptr && p->views == nullptr && p->uv == nullptr && p->corner == nullptr && p->bad_faces == nullptr) return EG3D_OK;
-    TextureArgs a;
-    a.s = MeshViews{p->cams, p->images, p->depth, p->mask, p->N, p->H, p->R, p->depth_tol, p->cos_min, p->power};
     a.points = p->points;
     a.normals = p->normals;
     a.faces = p->faces;
@@ -400,54 +349,29 @@ extern "C" int eg3d_mesh_texture(const eg3d_mesh_texture_params* p, void* stream
 
 extern "C" int eg3d_mesh_normals(const eg3d_mesh_normals_params* p, void* stream) {
     if (p == nullptr || p->vol == nullptr || p->V < 0) return EG3D_ERR_INVALID;
-    if (p->D0 < 2 || p->D1 < 2 || p->D2 < 2) return EG3D_ERR_INVALID;
-    int seen = 0;
-    for (int i = 0; i < 3; ++i) {
-        if (p->axes[i] < 0 || p->axes[i] > 2) return EG3D_ERR_INVALID;
-        seen |= 1 << p->axes[i];
-        if (!mesh_finite(p->spacing[i]) || p->spacing[i] == 0.0f || !mesh_finite(p->origin[i])) return EG3D_ERR_INVALID;
-    }
-    if (seen != 7) return EG3D_ERR_INVALID;
-    if ((int64_t)p->D0 * p->D1 * p->D2 > INT32_MAX || p->V > INT32_MAX) return EG3D_ERR_TOO_LARGE;
+    NormalArgs a;
+    const int gs = shape::grid_fill(p->vol, p->D0, p->D1, p->D2, a.g);
+    if (gs == EG3D_ERR_INVALID) return gs;
+    if (!shape::frame_fill(p->axes, p->origin, p->spacing, a.fr)) return EG3D_ERR_INVALID;      // a bad frame is reported before a grid that is too large
+    if (gs != EG3D_OK || p->V > INT32_MAX) return EG3D_ERR_TOO_LARGE;
     if (p->V == 0) return EG3D_OK;
     if (p->points == nullptr || p->normals == nullptr) return EG3D_ERR_INVALID;
-    NormalArgs a;
-    a.g.vol = p->vol;
-    a.g.D0 = p->D0;
-    a.g.D1 = p->D1;
-    a.g.D2 = p->D2;
-    a.g.S = p->D1 * p->D2;
-    a.g.h0 = (float)(p->D0 - 1);
-    a.g.h1 = (float)(p->D1 - 1);
-    a.g.h2 = (float)(p->D2 - 1);
     a.points = p->points;
     a.normals = p->normals;
     a.V = p->V;
-    a.ax0 = p->axes[0];
-    a.ax1 = p->axes[1];
-    a.ax2 = p->axes[2];
-    a.org0 = p->origin[0];
-    a.org1 = p->origin[1];
-    a.org2 = p->origin[2];
-    a.sp0 = p->spacing[0];
-    a.sp1 = p->spacing[1];
-    a.sp2 = p->spacing[2];
     hipLaunchKernelGGL(mesh_normals_kernel, dim3((unsigned)((p->V + MESH_THREADS - 1) / MESH_THREADS)), dim3(MESH_THREADS), 0, (hipStream_t)stream, a);
     EG3D_LAUNCH_CHECK();
     return EG3D_OK;
 }
 
 extern "C" int eg3d_mesh_bake(const eg3d_mesh_bake_params* p, void* stream) {
-    if (p == nullptr || p->V < 0 || p->F < 1 || p->H < 1 || p->R < 1) return EG3D_ERR_INVALID;
-    if (p->cams == nullptr || p->images == nullptr || p->depth == nullptr || p->mask == nullptr) return EG3D_ERR_INVALID;
-    if (!(p->depth_tol >= 0.0f) || !mesh_finite(p->depth_tol) || !(p->cos_min >= 0.0f && p->cos_min < 1.0f)) return EG3D_ERR_INVALID;
-    if (p->power < 1 || p->power > 8) return EG3D_ERR_INVALID;
-    if (p->F > 255 || p->H > 16384 || p->R > 16384) return EG3D_ERR_UNSUPPORTED;
+    if (p == nullptr || p->V < 0) return EG3D_ERR_INVALID;
+    BakeArgs a;
+    const int rc = mesh_views(p, p->F, a.s);
+    if (rc != EG3D_OK) return rc;
     if (p->V > INT32_MAX) return EG3D_ERR_TOO_LARGE;
     if (p->V == 0) return EG3D_OK;
     if (p->points == nullptr || p->normals == nullptr) return EG3D_ERR_INVALID;
-    BakeArgs a;
-    a.s = MeshViews{p->cams, p->images, p->depth, p->mask, p->F, p->H, p->R, p->depth_tol, p->cos_min, p->power};
     a.points = p->points;
     a.normals = p->normals;
     a.fallback = p->fallback;

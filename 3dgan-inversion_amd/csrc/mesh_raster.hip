@@ -12,9 +12,9 @@
 //                          of the box, one lane per pixel: no lane ever walks a large box alone and no wave waits for one that does
 //   raster_resolve_kernel  one thread per pixel: the winner's weights again (the same device function, so the same bits) and the outputs
 // The depth test is a 64-bit unsigned atomicMin on (bits(zp) << 32) | face: global_atomic_umin_x2 on gfx950, not a compare-and-swap loop.
-// The arithmetic is the header's specification operation for operation: tests/support/raster_ref.py restates it and the outputs are compared
-// bit for bit, so nothing here may be reassociated, contracted or replaced by a reciprocal.
-#include "common.h"
+// The camera maps, the headlight and the small arithmetic are csrc/shape_common.h's; its rule holds here too: the arithmetic is the header's
+// specification operation for operation (tests/support/raster_ref.py restates it, the outputs are compared bit for bit).
+#include "shape_common.h"
 
 namespace {
 
@@ -78,14 +78,9 @@ __global__ void __launch_bounds__(RASTER_THREADS) raster_vertex_kernel(RasterArg
     if (v >= a.V) return;
     const int32_t n = (int32_t)blockIdx.y;
     const float* __restrict__ m = a.cams + (int64_t)n * 25;
-    const float q0 = a.points[v * 3] - m[3], q1 = a.points[v * 3 + 1] - m[7], q2 = a.points[v * 3 + 2] - m[11];
-    const float c0 = (m[0] * q0 + m[4] * q1) + m[8] * q2;
-    const float c1 = (m[1] * q0 + m[5] * q1) + m[9] * q2;
-    const float c2 = (m[2] * q0 + m[6] * q1) + m[10] * q2;
-    const float fx = m[16], sk = m[17], cx = m[18], fy = m[20], cy = m[21];
-    const float xl = c0 / c2, yl = c1 / c2;
-    const float yc = yl * fy + cy;
-    const float xc = ((xl * fx + cx) - (cy * sk) / fy) + (sk * yc) / fy;
+    float q0, q1, q2, c0, c1, c2, xc, yc;
+    shape::world_to_camera(m, a.points[v * 3], a.points[v * 3 + 1], a.points[v * 3 + 2], q0, q1, q2, c0, c1, c2);
+    shape::camera_to_image(m, c0, c1, c2, xc, yc);
     const float fr = (float)a.res;
     const float px = xc * fr - 0.5f, py = yc * fr - 0.5f;
     RasterVertex o;
@@ -208,15 +203,6 @@ __global__ void __launch_bounds__(RASTER_THREADS) raster_large_kernel(RasterArgs
     }
 }
 
-__device__ __forceinline__ float raster_mix(float b0, float b1, float b2, float a0, float a1, float a2) { return (b0 * a0 + b1 * a1) + b2 * a2; }
-
-__device__ __forceinline__ float raster_clamp(float p, float h) {
-    p = p > 0.0f ? p : 0.0f;                          // NaN -> 0
-    return p < h ? p : h;
-}
-
-__device__ __forceinline__ float raster_lerp(float a, float b, float f) { return a + f * (b - a); }
-
 __global__ void __launch_bounds__(RASTER_THREADS) raster_resolve_kernel(RasterArgs a) {
     if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) {
         if (a.bad_faces) *a.bad_faces = RLOAD(&a.counters[2]);
@@ -254,12 +240,7 @@ __global__ void __launch_bounds__(RASTER_THREADS) raster_resolve_kernel(RasterAr
     const bool need_ray = a.depth != nullptr || (a.image != nullptr && a.mode == EG3D_RASTER_LAMBERT);
     float xl = 0.0f, yl = 0.0f;
     const float* __restrict__ c = a.cams + (int64_t)n * 25;
-    if (need_ray) {
-        const float fx = c[16], sk = c[17], cx = c[18], fy = c[20], cy = c[21];
-        const float xc = ((float)x + 0.5f) / (float)a.res, yc = ((float)y + 0.5f) / (float)a.res;
-        xl = (((xc - cx) + (cy * sk) / fy) - (sk * yc) / fy) / fx;
-        yl = (yc - cy) / fy;
-    }
+    if (need_ray) shape::pixel_to_local(c, x, y, a.res, xl, yl);
     if (a.depth) a.depth[pix] = hit ? zp * sqrtf((xl * xl + yl * yl) + 1.0f) : 0.0f;
     if (!a.image) return;
     float s0 = a.background, s1 = a.background, s2 = a.background;
@@ -267,15 +248,15 @@ __global__ void __launch_bounds__(RASTER_THREADS) raster_resolve_kernel(RasterAr
         const int32_t k0 = a.faces[f * 3], k1 = a.faces[f * 3 + 1], k2 = a.faces[f * 3 + 2];
         if (a.mode == EG3D_RASTER_TEXTURE) {
             const float* __restrict__ A = a.uv + f * 6;
-            const float u = raster_mix(b0, b1, b2, A[0], A[2], A[4]), v = raster_mix(b0, b1, b2, A[1], A[3], A[5]);
-            const float tx = raster_clamp(u * (float)a.Wt - 0.5f, (float)(a.Wt - 1)), ty = raster_clamp(v * (float)a.Ht - 0.5f, (float)(a.Ht - 1));
+            const float u = shape::mix(b0, b1, b2, A[0], A[2], A[4]), v = shape::mix(b0, b1, b2, A[1], A[3], A[5]);
+            const float tx = shape::clamp(u * (float)a.Wt - 0.5f, (float)(a.Wt - 1)), ty = shape::clamp(v * (float)a.Ht - 0.5f, (float)(a.Ht - 1));
             const int32_t ix = min((int32_t)floorf(tx), a.Wt - 2), iy = min((int32_t)floorf(ty), a.Ht - 2);
             const float gx = tx - (float)ix, gy = ty - (float)iy;
             const uint8_t* __restrict__ r0 = a.texture + ((int64_t)iy * a.Wt + ix) * 3;
             const uint8_t* __restrict__ r1 = r0 + (int64_t)a.Wt * 3;
             float col[3];
             for (int j = 0; j < 3; ++j) {
-                col[j] = raster_lerp(raster_lerp((float)r0[j], (float)r0[3 + j], gx), raster_lerp((float)r1[j], (float)r1[3 + j], gx), gy);
+                col[j] = shape::lerp(shape::lerp((float)r0[j], (float)r0[3 + j], gx), shape::lerp((float)r1[j], (float)r1[3 + j], gx), gy);
                 col[j] = (col[j] - 127.5f) / 127.5f;
             }
             s0 = col[0], s1 = col[1], s2 = col[2];
@@ -283,28 +264,21 @@ __global__ void __launch_bounds__(RASTER_THREADS) raster_resolve_kernel(RasterAr
             const float* __restrict__ C0 = a.colors + (int64_t)k0 * 3;
             const float* __restrict__ C1 = a.colors + (int64_t)k1 * 3;
             const float* __restrict__ C2 = a.colors + (int64_t)k2 * 3;
-            s0 = raster_mix(b0, b1, b2, C0[0], C1[0], C2[0]);
-            s1 = raster_mix(b0, b1, b2, C0[1], C1[1], C2[1]);
-            s2 = raster_mix(b0, b1, b2, C0[2], C1[2], C2[2]);
+            s0 = shape::mix(b0, b1, b2, C0[0], C1[0], C2[0]);
+            s1 = shape::mix(b0, b1, b2, C0[1], C1[1], C2[1]);
+            s2 = shape::mix(b0, b1, b2, C0[2], C1[2], C2[2]);
         } else {
             const float* __restrict__ N0 = a.normals + (int64_t)k0 * 3;
             const float* __restrict__ N1 = a.normals + (int64_t)k1 * 3;
             const float* __restrict__ N2 = a.normals + (int64_t)k2 * 3;
             float nn[3];
-            for (int j = 0; j < 3; ++j) nn[j] = raster_mix(b0, b1, b2, N0[j], N1[j], N2[j]);
+            for (int j = 0; j < 3; ++j) nn[j] = shape::mix(b0, b1, b2, N0[j], N1[j], N2[j]);
             const float len = sqrtf((nn[0] * nn[0] + nn[1] * nn[1]) + nn[2] * nn[2]);
             const bool ok = len > 0.0f && len < INFINITY;
             for (int j = 0; j < 3; ++j) nn[j] = ok ? nn[j] / len : 0.0f;
-            float d[3];
-            for (int i = 0; i < 3; ++i) {
-                const float w = ((c[4 * i] * xl + c[4 * i + 1] * yl) + c[4 * i + 2]) + c[4 * i + 3];
-                d[i] = w - c[4 * i + 3];
-            }
-            const float dn = sqrtf((d[0] * d[0] + d[1] * d[1]) + d[2] * d[2]);
-            for (int i = 0; i < 3; ++i) d[i] = d[i] / dn;
-            float l = -((nn[0] * d[0] + nn[1] * d[1]) + nn[2] * d[2]);
-            l = l > 0.0f ? l : 0.0f;
-            const float v = a.ambient + (1.0f - a.ambient) * l;
+            float o[3], d[3];
+            shape::local_to_world_dir(c, xl, yl, o, d);
+            const float v = shape::headlight(a.ambient, nn, d);
             s0 = s1 = s2 = v * 2.0f - 1.0f;
         }
     }
@@ -313,8 +287,6 @@ __global__ void __launch_bounds__(RASTER_THREADS) raster_resolve_kernel(RasterAr
     ip[a.pixels] = s1;
     ip[2 * a.pixels] = s2;
 }
-
-bool raster_finite(float v) { return v == v && v - v == 0.0f; }
 
 int64_t raster_align(int64_t b) { return (b + 15) & ~(int64_t)15; }
 
@@ -325,7 +297,7 @@ struct RasterLayout {
 // validates everything but the workspace; fills the workspace layout
 int raster_check(const eg3d_mesh_raster_params* p, RasterLayout& l) {
     if (p == nullptr || p->V < 0 || p->F < 0 || p->N < 1 || p->res < 1) return EG3D_ERR_INVALID;
-    if (!(p->near > 0.0f) || !raster_finite(p->near) || !(p->ambient >= 0.0f && p->ambient <= 1.0f)) return EG3D_ERR_INVALID;
+    if (!(p->near > 0.0f) || !shape::finite(p->near) || !(p->ambient >= 0.0f && p->ambient <= 1.0f)) return EG3D_ERR_INVALID;
     if (p->cull != 0 && p->cull != 1) return EG3D_ERR_INVALID;
     if (p->mode != EG3D_RASTER_TEXTURE && p->mode != EG3D_RASTER_VERTEX && p->mode != EG3D_RASTER_LAMBERT) return EG3D_ERR_INVALID;
     if (p->cams == nullptr || (p->V > 0 && p->points == nullptr) || (p->F > 0 && p->faces == nullptr)) return EG3D_ERR_INVALID;

@@ -1766,15 +1766,35 @@ def noise_normalize_(bufs):
 _INT32_MAX = 2 ** 31 - 1
 
 
+def _grid3(vol: torch.Tensor, what: str) -> torch.Tensor:
+    """vol checked as a 3-D fp32 grid on the GPU: the contiguous grid."""
+    L.require_cuda(vol)
+    if vol.dim() != 3 or vol.dtype != torch.float32:
+        raise L.Eg3dHipError(f'{what}: a 3-D fp32 grid, got {tuple(vol.shape)} {vol.dtype}')
+    return vol.contiguous()
+
+
+def _cams25(cams: torch.Tensor, what: str, dev) -> torch.Tensor:
+    """cams checked as camera vectors [F >= 1, 25] on a GPU: contiguous fp32 on dev."""
+    L.require_cuda(cams)
+    if cams.dim() != 2 or cams.shape[1] != 25 or cams.shape[0] < 1:
+        raise L.Eg3dHipError(f'{what}: cameras [F >= 1, 25], got {tuple(cams.shape)}')
+    return cams.to(device=dev, dtype=torch.float32).contiguous()
+
+
+def _fill_frame(p, origin, spacing, axes):
+    """The world-to-grid frame of a params struct that has one (IsoParams, MeshNormalsParams)."""
+    p.axes[:] = [int(v) for v in axes]
+    p.origin[:] = [float(v) for v in origin]
+    p.spacing[:] = [float(v) for v in spacing]
+
+
 def marching_cubes(vol: torch.Tensor, level: float, origin=None, spacing=None):
     """(verts fp32 [V,3], faces int32 [F,3]) of the level-`level` surface of the fp32 grid vol [D0,D1,D2] (eg3d_mc_*; include/eg3d_hip.h):
     the frame of skimage's marching_cubes(vol.transpose(2,1,0), level) (grid point (i0,i1,i2) -> (i2,i1,i0)), then * spacing + origin per
     output axis.  Inside = v > level; the faces' right-hand normals point toward lower values.  Finite values assumed.  Workspace from
     the caching allocator; one host synchronise (the totals)."""
-    L.require_cuda(vol)
-    if vol.dim() != 3 or vol.dtype != torch.float32:
-        raise L.Eg3dHipError(f'marching_cubes: a 3-D fp32 grid, got {tuple(vol.shape)} {vol.dtype}')
-    vol = vol.contiguous()
+    vol = _grid3(vol, 'marching_cubes')
     dev = vol.device
     p = L.McParams(vol=vol.data_ptr(), D0=vol.shape[0], D1=vol.shape[1], D2=vol.shape[2], level=float(level))
     p.origin[:] = [float(v) for v in (origin if origin is not None else (0.0, 0.0, 0.0))]
@@ -1801,10 +1821,7 @@ def marching_cubes(vol: torch.Tensor, level: float, origin=None, spacing=None):
 
 
 def _iso_grid_params(vol: torch.Tensor, what: str):
-    L.require_cuda(vol)
-    if vol.dim() != 3 or vol.dtype != torch.float32:
-        raise L.Eg3dHipError(f'{what}: a 3-D fp32 grid, got {tuple(vol.shape)} {vol.dtype}')
-    vol = vol.contiguous()
+    vol = _grid3(vol, what)
     return vol, L.IsoParams(vol=vol.data_ptr(), D0=vol.shape[0], D1=vol.shape[1], D2=vol.shape[2])
 
 
@@ -1848,12 +1865,9 @@ def iso_render(vol: torch.Tensor, cams: torch.Tensor, res: int, level: float, or
     skip=True jumps over bricks whose maximum is <= level; the outputs are bit-identical either way.  One launch (two when it has to build the
     bricks), no host synchronise."""
     vol, p = _iso_grid_params(vol, 'iso_render')
-    L.require_cuda(cams)
-    if cams.dim() != 2 or cams.shape[1] != 25 or cams.shape[0] < 1:
-        raise L.Eg3dHipError(f'iso_render: cameras [F >= 1, 25], got {tuple(cams.shape)}')
+    cams = _cams25(cams, 'iso_render', vol.device)
     if shade not in ISO_SHADE_MODES:
         raise L.Eg3dHipError(f'iso_render: shade {sorted(ISO_SHADE_MODES)}, got {shade!r}')
-    cams = cams.to(device=vol.device, dtype=torch.float32).contiguous()
     dev, F, res = vol.device, cams.shape[0], int(res)
     if skip:
         if bricks is None:
@@ -1871,9 +1885,7 @@ def iso_render(vol: torch.Tensor, cams: torch.Tensor, res: int, level: float, or
     p.cams, p.bricks = cams.data_ptr(), (bricks.data_ptr() if skip else None)
     p.depth, p.normal, p.mask, p.shade = out['depth'].data_ptr(), out['normal'].data_ptr(), out['mask'].data_ptr(), out['shade'].data_ptr()
     p.F, p.res = F, res
-    p.axes[:] = [int(v) for v in axes]
-    p.origin[:] = [float(v) for v in origin]
-    p.spacing[:] = [float(v) for v in spacing]
+    _fill_frame(p, origin, spacing, axes)
     p.level, p.step, p.refine, p.skip = float(level), float(step), int(refine), int(bool(skip))
     p.shade_mode, p.ambient, p.background = ISO_SHADE_MODES[shade], float(ambient), float(background)
     L.check(L.lib().eg3d_iso_render(C.byref(p), L.stream_ptr()), 'iso_render')
@@ -1895,26 +1907,20 @@ def mesh_normals(vol: torch.Tensor, points: torch.Tensor, origin, spacing, axes=
     the dense region): clamped +-1 voxel differences of iso_render's field, its 'normal at the hit' at arbitrary points (eg3d_mesh_normals;
     include/eg3d_hip.h "Mesh attributes").  The frame (origin, spacing, axes) is iso_render's.  0 where the gradient vanishes or is not finite
     and for a NaN point.  One launch, no host synchronise."""
-    L.require_cuda(vol)
-    if vol.dim() != 3 or vol.dtype != torch.float32:
-        raise L.Eg3dHipError(f'mesh_normals: a 3-D fp32 grid, got {tuple(vol.shape)} {vol.dtype}')
-    vol = vol.contiguous()
+    vol = _grid3(vol, 'mesh_normals')
     points = _mesh_rows(points, 'mesh_normals: points', vol.device)
     out = torch.empty_like(points)
     p = L.MeshNormalsParams(vol=vol.data_ptr(), points=points.data_ptr(), normals=out.data_ptr(), V=points.shape[0], D0=vol.shape[0], D1=vol.shape[1],
                             D2=vol.shape[2])
-    p.axes[:] = [int(v) for v in axes]
-    p.origin[:] = [float(v) for v in origin]
-    p.spacing[:] = [float(v) for v in spacing]
+    _fill_frame(p, origin, spacing, axes)
     L.check(L.lib().eg3d_mesh_normals(C.byref(p), L.stream_ptr()), 'mesh_normals')
     return out
 
 
 def _bake_views(what: str, images, depth, mask, cams, dev):
     """The views of mesh_bake / mesh_texture checked: (F, cams as contiguous fp32)."""
-    L.require_cuda(images, depth, mask, cams)
-    if cams.dim() != 2 or cams.shape[1] != 25 or cams.shape[0] < 1:
-        raise L.Eg3dHipError(f'{what}: cameras [F >= 1, 25], got {tuple(cams.shape)}')
+    L.require_cuda(images, depth, mask)
+    cams = _cams25(cams, what, dev)
     F = cams.shape[0]
     if images.dim() != 4 or images.shape[0] != F or images.shape[1] != 3 or images.shape[2] != images.shape[3] or images.shape[2] < 1 \
             or images.dtype != torch.float32 or not images.is_contiguous():
@@ -1924,10 +1930,10 @@ def _bake_views(what: str, images, depth, mask, cams, dev):
         raise L.Eg3dHipError(f'{what}: depth must be contiguous fp32 [{F}, R, R], got {tuple(depth.shape)} {depth.dtype}')
     if tuple(mask.shape) != tuple(depth.shape) or mask.dtype != torch.uint8 or not mask.is_contiguous():
         raise L.Eg3dHipError(f'{what}: mask must be contiguous uint8 {tuple(depth.shape)}, got {tuple(mask.shape)} {mask.dtype}')
-    for name, t in (('images', images), ('depth', depth), ('mask', mask), ('cams', cams)):
+    for name, t in (('images', images), ('depth', depth), ('mask', mask)):
         if t.device != dev:
             raise L.Eg3dHipError(f'{what}: {name} is on {t.device}, expected {dev}')
-    return F, cams.to(dtype=torch.float32).contiguous()
+    return F, cams
 
 
 def mesh_bake(points: torch.Tensor, normals: torch.Tensor, images: torch.Tensor, depth: torch.Tensor, mask: torch.Tensor, cams: torch.Tensor,
@@ -2028,10 +2034,7 @@ def mesh_raster(points: torch.Tensor, faces: torch.Tensor, cams: torch.Tensor, r
     dev, V = points.device, points.shape[0]
     faces = _mesh_faces(faces, 'mesh_raster: faces', dev)
     F, res = faces.shape[0], int(res)
-    L.require_cuda(cams)
-    if cams.dim() != 2 or cams.shape[1] != 25 or cams.shape[0] < 1 or cams.device != dev:
-        raise L.Eg3dHipError(f'mesh_raster: cameras [N >= 1, 25] on {dev}, got {tuple(cams.shape)} on {cams.device}')
-    cams = cams.to(dtype=torch.float32).contiguous()
+    cams = _cams25(cams, 'mesh_raster', dev)
     N = cams.shape[0]
     if mode not in RASTER_MODES or cull not in RASTER_CULL:
         raise L.Eg3dHipError(f'mesh_raster: mode {sorted(RASTER_MODES)} and cull {sorted(RASTER_CULL)}, got {mode!r}, {cull!r}')
@@ -2078,13 +2081,6 @@ def mesh_raster(points: torch.Tensor, faces: torch.Tensor, cams: torch.Tensor, r
     return out
 
 
-def _cc_grid(vol: torch.Tensor, what: str) -> torch.Tensor:
-    L.require_cuda(vol)
-    if vol.dim() != 3 or vol.dtype != torch.float32:
-        raise L.Eg3dHipError(f'{what}: a 3-D fp32 grid, got {tuple(vol.shape)} {vol.dtype}')
-    return vol.contiguous()
-
-
 def grid_components(vol: torch.Tensor, level: float, connectivity: int = 6) -> dict:
     """Connected components of {vol > level} of the fp32 grid vol [D0,D1,D2] (eg3d_cc_*; include/eg3d_hip.h "Grid components").  Inside =
     v > level as in marching_cubes and iso_render (NaN and v == level are outside); connectivity 6 joins face neighbours, 26 also edge and
@@ -2094,7 +2090,7 @@ def grid_components(vol: torch.Tensor, level: float, connectivity: int = 6) -> d
       count  K;   inside        voxels above the level (Python ints)
     The result is a function of the input alone (bit-identical between runs and builds).  Workspace (4 bytes per voxel) from the caching
     allocator; one host synchronise (the totals)."""
-    vol = _cc_grid(vol, 'grid_components')
+    vol = _grid3(vol, 'grid_components')
     if connectivity not in (6, 26):
         raise L.Eg3dHipError(f'grid_components: connectivity 6 or 26, got {connectivity!r}')
     dev = vol.device
@@ -2120,7 +2116,7 @@ def grid_keep(vol: torch.Tensor, labels: torch.Tensor, keep_mask: torch.Tensor, 
     """A copy of the fp32 grid vol in which every voxel of a component the mask drops holds `fill`: out = keep[labels] ? vol : fill with
     keep = (True, *keep_mask) -- keep_mask [K] is indexed by label - 1 (select_components' result), and label 0, the outside, stays as it
     was (NaN included).  labels as grid_components returns them.  One streaming launch (eg3d_cc_keep), no host synchronise."""
-    vol = _cc_grid(vol, 'grid_keep')
+    vol = _grid3(vol, 'grid_keep')
     L.require_cuda(labels)
     if labels.shape != vol.shape or labels.dtype != torch.int32 or not labels.is_contiguous() or labels.device != vol.device:
         raise L.Eg3dHipError(f'grid_keep: labels must be contiguous int32 {tuple(vol.shape)} on {vol.device}, got {tuple(labels.shape)} {labels.dtype}')

@@ -1,5 +1,7 @@
 // Baseline JPEG decoder (target-image ingestion: the photographs arrive as JPEGs; include/eg3d_hip.h "Baseline JPEG decoder").  One image per
-// call, integers only, the output bytes are those of libjpeg(-turbo)'s default decode (ISLOW IDCT, fancy upsampling).
+// call, or N images of any geometry per call (eg3d_jpegdec_batch_*: the same kernels, each launched once, the image in blockIdx.y -- .z for
+// the colour pass -- and its record read from device memory); integers only, the output bytes are those of libjpeg(-turbo)'s default decode
+// (ISLOW IDCT, fancy upsampling).
 //
 //   jd_marker_count / _scan / _apply   the raw entropy-coded segment: every FF xx classified (FF 00 stuffing, FF D0..D7 restart, else status), a
 //                                      scan of the kept bytes and of the restart markers, the compaction -> the unstuffed stream and the start
@@ -20,6 +22,8 @@
 // The per-item arithmetic is csrc/jpeg_decode_core.h.  Every store of the entropy passes is guarded by the geometry and every read beyond a
 // segment's end yields zero bits: a malformed stream ends in a status, not in an access out of range.  The only atomics are integer ORs into
 // the status word (order-independent).
+#include <algorithm>
+
 #include "common.h"
 #include "jpeg_decode_core.h"
 
@@ -36,10 +40,35 @@ constexpr int JD_QUANT_BYTES = 256, JD_HUFF_BYTES = 16 + 256;     // the tables 
 // result words
 constexpr int JD_STATUS = 0, JD_ROUNDS_IN = 1, JD_ROUNDS_X = 2, JD_L = 3, JD_TOTAL = 4, JD_NRST = 5;
 
-struct JdLayout {                                   // byte offsets into the workspace
-    int64_t sums, offs, stream, seg_start, lane_base, exit, entry, acc, pre, rounds, coef, planes, total;
-    int64_t plane[3];                               // offsets of the component planes from `planes`
-    int32_t pw[3], ph[3];                           // padded plane sizes
+// the workspace ranges of one image, in the order they lie in (each a multiple of JD_ALIGN bytes)
+enum { F_SUMS, F_OFFS, F_STREAM, F_SEG_START, F_LANE_BASE, F_EXIT, F_ENTRY, F_ACC, F_PRE, F_ROUNDS, F_COEF, F_PLANE0, F_PLANE1, F_PLANE2, JD_FIELDS };
+
+struct JdImage {                                    // everything the kernels know about one image: the geometry and where its data lies
+    JdGeom g;
+    const uint8_t* raw;                             // the entropy-coded segment as in the file
+    const uint8_t* blob;                            // the tables
+    uint8_t* out;
+    int32_t* result;
+    int2 *sums, *offs;
+    uint8_t* stream;
+    int32_t *seg_start, *lane_base;
+    unsigned long long *exit_state, *entry_state;
+    int4 *acc, *pre;
+    int32_t* rounds;
+    int16_t* coef;
+    uint8_t* plane[3];
+    int32_t pw[3], reserved;                        // padded plane widths
+};
+
+// where a workgroup finds its image: the one-image call passes the record as a kernel argument, the batch call an array in device memory
+// (uniform per workgroup: scalar loads)
+struct JdOne {
+    JdImage im;
+    __device__ __forceinline__ const JdImage& at(unsigned) const { return im; }
+};
+struct JdMany {
+    const JdImage* ims;
+    __device__ __forceinline__ const JdImage& at(unsigned i) const { return ims[i]; }
 };
 
 struct JdLane {
@@ -87,8 +116,15 @@ __device__ __forceinline__ int jd_classify(const JdBytes& r, int64_t n, int q) {
     return 4;
 }
 
-__global__ void __launch_bounds__(256) jd_marker_count_kernel(const uint8_t* __restrict__ raw, JdGeom g, int2* __restrict__ sums, int32_t* __restrict__ result) {
+template <class Src>
+__global__ void __launch_bounds__(256) jd_marker_count_kernel(Src src) {
     __shared__ int s_k[256], s_r[256];
+    const JdImage& im = src.at(blockIdx.y);
+    const JdGeom g = im.g;
+    if ((int)blockIdx.x >= g.nchunks) return;                                      // (the whole workgroup: a batch's grid is its largest image's)
+    const uint8_t* __restrict__ raw = im.raw;
+    int2* __restrict__ sums = im.sums;
+    int32_t* __restrict__ result = im.result;
     const int t = threadIdx.x;
     const JdBytes r = jd_load16(raw, g.n, (int64_t)blockIdx.x * JD_CHUNK + t * 16);
     int keep = 0, rst = 0, err = 0;
@@ -143,9 +179,15 @@ __device__ __forceinline__ int4 jd_scan_one(int64_t M, Load ld, Store st, int4 (
     return total;
 }
 
-__global__ void __launch_bounds__(JD_ONE) jd_marker_scan_kernel(const int2* __restrict__ sums, JdGeom g, int2* __restrict__ offs, int32_t* __restrict__ seg_start,
-                                                                int32_t* __restrict__ result) {
+template <class Src>
+__global__ void __launch_bounds__(JD_ONE) jd_marker_scan_kernel(Src src) {
     __shared__ int4 sh[2][JD_ONE];
+    const JdImage& im = src.at(blockIdx.y);
+    const JdGeom g = im.g;
+    const int2* __restrict__ sums = im.sums;
+    int2* __restrict__ offs = im.offs;
+    int32_t* __restrict__ seg_start = im.seg_start;
+    int32_t* __restrict__ result = im.result;
     const int4 total = jd_scan_one(
         g.nchunks, [&](int64_t j) { const int2 v = sums[j]; return make_int4(v.x, v.y, 0, 0); },
         [&](int64_t j, int4 p) { offs[j] = make_int2(p.x, p.y); }, sh);
@@ -157,9 +199,17 @@ __global__ void __launch_bounds__(JD_ONE) jd_marker_scan_kernel(const int2* __re
     }
 }
 
-__global__ void __launch_bounds__(256) jd_marker_apply_kernel(const uint8_t* __restrict__ raw, JdGeom g, const int2* __restrict__ offs, uint8_t* __restrict__ stream,
-                                                              int32_t* __restrict__ seg_start, int32_t* __restrict__ result) {
+template <class Src>
+__global__ void __launch_bounds__(256) jd_marker_apply_kernel(Src src) {
     __shared__ int s_k[2][256], s_r[2][256];
+    const JdImage& im = src.at(blockIdx.y);
+    const JdGeom g = im.g;
+    if ((int)blockIdx.x >= g.nchunks) return;                                      // (the whole workgroup)
+    const uint8_t* __restrict__ raw = im.raw;
+    const int2* __restrict__ offs = im.offs;
+    uint8_t* __restrict__ stream = im.stream;
+    int32_t* __restrict__ seg_start = im.seg_start;
+    int32_t* __restrict__ result = im.result;
     const int t = threadIdx.x;
     const JdBytes r = jd_load16(raw, g.n, (int64_t)blockIdx.x * JD_CHUNK + t * 16);
     int flags[16], keep = 0, rst = 0;
@@ -194,8 +244,14 @@ __global__ void __launch_bounds__(256) jd_marker_apply_kernel(const uint8_t* __r
     if (err) atomicOr(&result[JD_STATUS], JD_ERR_SEGMENTS);
 }
 
-__global__ void __launch_bounds__(JD_ONE) jd_segments_kernel(JdGeom g, const int32_t* __restrict__ seg_start, int32_t* __restrict__ lane_base, int32_t* __restrict__ result) {
+template <class Src>
+__global__ void __launch_bounds__(JD_ONE) jd_segments_kernel(Src src) {
     __shared__ int4 sh[2][JD_ONE];
+    const JdImage& im = src.at(blockIdx.y);
+    const JdGeom g = im.g;
+    const int32_t* __restrict__ seg_start = im.seg_start;
+    int32_t* __restrict__ lane_base = im.lane_base;
+    int32_t* __restrict__ result = im.result;
     const bool ok = result[JD_STATUS] == 0 && result[JD_NRST] + 1 == g.nseg;       // (written by earlier launches)
     __syncthreads();
     if (!ok) {
@@ -259,13 +315,22 @@ __device__ __forceinline__ JdLane jd_lane(int i, const JdGeom& g, const int32_t*
     return l;
 }
 
-__global__ void __launch_bounds__(JD_LANES) jd_sync_kernel(const uint8_t* __restrict__ blob, const uint32_t* __restrict__ words, JdGeom g,
-                                                           const int32_t* __restrict__ lane_base, const int32_t* __restrict__ seg_start,
-                                                           unsigned long long* __restrict__ exit_state, unsigned long long* __restrict__ entry_state,
-                                                           int4* __restrict__ acc_out, int32_t* __restrict__ rounds_wg, const int32_t* __restrict__ result) {
+template <class Src>
+__global__ void __launch_bounds__(JD_LANES) jd_sync_kernel(Src src) {
     __shared__ JdHuff tabs[4];
     __shared__ unsigned long long s_exit[JD_LANES];
     __shared__ int s_flag;
+    const JdImage& im = src.at(blockIdx.y);
+    const JdGeom g = im.g;
+    const uint8_t* __restrict__ blob = im.blob;
+    const uint32_t* __restrict__ words = reinterpret_cast<const uint32_t*>(im.stream);
+    const int32_t* __restrict__ lane_base = im.lane_base;
+    const int32_t* __restrict__ seg_start = im.seg_start;
+    unsigned long long* __restrict__ exit_state = im.exit_state;
+    unsigned long long* __restrict__ entry_state = im.entry_state;
+    int4* __restrict__ acc_out = im.acc;
+    int32_t* __restrict__ rounds_wg = im.rounds;
+    const int32_t* __restrict__ result = im.result;
     const int t = threadIdx.x, L = result[JD_L];
     const int i = blockIdx.x * JD_LANES + t;
     if (blockIdx.x * JD_LANES >= L) return;                                        // (the whole workgroup)
@@ -313,15 +378,24 @@ __global__ void __launch_bounds__(JD_LANES) jd_sync_kernel(const uint8_t* __rest
     if (t == 0) rounds_wg[blockIdx.x] = rounds;
 }
 
-__global__ void __launch_bounds__(JD_ONE) jd_stitch_kernel(const uint8_t* __restrict__ blob, const uint32_t* __restrict__ words, JdGeom g,
-                                                           const int32_t* __restrict__ lane_base, const int32_t* __restrict__ seg_start,
-                                                           unsigned long long* __restrict__ exit_state, unsigned long long* __restrict__ entry_state,
-                                                           int4* __restrict__ acc_io, int4* __restrict__ pre, const int32_t* __restrict__ rounds_wg,
-                                                           int32_t* __restrict__ result) {
+template <class Src>
+__global__ void __launch_bounds__(JD_ONE) jd_stitch_kernel(Src src) {
     __shared__ JdHuff tabs[4];
     __shared__ int4 sh[2][JD_ONE];
     __shared__ int s_max[JD_ONE];
     __shared__ int s_flag;
+    const JdImage& im = src.at(blockIdx.y);
+    const JdGeom g = im.g;
+    const uint8_t* __restrict__ blob = im.blob;
+    const uint32_t* __restrict__ words = reinterpret_cast<const uint32_t*>(im.stream);
+    const int32_t* __restrict__ lane_base = im.lane_base;
+    const int32_t* __restrict__ seg_start = im.seg_start;
+    unsigned long long* __restrict__ exit_state = im.exit_state;
+    unsigned long long* __restrict__ entry_state = im.entry_state;
+    int4* __restrict__ acc_io = im.acc;
+    int4* __restrict__ pre = im.pre;
+    const int32_t* __restrict__ rounds_wg = im.rounds;
+    int32_t* __restrict__ result = im.result;
     const int t = threadIdx.x, L = result[JD_L];
     if (L <= 0) return;
     jd_load_tables(blob, tabs, JD_ONE);
@@ -400,12 +474,20 @@ __global__ void __launch_bounds__(JD_ONE) jd_stitch_kernel(const uint8_t* __rest
     if (err) atomicOr(&result[JD_STATUS], JD_ERR_BLOCKS);
 }
 
-__global__ void __launch_bounds__(JD_LANES) jd_write_kernel(const uint8_t* __restrict__ blob, const uint32_t* __restrict__ words, JdGeom g,
-                                                            const int32_t* __restrict__ lane_base, const int32_t* __restrict__ seg_start,
-                                                            const unsigned long long* __restrict__ exit_state, const int4* __restrict__ pre,
-                                                            int16_t* __restrict__ coef, int32_t* __restrict__ result) {
+template <class Src>
+__global__ void __launch_bounds__(JD_LANES) jd_write_kernel(Src src) {
     __shared__ JdHuff tabs[4];
     __shared__ uint8_t s_nat[64];
+    const JdImage& im = src.at(blockIdx.y);
+    const JdGeom g = im.g;
+    const uint8_t* __restrict__ blob = im.blob;
+    const uint32_t* __restrict__ words = reinterpret_cast<const uint32_t*>(im.stream);
+    const int32_t* __restrict__ lane_base = im.lane_base;
+    const int32_t* __restrict__ seg_start = im.seg_start;
+    const unsigned long long* __restrict__ exit_state = im.exit_state;
+    const int4* __restrict__ pre = im.pre;
+    int16_t* __restrict__ coef = im.coef;
+    int32_t* __restrict__ result = im.result;
     const int t = threadIdx.x, L = result[JD_L];
     if (blockIdx.x * JD_LANES >= L || result[JD_STATUS] != 0) return;             // (the whole workgroup: both were written by earlier launches)
     if (t < 64) s_nat[jpeg_zz_of_nat[t]] = (uint8_t)t;
@@ -422,14 +504,19 @@ __global__ void __launch_bounds__(JD_LANES) jd_write_kernel(const uint8_t* __res
 }
 
 // 32 blocks per workgroup; thread = (block, column) in the column pass, (block, row) in the row pass.  LDS rows are 9 words apart: no bank conflicts
-__global__ void __launch_bounds__(256) jd_idct_kernel(const int16_t* __restrict__ coef, const uint8_t* __restrict__ blob, JdGeom g, JdLayout lay,
-                                                      uint8_t* __restrict__ planes) {
+template <class Src>
+__global__ void __launch_bounds__(256) jd_idct_kernel(Src src) {
     __shared__ int32_t s_v[32 * 72];
     __shared__ int32_t s_q[3 * 64];
-    const int t = threadIdx.x;
-    if (t < g.ncomp * 64) s_q[t] = blob[g.tq[t >> 6] * 64 + (t & 63)];
-    __syncthreads();
+    const JdImage& im = src.at(blockIdx.y);
+    const JdGeom g = im.g;
     const int64_t blk0 = (int64_t)blockIdx.x * 32;
+    if (blk0 >= g.nblk) return;                                                    // (the whole workgroup)
+    const int16_t* __restrict__ coef = im.coef;
+    const uint8_t* __restrict__ blob = im.blob;
+    const int t = threadIdx.x;
+    if (t < g.ncomp * 64) s_q[t] = blob[(t < 64 ? g.tq[0] : (t < 128 ? g.tq[1] : g.tq[2])) * 64 + (t & 63)];   // (constant indices: the record stays in registers)
+    __syncthreads();
     for (int e = t; e < 32 * 64; e += 256) {                                       // coalesced: 2048 consecutive coefficients
         const int64_t blk = blk0 + (e >> 6);
         int v = 0;
@@ -459,20 +546,26 @@ __global__ void __launch_bounds__(256) jd_idct_kernel(const int16_t* __restrict_
         lo |= (uint32_t)jd_range_limit(x[c]) << (8 * c);
         hi |= (uint32_t)jd_range_limit(x[c + 4]) << (8 * c);
     }
-    *reinterpret_cast<uint2*>(planes + lay.plane[comp] + (int64_t)y0 * lay.pw[comp] + x0) = make_uint2(lo, hi);   // 8-byte aligned: pw, x0 multiples of 8
+    uint8_t* plane = comp == 0 ? im.plane[0] : (comp == 1 ? im.plane[1] : im.plane[2]);
+    const int pw = comp == 0 ? im.pw[0] : (comp == 1 ? im.pw[1] : im.pw[2]);
+    *reinterpret_cast<uint2*>(plane + (int64_t)y0 * pw + x0) = make_uint2(lo, hi);   // 8-byte aligned: the plane, pw and x0 are multiples of 8
 }
 
-__global__ void __launch_bounds__(256) jd_colour_kernel(const uint8_t* __restrict__ planes, JdGeom g, JdLayout lay, uint8_t* __restrict__ out) {
+template <class Src>
+__global__ void __launch_bounds__(256) jd_colour_kernel(Src src) {
+    const JdImage& im = src.at(blockIdx.z);
+    const JdGeom g = im.g;
     const int x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6);
     if (x >= g.W || y >= g.H) return;
-    const int yy = planes[lay.plane[0] + (int64_t)y * lay.pw[0] + x];
+    uint8_t* __restrict__ out = im.out;
+    const int yy = im.plane[0][(int64_t)y * im.pw[0] + x];
     uint8_t rgb[3];
     if (g.ncomp == 1) {
         rgb[0] = rgb[1] = rgb[2] = (uint8_t)yy;
     } else {
         const int dw = (g.W + g.hs - 1) / g.hs, dh = (g.H + g.vs - 1) / g.vs;      // the chroma's real size
-        const int cb = jd_chroma(planes + lay.plane[1], lay.pw[1], dw, dh, g.hs, g.vs, y, x);
-        const int cr = jd_chroma(planes + lay.plane[2], lay.pw[2], dw, dh, g.hs, g.vs, y, x);
+        const int cb = jd_chroma(im.plane[1], im.pw[1], dw, dh, g.hs, g.vs, y, x);
+        const int cr = jd_chroma(im.plane[2], im.pw[2], dw, dh, g.hs, g.vs, y, x);
         jd_ycc_to_rgb(yy, cb, cr, rgb);
     }
     uint8_t* o = out + ((int64_t)y * g.W + x) * 3;
@@ -481,64 +574,224 @@ __global__ void __launch_bounds__(256) jd_colour_kernel(const uint8_t* __restric
 
 int64_t jd_align(int64_t b) { return (b + JD_ALIGN - 1) / JD_ALIGN * JD_ALIGN; }
 
-int jd_geom(const eg3d_jpegdec_params* p, JdGeom& g, JdLayout& l) {
-    if (p == nullptr) return EG3D_ERR_INVALID;
-    if (p->H < 1 || p->W < 1 || p->H > 65535 || p->W > 65535 || (p->ncomp != 1 && p->ncomp != 3) || p->data_bytes < 0 || p->restart_interval < 0 ||
-        p->restart_interval > 65535)
+// one image as either entry describes it
+struct JdDesc {
+    int32_t H, W, ncomp, hsamp, vsamp, restart_interval;
+    const int32_t *tq, *td, *ta;
+    int64_t data_bytes;
+};
+
+int jd_call_args(int B, int stages) { return (B < 16 || B > 1024 || (B & (B - 1)) || stages < 0 || stages > 31) ? EG3D_ERR_INVALID : EG3D_OK; }
+
+// the geometry of one image, the bytes of each of its workspace ranges and its padded plane widths
+int jd_geom(const JdDesc& p, int B, JdGeom& g, int64_t* size, int32_t* pw) {
+    if (p.H < 1 || p.W < 1 || p.H > 65535 || p.W > 65535 || (p.ncomp != 1 && p.ncomp != 3) || p.data_bytes < 0 || p.restart_interval < 0 ||
+        p.restart_interval > 65535)
         return EG3D_ERR_INVALID;
-    const int B = p->subseq_bytes;
-    if (B < 16 || B > 1024 || (B & (B - 1)) || p->stages < 0 || p->stages > 31) return EG3D_ERR_INVALID;
-    g.ncomp = p->ncomp;
-    g.hs = p->ncomp == 3 ? p->hsamp : 1;
-    g.vs = p->ncomp == 3 ? p->vsamp : 1;
+    g.ncomp = p.ncomp;
+    g.hs = p.ncomp == 3 ? p.hsamp : 1;
+    g.vs = p.ncomp == 3 ? p.vsamp : 1;
     if (!((g.hs == 1 && g.vs == 1) || (g.hs == 2 && g.vs == 1) || (g.hs == 2 && g.vs == 2))) return EG3D_ERR_UNSUPPORTED;
     g.dc_sel = g.ac_sel = 0;
     for (int c = 0; c < 3; ++c) {
         g.tq[c] = 0;
-        if (c >= p->ncomp) continue;
-        if (p->tq[c] < 0 || p->tq[c] > 3 || p->td[c] < 0 || p->td[c] > 1 || p->ta[c] < 0 || p->ta[c] > 1) return EG3D_ERR_INVALID;
-        g.tq[c] = p->tq[c];
-        g.dc_sel |= p->td[c] << c;
-        g.ac_sel |= p->ta[c] << c;
+        if (c >= p.ncomp) continue;
+        if (p.tq[c] < 0 || p.tq[c] > 3 || p.td[c] < 0 || p.td[c] > 1 || p.ta[c] < 0 || p.ta[c] > 1) return EG3D_ERR_INVALID;
+        g.tq[c] = p.tq[c];
+        g.dc_sel |= p.td[c] << c;
+        g.ac_sel |= p.ta[c] << c;
     }
-    if (p->data_bytes >= (1ll << 28)) return EG3D_ERR_TOO_LARGE;                    // bit positions are 32-bit
-    g.H = p->H; g.W = p->W; g.B = B; g.n = p->data_bytes;
-    g.mx = (p->W + 8 * g.hs - 1) / (8 * g.hs);
-    g.my = (p->H + 8 * g.vs - 1) / (8 * g.vs);
+    if (p.data_bytes >= (1ll << 28)) return EG3D_ERR_TOO_LARGE;                     // bit positions are 32-bit
+    g.H = p.H; g.W = p.W; g.B = B; g.n = p.data_bytes;
+    g.mx = (p.W + 8 * g.hs - 1) / (8 * g.hs);
+    g.my = (p.H + 8 * g.vs - 1) / (8 * g.vs);
     const int64_t mcus = (int64_t)g.mx * g.my;
-    g.bpm = p->ncomp == 1 ? 1 : g.hs * g.vs + 2;
+    g.bpm = p.ncomp == 1 ? 1 : g.hs * g.vs + 2;
     if (mcus * g.bpm * 64 > INT32_MAX) return EG3D_ERR_TOO_LARGE;
     g.mcus = (int32_t)mcus;
     g.nblk = (int32_t)(mcus * g.bpm);
-    g.R = p->restart_interval > 0 ? (int32_t)(p->restart_interval < mcus ? p->restart_interval : mcus) : (int32_t)mcus;
+    g.R = p.restart_interval > 0 ? (int32_t)(p.restart_interval < mcus ? p.restart_interval : mcus) : (int32_t)mcus;
     g.nseg = (int32_t)((mcus + g.R - 1) / g.R);
     g.Lmax = (int32_t)(g.n / B) + g.nseg + 1;                                      // sum over the segments of max(1, ceil(len / B)) <= n / B + nseg
     g.nchunks = (int32_t)((g.n + JD_CHUNK - 1) / JD_CHUNK);
-    if ((g.Lmax + JD_LANES - 1) / JD_LANES > 65536) return EG3D_ERR_TOO_LARGE;
-    int64_t o = 0;
-    auto take = [&](int64_t bytes) { const int64_t at = o; o += jd_align(bytes); return at; };
     const int nwg = (g.Lmax + JD_LANES - 1) / JD_LANES;
-    l.sums = take((int64_t)(g.nchunks + 1) * 8);
-    l.offs = take((int64_t)(g.nchunks + 1) * 8);
-    l.stream = take(g.n + 16);                                                     // the decode reads whole dwords, one beyond the last bit's
-    l.seg_start = take((int64_t)(g.nseg + 1) * 4);
-    l.lane_base = take((int64_t)(g.nseg + 1) * 4);
-    l.exit = take((int64_t)g.Lmax * 8);
-    l.entry = take((int64_t)g.Lmax * 8);
-    l.acc = take((int64_t)g.Lmax * 16);
-    l.pre = take((int64_t)g.Lmax * 16);
-    l.rounds = take((int64_t)nwg * 4);
-    l.coef = take((int64_t)g.nblk * 64 * 2);
-    l.planes = o;
-    int64_t po = 0;
+    if (nwg > 65536) return EG3D_ERR_TOO_LARGE;
+    size[F_SUMS] = jd_align((int64_t)(g.nchunks + 1) * 8);
+    size[F_OFFS] = jd_align((int64_t)(g.nchunks + 1) * 8);
+    size[F_STREAM] = jd_align(g.n + 16);                                           // the decode reads whole dwords, one beyond the last bit's
+    size[F_SEG_START] = jd_align((int64_t)(g.nseg + 1) * 4);
+    size[F_LANE_BASE] = jd_align((int64_t)(g.nseg + 1) * 4);
+    size[F_EXIT] = jd_align((int64_t)g.Lmax * 8);
+    size[F_ENTRY] = jd_align((int64_t)g.Lmax * 8);
+    size[F_ACC] = jd_align((int64_t)g.Lmax * 16);
+    size[F_PRE] = jd_align((int64_t)g.Lmax * 16);
+    size[F_ROUNDS] = jd_align((int64_t)nwg * 4);
+    size[F_COEF] = jd_align((int64_t)g.nblk * 64 * 2);
     for (int c = 0; c < 3; ++c) {
-        l.pw[c] = g.mx * 8 * (c == 0 ? g.hs : 1);
-        l.ph[c] = g.my * 8 * (c == 0 ? g.vs : 1);
-        l.plane[c] = po;
-        if (c < g.ncomp) po += jd_align((int64_t)l.pw[c] * l.ph[c]);
+        pw[c] = g.mx * 8 * (c == 0 ? g.hs : 1);
+        size[F_PLANE0 + c] = c < g.ncomp ? jd_align((int64_t)pw[c] * (g.my * 8 * (c == 0 ? g.vs : 1))) : 0;
     }
-    o += po;
-    l.total = o;
+    return EG3D_OK;
+}
+
+void jd_bind(JdImage& im, char* ws, const int64_t* off, const int32_t* pw) {
+    im.sums = reinterpret_cast<int2*>(ws + off[F_SUMS]);
+    im.offs = reinterpret_cast<int2*>(ws + off[F_OFFS]);
+    im.stream = reinterpret_cast<uint8_t*>(ws + off[F_STREAM]);
+    im.seg_start = reinterpret_cast<int32_t*>(ws + off[F_SEG_START]);
+    im.lane_base = reinterpret_cast<int32_t*>(ws + off[F_LANE_BASE]);
+    im.exit_state = reinterpret_cast<unsigned long long*>(ws + off[F_EXIT]);
+    im.entry_state = reinterpret_cast<unsigned long long*>(ws + off[F_ENTRY]);
+    im.acc = reinterpret_cast<int4*>(ws + off[F_ACC]);
+    im.pre = reinterpret_cast<int4*>(ws + off[F_PRE]);
+    im.rounds = reinterpret_cast<int32_t*>(ws + off[F_ROUNDS]);
+    im.coef = reinterpret_cast<int16_t*>(ws + off[F_COEF]);
+    for (int c = 0; c < 3; ++c) {
+        im.plane[c] = reinterpret_cast<uint8_t*>(ws + off[F_PLANE0 + c]);
+        im.pw[c] = pw[c];
+    }
+    im.reserved = 0;
+}
+
+// what a call launches, over all of its images
+struct JdGrid {
+    int n;                                           // images
+    int nchunks, nwg, nblk, tx, ty;                  // the largest image's workgroups per pass
+    char* ws;
+    int64_t zero_segs, zero_segs_words, zero_coef, zero_coef_words;      // the ranges a call zeroes: segment starts + lane bases, coefficients
+    int32_t* result;
+};
+
+void jd_grid_add(JdGrid& k, const JdGeom& g) {
+    k.nchunks = std::max(k.nchunks, g.nchunks);
+    k.nwg = std::max(k.nwg, (g.Lmax + JD_LANES - 1) / JD_LANES);
+    k.nblk = std::max(k.nblk, (g.nblk + 31) / 32);
+    k.tx = std::max(k.tx, (g.W + 63) / 64);
+    k.ty = std::max(k.ty, (g.H + 3) / 4);
+}
+
+// the launches of both entries: every pass once, whatever the number of images
+template <class Src>
+int jd_run(const Src& src, const JdGrid& k, int stages, hipStream_t st) {
+    const unsigned n = (unsigned)k.n;
+    if (stages == 0) stages = 31;
+    if (stages & EG3D_JPEGDEC_STAGE_MARKERS) {
+        eg3d_zero_words(k.result, (int64_t)k.n * EG3D_JPEGDEC_RESULT_WORDS, st);
+        eg3d_zero_words(k.ws + k.zero_segs, k.zero_segs_words, st);
+        EG3D_LAUNCH_CHECK();
+        if (k.nchunks > 0) {
+            hipLaunchKernelGGL(jd_marker_count_kernel<Src>, dim3((unsigned)k.nchunks, n), dim3(256), 0, st, src);
+            EG3D_LAUNCH_CHECK();
+        }
+        hipLaunchKernelGGL(jd_marker_scan_kernel<Src>, dim3(1, n), dim3(JD_ONE), 0, st, src);
+        EG3D_LAUNCH_CHECK();
+        if (k.nchunks > 0) {
+            hipLaunchKernelGGL(jd_marker_apply_kernel<Src>, dim3((unsigned)k.nchunks, n), dim3(256), 0, st, src);
+            EG3D_LAUNCH_CHECK();
+        }
+    }
+    if (stages & EG3D_JPEGDEC_STAGE_SYNC) {
+        hipLaunchKernelGGL(jd_segments_kernel<Src>, dim3(1, n), dim3(JD_ONE), 0, st, src);
+        EG3D_LAUNCH_CHECK();
+        hipLaunchKernelGGL(jd_sync_kernel<Src>, dim3((unsigned)k.nwg, n), dim3(JD_LANES), 0, st, src);
+        EG3D_LAUNCH_CHECK();
+        hipLaunchKernelGGL(jd_stitch_kernel<Src>, dim3(1, n), dim3(JD_ONE), 0, st, src);
+        EG3D_LAUNCH_CHECK();
+    }
+    if (stages & EG3D_JPEGDEC_STAGE_WRITE) {
+        eg3d_zero_words(k.ws + k.zero_coef, k.zero_coef_words, st);
+        hipLaunchKernelGGL(jd_write_kernel<Src>, dim3((unsigned)k.nwg, n), dim3(JD_LANES), 0, st, src);
+        EG3D_LAUNCH_CHECK();
+    }
+    if (stages & EG3D_JPEGDEC_STAGE_IDCT) {
+        hipLaunchKernelGGL(jd_idct_kernel<Src>, dim3((unsigned)k.nblk, n), dim3(256), 0, st, src);
+        EG3D_LAUNCH_CHECK();
+    }
+    if (stages & EG3D_JPEGDEC_STAGE_COLOUR) {
+        hipLaunchKernelGGL(jd_colour_kernel<Src>, dim3((unsigned)k.tx, (unsigned)k.ty, n), dim3(256), 0, st, src);
+        EG3D_LAUNCH_CHECK();
+    }
+    return EG3D_OK;
+}
+
+// ---- one image -------------------------------------------------------------------------------------------------------------------------------------------
+int jd_one(const eg3d_jpegdec_params* p, JdImage& im, int64_t* off) {                // off: JD_FIELDS + 1 offsets, the last one the total
+    if (p == nullptr) return EG3D_ERR_INVALID;
+    const JdDesc d = {p->H, p->W, p->ncomp, p->hsamp, p->vsamp, p->restart_interval, p->tq, p->td, p->ta, p->data_bytes};
+    int64_t size[JD_FIELDS];
+    int s = jd_call_args(p->subseq_bytes, p->stages);
+    if (s == EG3D_OK) s = jd_geom(d, p->subseq_bytes, im.g, size, im.pw);
+    if (s != EG3D_OK) return s;
+    off[0] = 0;
+    for (int f = 0; f < JD_FIELDS; ++f) off[f + 1] = off[f] + size[f];
+    return EG3D_OK;
+}
+
+// ---- a batch ---------------------------------------------------------------------------------------------------------------------------------------------
+constexpr int JD_MAX_BATCH = 65535;                  // the image is a grid dimension
+
+int64_t jd_plan_bytes(int n) { return jd_align((int64_t)n * (int64_t)sizeof(JdImage)); }
+
+bool jd_batch_pointers(const eg3d_jpegdec_batch_params* p, int64_t total) {
+    return p->upload != nullptr && p->workspace != nullptr && p->result != nullptr && p->workspace_bytes >= total &&
+           !(reinterpret_cast<uintptr_t>(p->workspace) & (JD_ALIGN - 1)) && !(reinterpret_cast<uintptr_t>(p->upload) & (JD_ALIGN - 1));
+}
+
+// Every image's geometry and place.  The workspace holds range after range, each range image after image, so that what a call zeroes is
+// two stretches whatever the number of images.  plan (may be null): the records; k (may be null): the grid.
+int jd_batch(const eg3d_jpegdec_batch_params* p, JdImage* plan, JdGrid* k, int64_t* total) {
+    if (p == nullptr || p->images == nullptr || p->n < 1) return EG3D_ERR_INVALID;
+    if (p->n > JD_MAX_BATCH) return EG3D_ERR_TOO_LARGE;
+    int s = jd_call_args(p->subseq_bytes, p->stages);
+    if (s != EG3D_OK) return s;
+    int64_t range[JD_FIELDS + 1] = {0};              // bytes of every range over the batch, then their starts
+    JdGeom g;
+    int64_t size[JD_FIELDS];
+    int32_t pw[3];
+    for (int i = 0; i < p->n; ++i) {
+        const eg3d_jpegdec_image& q = p->images[i];
+        const JdDesc d = {q.H, q.W, q.ncomp, q.hsamp, q.vsamp, q.restart_interval, q.tq, q.td, q.ta, q.data_bytes};
+        s = jd_geom(d, p->subseq_bytes, g, size, pw);
+        if (s != EG3D_OK) return s;
+        if (k != nullptr) jd_grid_add(*k, g);
+        for (int f = 0; f < JD_FIELDS; ++f) range[f] += size[f];
+    }
+    int64_t at = 0;
+    for (int f = 0; f <= JD_FIELDS; ++f) {
+        const int64_t bytes = range[f];
+        range[f] = at;
+        at += bytes;
+    }
+    *total = range[JD_FIELDS];
+    if ((plan != nullptr || k != nullptr) && !jd_batch_pointers(p, *total)) return EG3D_ERR_INVALID;
+    if (k != nullptr) {
+        k->n = p->n;
+        k->ws = reinterpret_cast<char*>(p->workspace);
+        k->result = p->result;
+        k->zero_segs = range[F_SEG_START];
+        k->zero_segs_words = (range[F_EXIT] - range[F_SEG_START]) / 4;
+        k->zero_coef = range[F_COEF];
+        k->zero_coef_words = (range[F_PLANE0] - range[F_COEF]) / 4;
+    }
+    if (plan == nullptr) return EG3D_OK;
+    const int64_t head = jd_plan_bytes(p->n);
+    int64_t off[JD_FIELDS];
+    for (int f = 0; f < JD_FIELDS; ++f) off[f] = range[f];
+    for (int i = 0; i < p->n; ++i) {
+        const eg3d_jpegdec_image& q = p->images[i];
+        const JdDesc d = {q.H, q.W, q.ncomp, q.hsamp, q.vsamp, q.restart_interval, q.tq, q.td, q.ta, q.data_bytes};
+        JdImage& im = plan[i];
+        jd_geom(d, p->subseq_bytes, im.g, size, pw);
+        if (q.out == nullptr || q.data_offset < head || q.tables_offset < head || (q.data_offset & (JD_ALIGN - 1)) ||
+            q.data_offset + jd_align(q.data_bytes) > p->upload_bytes || q.tables_offset + EG3D_JPEGDEC_TABLE_BYTES > p->upload_bytes)
+            return EG3D_ERR_INVALID;
+        jd_bind(im, reinterpret_cast<char*>(p->workspace), off, pw);
+        im.raw = p->upload + q.data_offset;
+        im.blob = p->upload + q.tables_offset;
+        im.out = q.out;
+        im.result = p->result + (int64_t)i * EG3D_JPEGDEC_RESULT_WORDS;
+        for (int f = 0; f < JD_FIELDS; ++f) off[f] += size[f];
+    }
     return EG3D_OK;
 }
 
@@ -546,76 +799,64 @@ int jd_geom(const eg3d_jpegdec_params* p, JdGeom& g, JdLayout& l) {
 
 extern "C" int eg3d_jpegdec_query_workspace(const eg3d_jpegdec_params* p, int64_t* workspace_bytes) {
     if (workspace_bytes == nullptr) return EG3D_ERR_INVALID;
-    JdGeom g;
-    JdLayout l;
-    const int s = jd_geom(p, g, l);
+    JdImage im;
+    int64_t off[JD_FIELDS + 1];
+    const int s = jd_one(p, im, off);
     if (s != EG3D_OK) return s;
-    *workspace_bytes = l.total;
+    *workspace_bytes = off[JD_FIELDS];
     return EG3D_OK;
 }
 
 extern "C" int eg3d_jpegdec_decode(const eg3d_jpegdec_params* p, void* stream) {
-    JdGeom g;
-    JdLayout l;
-    const int s = jd_geom(p, g, l);
+    JdOne src;
+    int64_t off[JD_FIELDS + 1];
+    const int s = jd_one(p, src.im, off);
     if (s != EG3D_OK) return s;
-    if (p->data == nullptr || p->tables == nullptr || p->workspace == nullptr || p->out == nullptr || p->result == nullptr || p->workspace_bytes < l.total ||
-        (reinterpret_cast<uintptr_t>(p->workspace) & (JD_ALIGN - 1)) || (reinterpret_cast<uintptr_t>(p->data) & (JD_ALIGN - 1)))
+    if (p->data == nullptr || p->tables == nullptr || p->workspace == nullptr || p->out == nullptr || p->result == nullptr ||
+        p->workspace_bytes < off[JD_FIELDS] || (reinterpret_cast<uintptr_t>(p->workspace) & (JD_ALIGN - 1)) ||
+        (reinterpret_cast<uintptr_t>(p->data) & (JD_ALIGN - 1)))
         return EG3D_ERR_INVALID;
-    hipStream_t st = (hipStream_t)stream;
-    char* ws = reinterpret_cast<char*>(p->workspace);
-    int2* sums = reinterpret_cast<int2*>(ws + l.sums);
-    int2* offs = reinterpret_cast<int2*>(ws + l.offs);
-    uint8_t* unstuffed = reinterpret_cast<uint8_t*>(ws + l.stream);
-    int32_t* seg_start = reinterpret_cast<int32_t*>(ws + l.seg_start);
-    int32_t* lane_base = reinterpret_cast<int32_t*>(ws + l.lane_base);
-    unsigned long long* exit_state = reinterpret_cast<unsigned long long*>(ws + l.exit);
-    unsigned long long* entry_state = reinterpret_cast<unsigned long long*>(ws + l.entry);
-    int4* acc = reinterpret_cast<int4*>(ws + l.acc);
-    int4* pre = reinterpret_cast<int4*>(ws + l.pre);
-    int32_t* rounds = reinterpret_cast<int32_t*>(ws + l.rounds);
-    int16_t* coef = reinterpret_cast<int16_t*>(ws + l.coef);
-    uint8_t* planes = reinterpret_cast<uint8_t*>(ws + l.planes);
-    const int nwg = (g.Lmax + JD_LANES - 1) / JD_LANES;
-    const int stages = p->stages == 0 ? 31 : p->stages;
-    const uint32_t* words = reinterpret_cast<const uint32_t*>(unstuffed);
-    if (stages & EG3D_JPEGDEC_STAGE_MARKERS) {
-        eg3d_zero_words(p->result, EG3D_JPEGDEC_RESULT_WORDS, st);
-        eg3d_zero_words(seg_start, (l.exit - l.seg_start) / 4, st);                // segment starts and lane bases
-        EG3D_LAUNCH_CHECK();
-        if (g.nchunks > 0) {
-            hipLaunchKernelGGL(jd_marker_count_kernel, dim3((unsigned)g.nchunks), dim3(256), 0, st, p->data, g, sums, p->result);
-            EG3D_LAUNCH_CHECK();
-        }
-        hipLaunchKernelGGL(jd_marker_scan_kernel, dim3(1), dim3(JD_ONE), 0, st, sums, g, offs, seg_start, p->result);
-        EG3D_LAUNCH_CHECK();
-        if (g.nchunks > 0) {
-            hipLaunchKernelGGL(jd_marker_apply_kernel, dim3((unsigned)g.nchunks), dim3(256), 0, st, p->data, g, offs, unstuffed, seg_start, p->result);
-            EG3D_LAUNCH_CHECK();
-        }
-    }
-    if (stages & EG3D_JPEGDEC_STAGE_SYNC) {
-        hipLaunchKernelGGL(jd_segments_kernel, dim3(1), dim3(JD_ONE), 0, st, g, seg_start, lane_base, p->result);
-        EG3D_LAUNCH_CHECK();
-        hipLaunchKernelGGL(jd_sync_kernel, dim3((unsigned)nwg), dim3(JD_LANES), 0, st, p->tables, words, g, lane_base, seg_start, exit_state, entry_state, acc,
-                           rounds, p->result);
-        EG3D_LAUNCH_CHECK();
-        hipLaunchKernelGGL(jd_stitch_kernel, dim3(1), dim3(JD_ONE), 0, st, p->tables, words, g, lane_base, seg_start, exit_state, entry_state, acc, pre, rounds,
-                           p->result);
-        EG3D_LAUNCH_CHECK();
-    }
-    if (stages & EG3D_JPEGDEC_STAGE_WRITE) {
-        eg3d_zero_words(coef, (l.planes - l.coef) / 4, st);
-        hipLaunchKernelGGL(jd_write_kernel, dim3((unsigned)nwg), dim3(JD_LANES), 0, st, p->tables, words, g, lane_base, seg_start, exit_state, pre, coef, p->result);
-        EG3D_LAUNCH_CHECK();
-    }
-    if (stages & EG3D_JPEGDEC_STAGE_IDCT) {
-        hipLaunchKernelGGL(jd_idct_kernel, dim3((unsigned)((g.nblk + 31) / 32)), dim3(256), 0, st, coef, p->tables, g, l, planes);
-        EG3D_LAUNCH_CHECK();
-    }
-    if (stages & EG3D_JPEGDEC_STAGE_COLOUR) {
-        hipLaunchKernelGGL(jd_colour_kernel, dim3((unsigned)((g.W + 63) / 64), (unsigned)((g.H + 3) / 4)), dim3(256), 0, st, planes, g, l, p->out);
-        EG3D_LAUNCH_CHECK();
-    }
+    int32_t pw[3] = {src.im.pw[0], src.im.pw[1], src.im.pw[2]};
+    jd_bind(src.im, reinterpret_cast<char*>(p->workspace), off, pw);
+    src.im.raw = p->data;
+    src.im.blob = p->tables;
+    src.im.out = p->out;
+    src.im.result = p->result;
+    JdGrid k = {};
+    jd_grid_add(k, src.im.g);
+    k.n = 1;
+    k.ws = reinterpret_cast<char*>(p->workspace);
+    k.result = p->result;
+    k.zero_segs = off[F_SEG_START];
+    k.zero_segs_words = (off[F_EXIT] - off[F_SEG_START]) / 4;
+    k.zero_coef = off[F_COEF];
+    k.zero_coef_words = (off[F_PLANE0] - off[F_COEF]) / 4;
+    return jd_run(src, k, p->stages, (hipStream_t)stream);
+}
+
+extern "C" int eg3d_jpegdec_batch_query_workspace(const eg3d_jpegdec_batch_params* p, int64_t* workspace_bytes, int64_t* plan_bytes) {
+    if (workspace_bytes == nullptr || plan_bytes == nullptr) return EG3D_ERR_INVALID;
+    int64_t total = 0;
+    const int s = jd_batch(p, nullptr, nullptr, &total);
+    if (s != EG3D_OK) return s;
+    *workspace_bytes = total;
+    *plan_bytes = jd_plan_bytes(p->n);
     return EG3D_OK;
+}
+
+extern "C" int eg3d_jpegdec_batch_plan(const eg3d_jpegdec_batch_params* p) {
+    int64_t total = 0;
+    if (p == nullptr || p->plan == nullptr || (reinterpret_cast<uintptr_t>(p->plan) & 7)) return EG3D_ERR_INVALID;
+    return jd_batch(p, reinterpret_cast<JdImage*>(p->plan), nullptr, &total);
+}
+
+extern "C" int eg3d_jpegdec_batch_decode(const eg3d_jpegdec_batch_params* p, void* stream) {
+    JdGrid k = {};
+    int64_t total = 0;
+    const int s = jd_batch(p, nullptr, &k, &total);
+    if (s != EG3D_OK) return s;
+    for (int i = 0; i < p->n; ++i)
+        if (p->images[i].out == nullptr) return EG3D_ERR_INVALID;
+    const JdMany src = {reinterpret_cast<const JdImage*>(p->upload)};
+    return jd_run(src, k, p->stages, (hipStream_t)stream);
 }

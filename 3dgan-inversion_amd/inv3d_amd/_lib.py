@@ -343,6 +343,21 @@ class JpegDecParams(C.Structure):
                 ('subseq_bytes', C.c_int32), ('stages', C.c_int32)]
 
 
+class JpegDecImage(C.Structure):
+    """eg3d_jpegdec_image: one image of a batch."""
+    _fields_ = [('data_offset', C.c_int64), ('data_bytes', C.c_int64), ('tables_offset', C.c_int64), ('out', C.c_void_p), ('H', C.c_int32),
+                ('W', C.c_int32), ('ncomp', C.c_int32), ('hsamp', C.c_int32), ('vsamp', C.c_int32), ('tq', C.c_int32 * 3), ('td', C.c_int32 * 3),
+                ('ta', C.c_int32 * 3), ('restart_interval', C.c_int32), ('reserved', C.c_int32)]
+
+
+class JpegDecBatchParams(C.Structure):
+    """eg3d_jpegdec_batch_params: N baseline JPEG files in one call (eg3d_jpegdec_batch_query_workspace / _plan / _decode)."""
+    _fields_ = [('images', C.POINTER(JpegDecImage)), ('plan', C.c_void_p), ('upload', C.c_void_p), ('upload_bytes', C.c_int64),
+                ('workspace', C.c_void_p), ('workspace_bytes', C.c_int64), ('result', C.c_void_p), ('n', C.c_int32), ('subseq_bytes', C.c_int32),
+                ('stages', C.c_int32), ('reserved', C.c_int32)]
+
+
+JPEGDEC_MAX_BATCH = 65535                # the image is a grid dimension
 JPEGDEC_TABLE_BYTES = 256 + 4 * 272      # EG3D_JPEGDEC_TABLE_BYTES
 JPEGDEC_RESULT_WORDS = 8                 # EG3D_JPEGDEC_RESULT_WORDS
 JPEGDEC_STAGES = dict(markers=1, sync=2, write=4, idct=8, colour=16)      # EG3D_JPEGDEC_STAGE_*
@@ -581,6 +596,9 @@ _SIGS = {
     'eg3d_jpeg_pack': (C.c_int, [C.POINTER(JpegParams), C.c_void_p]),
     'eg3d_jpegdec_query_workspace': (C.c_int, [C.POINTER(JpegDecParams), C.POINTER(C.c_int64)]),
     'eg3d_jpegdec_decode': (C.c_int, [C.POINTER(JpegDecParams), C.c_void_p]),
+    'eg3d_jpegdec_batch_query_workspace': (C.c_int, [C.POINTER(JpegDecBatchParams), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    'eg3d_jpegdec_batch_plan': (C.c_int, [C.POINTER(JpegDecBatchParams)]),
+    'eg3d_jpegdec_batch_decode': (C.c_int, [C.POINTER(JpegDecBatchParams), C.c_void_p]),
     'eg3d_png_query_workspace': (C.c_int, [C.POINTER(PngParams), C.POINTER(C.c_int64)]),
     'eg3d_png_encode': (C.c_int, [C.POINTER(PngParams), C.c_void_p]),
     'eg3d_png_pack': (C.c_int, [C.POINTER(PngParams), C.c_void_p]),

@@ -2644,6 +2644,110 @@ def jpeg_decode(data, subseq_bytes: int = 128, device=None, stats: Optional[dict
     return out
 
 
+def _jpeg_file_bytes(data, who: str) -> bytes:
+    if isinstance(data, torch.Tensor):
+        if data.is_cuda or data.dtype != torch.uint8 or data.dim() != 1:
+            raise L.Eg3dHipError(f'{who}: the file as bytes or a host uint8 [n] tensor, got {data.dtype} {tuple(data.shape)} on {data.device}')
+        return data.contiguous().numpy().tobytes()
+    return bytes(data)
+
+
+def _jpegdec_batch_begin(raws, plans, subseq_bytes: int, device=None):
+    """Upload and allocate for one eg3d_jpegdec_batch_decode of already parsed files: (params, tensors the params point into, outs, result).
+    One host buffer -- the plan records, then per file the tables and the entropy-coded bytes -- goes up in one copy; outs are views of one
+    output buffer."""
+    B = int(subseq_bytes)
+    if not (16 <= B <= 1024 and B & (B - 1) == 0):
+        raise L.Eg3dHipError(f'jpeg_decode_batch: subseq_bytes a power of two in 16..1024, got {subseq_bytes}')
+    if not torch.cuda.is_available():
+        raise L.Eg3dHipError('jpeg_decode_batch: no GPU (there is no fallback path)')
+    dev = torch.device('cuda' if device is None else device)
+    n = len(raws)
+    images = (L.JpegDecImage * n)()
+    p = L.JpegDecBatchParams(images=images, n=n, subseq_bytes=B)
+    for im, plan in zip(images, plans):
+        comps = plan.components
+        im.H, im.W, im.ncomp, im.hsamp, im.vsamp = plan.height, plan.width, len(comps), comps[0].h, comps[0].v
+        im.restart_interval, im.data_bytes = plan.restart_interval, plan.scan_end - plan.scan_start
+        for c, comp in enumerate(comps):
+            im.tq[c], im.td[c], im.ta[c] = comp.tq, comp.td, comp.ta
+    ws_bytes, plan_bytes = C.c_int64(0), C.c_int64(0)
+    lib = L.lib()
+    L.check(lib.eg3d_jpegdec_batch_query_workspace(C.byref(p), C.byref(ws_bytes), C.byref(plan_bytes)), 'jpegdec_batch_query_workspace')
+    head = (L.JPEGDEC_TABLE_BYTES + 15) // 16 * 16
+    at, px = plan_bytes.value, 0
+    for im in images:                                                              # tables, then the entropy-coded segment, both 16-byte aligned
+        im.tables_offset, im.data_offset = at, at + head
+        at += head + (im.data_bytes + 15) // 16 * 16
+        px += im.H * im.W * 3
+    host = torch.zeros(at, dtype=torch.uint8)
+    view = host.numpy()
+    for im, raw, plan in zip(images, raws, plans):
+        view[im.tables_offset:im.tables_offset + L.JPEGDEC_TABLE_BYTES] = np.frombuffer(jpeg_decode_tables(plan), dtype=np.uint8)
+        view[im.data_offset:im.data_offset + im.data_bytes] = np.frombuffer(raw, dtype=np.uint8, count=im.data_bytes, offset=plan.scan_start)
+    blob = torch.empty(at, dtype=torch.uint8, device=dev)
+    ws = torch.empty(ws_bytes.value, dtype=torch.uint8, device=dev)
+    out = torch.empty(px, dtype=torch.uint8, device=dev)
+    result = torch.empty((n, L.JPEGDEC_RESULT_WORDS), dtype=torch.int32, device=dev)
+    outs, px = [], 0
+    for im in images:
+        im.out = out.data_ptr() + px
+        outs.append(out[px:px + im.H * im.W * 3].view(im.H, im.W, 3))
+        px += im.H * im.W * 3
+    p.plan, p.upload, p.upload_bytes, p.workspace, p.workspace_bytes, p.result = host.data_ptr(), blob.data_ptr(), at, ws.data_ptr(), ws_bytes.value, result.data_ptr()
+    L.check(lib.eg3d_jpegdec_batch_plan(C.byref(p)), 'jpegdec_batch_plan')                # (host only: the records, with the device addresses in them)
+    blob.copy_(host)                                                                     # the one upload
+    p.plan = None
+    return p, (images, blob, ws, out), outs, result
+
+
+def _jpegdec_stats(res) -> dict:
+    return dict(status=res[0], rounds=res[1] + res[2], rounds_workgroup=res[1], rounds_across=res[2], lanes=res[3], unstuffed_bytes=res[4],
+                restart_markers=res[5])
+
+
+def jpeg_decode_batch(files, subseq_bytes: int = 128, device=None, stats: Optional[list] = None, return_errors: bool = False,
+                      default_huffman: bool = False) -> list:
+    """[uint8 [H,W,3] on the device per file]: jpeg_decode's pixels for every file of `files` (bytes or host uint8 tensors; any mix of sizes,
+    samplings, restart intervals and tables) in ONE device call (eg3d_jpegdec_batch_*; include/eg3d_hip.h "Baseline JPEG decoder, N images per
+    call"): one host buffer, one upload, one workspace, one output buffer of which the returned contiguous tensors are views, the launches of
+    a single decode, one host synchronise (the statuses).  Every file is parsed by video.jpeg_scan_plan (default_huffman: Annex K's tables
+    for those a file does not define, as Motion-JPEG frames leave them out).  A file the parser does not take raises video.JpegUnsupported
+    before anything runs; else the first file the device refuses raises JpegDecodeRefused.  return_errors=True: nothing raises; the list
+    holds the exception instance in place of that file's tensor, files that fail the parse never enter the device batch and every other file
+    is decoded.  stats, if given, is a list that receives one dict per file as jpeg_decode fills it (None for a file that failed the
+    parse).  An empty `files` gives []."""
+    from . import video as V
+    raws = [_jpeg_file_bytes(f, 'jpeg_decode_batch') for f in files]
+    got: list = [None] * len(raws)
+    plans, taken = [], []
+    for i, raw in enumerate(raws):
+        try:
+            plans.append(V.jpeg_scan_plan(raw, default_huffman=default_huffman))
+            taken.append(i)
+        except V.JpegUnsupported as e:
+            if not return_errors:
+                raise
+            got[i] = e
+    per: list = [None] * len(raws)
+    if taken:
+        p, keep, outs, result = _jpegdec_batch_begin([raws[i] for i in taken], plans, subseq_bytes, device)
+        with torch.cuda.device(result.device):
+            L.check(L.lib().eg3d_jpegdec_batch_decode(C.byref(p), L.stream_ptr()), 'jpegdec_batch_decode')
+            res = result.tolist()                                                  # the one synchronise
+        del keep
+        for i, out, r in zip(taken, outs, res):
+            per[i] = _jpegdec_stats(r)
+            got[i] = out if r[0] == 0 else JpegDecodeRefused(r[0])
+    if stats is not None:
+        stats[:] = per
+    if not return_errors:
+        for g in got:
+            if isinstance(g, Exception):
+                raise g
+    return got
+
+
 PNG_FILTERS = dict(adaptive=-1, none=0, sub=1, up=2, average=3, paeth=4)
 
 

@@ -12,6 +12,8 @@
   e4e_image_transform      <- training/coaches/base_coach.py:41-45: ToPILImage, Resize((256, 256)), ToTensor, Normalize
   load_landmarks           <- a .json ({name: 68 x 2}) or .npz (one array per name) mapping
   load_targets             <- ImagesDataset / make_dataset + ToTensor / Normalize: the (name, target, None) tuples InversionCoach.run takes
+  decode_rgb_batch,        no reference counterpart: many files per device decode (hipops.jpeg_decode_batch), and the frames of a Motion-JPEG
+  video_targets               AVI (video.read_mjpeg_frames) as such tuples
 
 PIL decodes the files on the host (imported lazily, and only in decode_rgb); decoder='gpu' moves the decode of baseline JPEG files to the
 device as well (hipops.jpeg_decode, csrc/jpeg_decode.hip: the same bytes); everything after the decode runs on the device."""
@@ -355,13 +357,53 @@ def decode_rgb(path: str, device, decoder: str = 'pil', report=None) -> torch.Te
     return torch.from_numpy(arr).to(device)
 
 
+def decode_rgb_batch(paths, device, decoder: str = 'pil', report=None) -> list:
+    """[uint8 [H,W,3] on the device per path]: decode_rgb of every path, the same bytes and the same fallback rule per file.  decoder='gpu':
+    the files named .jpg / .jpeg go through ONE hipops.jpeg_decode_batch (one upload, the launches of a single decode, one synchronise for
+    all of them, whatever their sizes); those the device decoder does not take or refuses, and every other format, take the PIL path, and
+    report(path, reason) is told about every such JPEG, once."""
+    if decoder not in DECODERS:
+        raise ValueError(f'decode_rgb_batch: decoder one of {DECODERS}, got {decoder!r}')
+    paths = list(paths)
+    out = [None] * len(paths)
+    jpegs = [i for i, p in enumerate(paths) if p.lower().endswith(JPEG_EXTENSIONS)] if decoder == 'gpu' else []
+    if jpegs:
+        from . import hipops
+        files = []
+        for i in jpegs:
+            with open(paths[i], 'rb') as f:
+                files.append(f.read())
+        for i, got in zip(jpegs, hipops.jpeg_decode_batch(files, device=device, return_errors=True)):
+            if isinstance(got, Exception):
+                if report is not None:
+                    report(paths[i], str(got))
+            else:
+                out[i] = got
+    return [decode_rgb(p, device, 'pil') if o is None else o for p, o in zip(paths, out)]
+
+
+def _decoded(files, device, decoder: str, report, decode_batch: int):
+    """(name, path, uint8 [H,W,3]) over [(name, path)]: decode_rgb per file (decode_batch = 1), or decode_rgb_batch of decode_batch files."""
+    if decode_batch < 1:
+        raise ValueError(f'decode_batch >= 1, got {decode_batch}')
+    if decode_batch == 1:
+        for name, path in files:
+            yield name, path, decode_rgb(path, device, decoder, report)
+        return
+    for k in range(0, len(files), decode_batch):
+        block = files[k:k + decode_batch]
+        for (name, path), img in zip(block, decode_rgb_batch([p for _, p in block], device, decoder, report)):
+            yield name, path, img
+
+
 def write_aligned(directory: str, landmarks, out_dir: str, output_size: int = 512, device='cuda', png_encoder: str = 'host', batch: int = 8,
-                  report=None, decoder: str = 'pil', decode_report=None):
+                  report=None, decoder: str = 'pil', decode_report=None, decode_batch: int = 1):
     """{out_dir}/{name}.png for every image file of `directory` whose name has landmarks ({name: 68 x 2}, or the path of a .json / .npz):
     decoded on the host, aligned by align_face, written by video.write_png.  png_encoder='gpu': the aligned frames -- all output_size squared
     -- go `batch` at a time through one video.write_pngs (one encode, one copy).  Files without landmarks are passed to `report(path)` and
     skipped.  decoder='gpu': JPEG files are decoded on the device too (decode_rgb; decode_report(path, reason) hears of every JPEG that took
-    the PIL path instead); the files written are the same.  Returns the paths written."""
+    the PIL path instead); the files written are the same.  decode_batch > 1: the files with landmarks are decoded that many at a time
+    (decode_rgb_batch), to the same files in the same order.  Returns the paths written."""
     from . import video
     if decoder not in DECODERS:
         raise ValueError(f'write_aligned: decoder one of {DECODERS}, got {decoder!r}')
@@ -376,13 +418,15 @@ def write_aligned(directory: str, landmarks, out_dir: str, output_size: int = 51
         if pending:
             video.write_pngs([p for p, _ in pending], torch.stack([f for _, f in pending]))
             pending.clear()
+    files = []
     for name, path in image_files(directory):
-        if name not in landmarks:
-            if report is not None:
-                report(path)
-            continue
+        if name in landmarks:
+            files.append((name, path))
+        elif report is not None:
+            report(path)
+    for name, path, img in _decoded(files, device, decoder, decode_report, decode_batch):
         out = os.path.join(out_dir, name + '.png')
-        frame = align_face(decode_rgb(path, device, decoder, decode_report), landmarks[name], output_size)
+        frame = align_face(img, landmarks[name], output_size)
         if png_encoder == 'gpu':
             pending.append((out, frame))
             if len(pending) == batch:
@@ -394,11 +438,13 @@ def write_aligned(directory: str, landmarks, out_dir: str, output_size: int = 51
     return written
 
 
-def load_targets(directory: str, landmarks=None, output_size: int = 512, device='cuda', decoder: str = 'pil', decode_report=None):
+def load_targets(directory: str, landmarks=None, output_size: int = 512, device='cuda', decoder: str = 'pil', decode_report=None,
+                 decode_batch: int = 1):
     """[(name, target fp32 [1,3,S,S] in [-1,1] on the device, None)] for InversionCoach.run, S = output_size: every image file of `directory` in
     sorted order, decoded to RGB; aligned by align_face where `landmarks` (a {name: 68 x 2} mapping, or the path of a .json / .npz holding
     one) has its name, otherwise required to be S x S already; then ToTensor + Normalize(0.5, 0.5) (hipops.u8_to_target).  decoder='gpu':
-    JPEG files are decoded on the device (decode_rgb), to the same targets."""
+    JPEG files are decoded on the device (decode_rgb), to the same targets.  decode_batch > 1: the files are decoded that many at a time
+    (decode_rgb_batch), to the same targets in the same order."""
     from . import hipops
     if decoder not in DECODERS:
         raise ValueError(f'load_targets: decoder one of {DECODERS}, got {decoder!r}')
@@ -406,12 +452,36 @@ def load_targets(directory: str, landmarks=None, output_size: int = 512, device=
         landmarks = load_landmarks(landmarks)
     landmarks = landmarks or {}
     out = []
-    for name, path in image_files(directory):
-        img = decode_rgb(path, device, decoder, decode_report)
+    for name, path, img in _decoded(image_files(directory), device, decoder, decode_report, decode_batch):
         if name in landmarks:
             img = align_face(img, landmarks[name], output_size)
         elif tuple(img.shape[:2]) != (output_size, output_size):
             raise ValueError(f'load_targets: {path} is {img.shape[1]} x {img.shape[0]} and has no landmarks: give landmarks for it or a '
                              f'{output_size} x {output_size} image')
         out.append((name, hipops.u8_to_target(img), None))
+    return out
+
+
+def video_targets(path: str, landmarks=None, frames: slice = slice(None), output_size: int = 512, device='cuda', batch: int = 16, decoder: str = 'gpu',
+                  decode_report=None):
+    """load_targets for the frames of a Motion-JPEG AVI (video.read_mjpeg_frames: `batch` frames per device decode): [(name, target fp32
+    [1,3,S,S] in [-1,1] on the device, None)] for frames[start:stop:step] of the file, name = f'{stem}_{index:06d}' with the file's name up
+    to its first dot and the frame's index in the file.  A frame is aligned by align_face where `landmarks` ({name: 68 x 2}, or the path of
+    a .json / .npz) has its name; otherwise it is required to be S x S already."""
+    from . import hipops, video
+    if isinstance(landmarks, str):
+        landmarks = load_landmarks(landmarks)
+    landmarks = landmarks or {}
+    stem = os.path.basename(path).split('.')[0]
+    step = 1 if frames.step is None else frames.step
+    out = []
+    for first, block in video.read_mjpeg_frames(path, frames.start, frames.stop, step, batch=batch, device=device, decoder=decoder, report=decode_report):
+        for j in range(block.shape[0]):
+            name, img = f'{stem}_{first + j * step:06d}', block[j]
+            if name in landmarks:
+                img = align_face(img, landmarks[name], output_size)
+            elif tuple(img.shape[:2]) != (output_size, output_size):
+                raise ValueError(f'video_targets: frame {first + j * step} of {path} is {img.shape[1]} x {img.shape[0]} and has no landmarks: give '
+                                 f'landmarks for {name} or a {output_size} x {output_size} video')
+            out.append((name, hipops.u8_to_target(img), None))
     return out

@@ -8,6 +8,8 @@
   MjpegAviWriter               <- imageio.get_writer(mp4, mode='I', fps=60, codec='libx264') of gen_interp_video, gen_videos.py:74-146: there
                                   is no video encoder to call, so the container is a Motion-JPEG AVI (RIFF 'AVI ', one 'MJPG' video stream,
                                   'idx1' index) written here, the frames are the GPU encoder's JFIF files
+  MjpegAviReader,              no reference counterpart: such files read back -- this project's own, a camera's, ffmpeg's -- `batch` frames per
+  read_mjpeg_frames               hipops.jpeg_decode_batch, to PIL's pixels
   write_png                    <- PIL.Image.fromarray(...).save(png), single_id_coach.py:60,83 (zlib only; encoder='gpu': hipops.png_encode)
   png_container, write_pngs    the file around the GPU encoder's zlib streams; N same-size images in one encode
   write_orbit_video            <- gen_interp_video(G, w_pivot, path), single_id_coach.py:61-62,84-85
@@ -145,12 +147,14 @@ _SOF_NAMES = {0xC1: 'extended sequential', 0xC2: 'progressive', 0xC3: 'lossless'
               0xCD: 'arithmetic-coded differential sequential', 0xCE: 'arithmetic-coded differential progressive', 0xCF: 'arithmetic-coded differential lossless'}
 
 
-def jpeg_scan_plan(data) -> JpegScanPlan:
+def jpeg_scan_plan(data, default_huffman: bool = False) -> JpegScanPlan:
     """Parse a JPEG file's markers (SOI, APPn / COM skipped, DQT, SOF0, DHT, DRI, SOS, EOI) into what the GPU decoder needs.  Taken: 8-bit
     baseline (SOF0), Huffman-coded, one interleaved scan of three components sampled 1x1 / 2x1 / 2x2 beside 1x1 chroma, or one component;
     any legal Huffman tables, any restart interval.  Everything else raises JpegUnsupported with the reason: progressive, extended, 12-bit,
     arithmetic coding, several scans, four components, other sampling factors, 16-bit quantisation tables, an Adobe APP14 segment with
-    transform 0 (RGB-coded), a truncated header, a missing EOI.  EXIF orientation is ignored, as PIL's open().convert() ignores it."""
+    transform 0 (RGB-coded), a truncated header, a missing EOI.  EXIF orientation is ignored, as PIL's open().convert() ignores it.
+    default_huffman=True: a Huffman table a component uses and the file does not define is Annex K's (table 0 the luma one, table 1 the
+    chroma one) -- Motion-JPEG frames are commonly written without DHT, and libjpeg-turbo, so PIL, decodes them with these tables."""
     data = bytes(data)
     n = len(data)
     if n < 4 or data[:2] != b'\xff\xd8':
@@ -260,8 +264,11 @@ def jpeg_scan_plan(data) -> JpegScanPlan:
             raise JpegUnsupported(f'component {cid} uses quantisation table {tq}, which the file does not define')
         if td > 1 or ta > 1:
             raise JpegUnsupported(f'component {cid} uses Huffman table {max(td, ta)}: baseline has tables 0 and 1')
-        if (0, td) not in huff or (1, ta) not in huff:
-            raise JpegUnsupported(f'component {cid} uses a Huffman table the file does not define')
+        for key in ((0, td), (1, ta)):
+            if key not in huff:
+                if not default_huffman:
+                    raise JpegUnsupported(f'component {cid} uses a Huffman table the file does not define')
+                huff[key] = HUFFMAN[2 * key[1] + key[0]]
         out.append(JpegComponent(cid, h, v, tq, td, ta))
     if len(out) == 3:
         if adobe_transform == 0:
@@ -346,6 +353,182 @@ class MjpegAviWriter:
 
     def __exit__(self, *exc):
         self.close()
+
+
+class MjpegAviReader:
+    """The reading side of MjpegAviWriter, and of the Motion-JPEG AVI 1.0 files cameras and ffmpeg write: num_frames, fps, width, height,
+    frame_bytes(i) (one complete JPEG file), iteration over the frames' bytes, a context manager.  The first video stream is read; chunks of
+    other streams (audio) are skipped.  Frames are located by the 'idx1' index where there is one -- its offsets counted from the 'movi'
+    fourcc, as MjpegAviWriter and most writers count them, or from the start of the file: whichever lands on the frame's '##dc' / '##db'
+    chunk header -- and by walking the 'movi' list ('rec ' lists included, chunks padded to an even length) otherwise.  Refused with a
+    ValueError that names the reason: a file that is no RIFF 'AVI ', no video stream, a video stream that is not 'MJPG', OpenDML 'AVIX'
+    extensions (files beyond the first RIFF chunk), a zero-length frame chunk (a dropped frame), a chunk or index entry beyond the file."""
+
+    def __init__(self, path: str):
+        self.path = path
+        self._f = open(path, 'rb')
+        try:
+            self._parse()
+        except Exception:
+            self._f.close()
+            self._f = None
+            raise
+
+    def _read(self, pos: int, n: int) -> bytes:
+        self._f.seek(pos)
+        return self._f.read(n)
+
+    def _chunks(self, pos: int, end: int):
+        """(fourcc, payload position, payload size) of the chunks in [pos, end)"""
+        while pos + 8 <= end:
+            cc, size = struct.unpack('<4sI', self._read(pos, 8))
+            yield cc, pos + 8, size
+            pos += 8 + size + (size & 1)
+
+    def _parse(self) -> None:
+        size = self._f.seek(0, 2)
+        head = self._read(0, 12)
+        if len(head) < 12 or head[:4] != b'RIFF' or head[8:12] != b'AVI ':
+            raise ValueError(f"MjpegAviReader: {self.path} is no RIFF 'AVI ' file")
+        riff = struct.unpack('<I', head[4:8])[0]
+        riff_end = min(size, 8 + riff + (riff & 1)) if riff else size            # (a size never patched: the file was not closed)
+        self._stream, self._rate, self._micro, self._total, self._avih_size, self._strf = None, None, 0, 0, (0, 0), None
+        movi, idx1 = None, None
+        for cc, at, n in self._chunks(12, riff_end):
+            if cc == b'LIST':
+                kind = self._read(at, 4)
+                if kind == b'hdrl':
+                    self._headers(at + 4, min(at + n, size))
+                elif kind == b'movi' and movi is None:
+                    movi = (at, min(at + n, size))                                 # from the 'movi' fourcc
+            elif cc == b'idx1' and idx1 is None:
+                idx1 = (at, min(n, size - at))
+        for cc, at, n in self._chunks(riff_end, size):
+            if cc == b'RIFF' and self._read(at, 4) == b'AVIX':
+                raise ValueError(f"MjpegAviReader: {self.path} has OpenDML 'AVIX' extensions, which are not read")
+        if self._stream is None:
+            raise ValueError(f'MjpegAviReader: {self.path} has no video stream')
+        handler, comp, bw, bh = self._strf
+        if comp.upper() != b'MJPG' or (handler.upper() != b'MJPG' and handler != bytes(4)):
+            raise ValueError(f"MjpegAviReader: the video stream of {self.path} is {comp!r} (handler {handler!r}), not 'MJPG'")
+        if movi is None:
+            raise ValueError(f"MjpegAviReader: {self.path} has no 'movi' list")
+        self.width, self.height = (bw, abs(bh)) if bw > 0 and bh != 0 else self._avih_size
+        scale, rate = self._rate
+        self.fps = rate / scale if scale > 0 and rate > 0 else (1e6 / self._micro if self._micro > 0 else 0.0)
+        ids = (b'%02ddc' % self._stream, b'%02ddb' % self._stream)
+        frames = self._from_index(idx1, movi, ids, size) if idx1 is not None else None
+        if frames is None:
+            frames = []
+            self._walk(movi[0] + 4, movi[1], ids, frames)
+        for i, (at, n) in enumerate(frames):
+            if n == 0:
+                raise ValueError(f'MjpegAviReader: frame {i} of {self.path} is a zero-length chunk (a dropped frame)')
+            if at + n > size:
+                raise ValueError(f'MjpegAviReader: frame {i} of {self.path} lies beyond the end of the file')
+        self._frames = frames
+        self.num_frames = len(frames)
+
+    def _headers(self, pos: int, end: int) -> None:
+        number = 0
+        for cc, at, n in self._chunks(pos, end):
+            if cc == b'avih' and n >= 40:
+                a = struct.unpack('<10I', self._read(at, 40))
+                self._micro, self._total, self._avih_size = a[0], a[4], (a[8], a[9])
+            elif cc == b'LIST' and self._read(at, 4) == b'strl':
+                strh = strf = None
+                for c2, at2, n2 in self._chunks(at + 4, at + n):
+                    if c2 == b'strh' and n2 >= 36:
+                        strh = self._read(at2, 36)
+                    elif c2 == b'strf' and n2 >= 20:
+                        strf = self._read(at2, 20)
+                if self._stream is None and strh is not None and strh[:4] == b'vids' and strf is not None:
+                    self._stream = number
+                    self._rate = struct.unpack('<II', strh[20:28])
+                    bw, bh = struct.unpack('<ii', strf[4:12])
+                    self._strf = (strh[4:8], strf[16:20], bw, bh)
+                number += 1
+
+    def _from_index(self, idx1, movi, ids, size):
+        """[(payload position, size)] from 'idx1', or None where its offsets fit neither convention"""
+        raw = self._read(idx1[0], idx1[1] // 16 * 16)
+        entries = [e for e in struct.iter_unpack('<4sIII', raw) if e[0] in ids]
+        if not entries:
+            return None
+        cc, _, off, n = entries[0]
+        for base in (movi[0], 0):
+            if base + off + 8 <= size and self._read(base + off, 8) == cc + struct.pack('<I', n):
+                return [(base + o + 8, m) for _, _, o, m in entries]
+        return None
+
+    def _walk(self, pos: int, end: int, ids, frames) -> None:
+        for cc, at, n in self._chunks(pos, end):
+            if cc == b'LIST':
+                if self._read(at, 4) == b'rec ':
+                    self._walk(at + 4, at + n, ids, frames)
+            elif cc in ids:
+                frames.append((at, n))
+
+    def frame_bytes(self, i: int) -> bytes:
+        if not 0 <= i < self.num_frames:
+            raise IndexError(f'MjpegAviReader: frame {i} of {self.num_frames}')
+        at, n = self._frames[i]
+        return self._read(at, n)
+
+    def __len__(self) -> int:
+        return self.num_frames
+
+    def __iter__(self):
+        return (self.frame_bytes(i) for i in range(self.num_frames))
+
+    def close(self) -> None:
+        if self._f is not None:
+            self._f.close()
+            self._f = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
+def read_mjpeg_frames(path: str, start: int = 0, stop: Optional[int] = None, step: int = 1, batch: int = 16, device='cuda', decoder: str = 'gpu',
+                      report=None):
+    """A generator of (first_index, uint8 [n,H,W,3] on the device) over frames start:stop:step of a Motion-JPEG AVI (MjpegAviReader), n <=
+    `batch` frames at a time; frame j of a block is frame first_index + j * step of the file.  decoder='gpu': a block is one
+    hipops.jpeg_decode_batch with Annex K's Huffman tables for frames that carry none; a frame the device decoder does not take or refuses
+    goes through PIL and report(index, reason), if given, is told -- the rule of images.decode_rgb.  decoder='pil': every frame is decoded
+    on the host.  The pixels are PIL.Image.open(frame).convert('RGB') either way.  The frames of one file have one geometry: ValueError
+    otherwise."""
+    import io
+    if decoder not in ('pil', 'gpu') or batch < 1:
+        raise ValueError(f"read_mjpeg_frames: decoder 'pil' | 'gpu' and batch >= 1, got {decoder!r}, {batch}")
+
+    def pil(data):
+        from PIL import Image
+        with Image.open(io.BytesIO(data)) as im:
+            return torch.from_numpy(np.array(im.convert('RGB'), dtype=np.uint8)).to(device)
+    with MjpegAviReader(path) as reader:
+        shape = None
+        index = range(reader.num_frames)[slice(start, stop, step)]
+        for k in range(0, len(index), batch):
+            block = index[k:k + batch]
+            files = [reader.frame_bytes(i) for i in block]
+            if decoder == 'gpu':
+                from .hipops import jpeg_decode_batch
+                frames = jpeg_decode_batch(files, device=device, return_errors=True, default_huffman=True)
+                for j, f in enumerate(frames):
+                    if isinstance(f, Exception):
+                        if report is not None:
+                            report(block[j], str(f))
+                        frames[j] = pil(files[j])
+            else:
+                frames = [pil(f) for f in files]
+            if any(f.shape != frames[0].shape for f in frames) or (shape is not None and frames[0].shape != shape):
+                raise ValueError(f'read_mjpeg_frames: the frames of {path} differ in size')
+            shape = frames[0].shape
+            yield block[0], torch.stack(frames)
 
 
 def _png_chunk(tag: bytes, payload: bytes) -> bytes:

@@ -1647,7 +1647,7 @@ int eg3d_jpeg_pack(const eg3d_jpeg_params* p, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Baseline JPEG decoder (target-image ingestion: PIL.Image.open(path).convert('RGB') of utils/ImagesDataset.py and utils/align_data.py for
- * the files photographs arrive as; csrc/jpeg_decode.hip, csrc/jpeg_decode_core.h).  One image per call.  The output bytes are those of
+ * the files photographs arrive as; csrc/jpeg_decode.hip, csrc/jpeg_decode_core.h).  One image per call (N per call: the block after this one).  The output bytes are those of
  * libjpeg(-turbo)'s default decode; tests/support/jpegdec_ref.py restates it.  Integers only, no floating point anywhere; the only atomics
  * are ORs into the status word: the output is a function of the input bytes, bit-identical between runs and between the two builds.
  *   Taken: 8-bit baseline (SOF0) Huffman-coded files with one interleaved scan of three components -- luma sampled hsamp x vsamp = 1 x 1
@@ -1718,6 +1718,64 @@ typedef struct eg3d_jpegdec_params {
 } eg3d_jpegdec_params;
 int eg3d_jpegdec_query_workspace(const eg3d_jpegdec_params* p, int64_t* workspace_bytes);
 int eg3d_jpegdec_decode(const eg3d_jpegdec_params* p, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Baseline JPEG decoder, N images per call (a directory of photographs, the frames of a Motion-JPEG file; csrc/jpeg_decode.hip).  The
+ * stages, the arithmetic, the status bits and the result words are those of the one-image call above, per image; what changes is that every
+ * pass is launched once for the whole batch, so the number of launches does not depend on N and the serial rounds of stage 2 -- latency,
+ * not throughput, at the sizes of video frames -- run side by side for all images.
+ *   The images are heterogeneous: each has its own H, W, component count, sampling, restart interval, table selectors, tables and
+ *   entropy-coded bytes.  subseq_bytes and stages are per call.
+ *   Grid: the image is blockIdx.y (blockIdx.z in the colour pass), gridDim.x the largest image's count of workgroups for that pass; a
+ *   workgroup past its own image's count leaves at once.  The three one-workgroup kernels (marker scan, segments, stitch) run one
+ *   workgroup per image.  No prefix table is walked: a workgroup reads its image's record -- geometry and addresses -- from device memory
+ *   by its grid index.  A very large image beside many small ones therefore costs N times the large image's empty workgroups.
+ *   One upload: the caller lays out one host buffer as [plan | tables and entropy-coded bytes at offsets of its choice], has
+ *   eg3d_jpegdec_batch_plan fill the plan (host only: it needs the device addresses of the upload buffer, the workspace, the result and
+ *   every `out`, so those are allocated first) and copies the buffer to `upload` once.
+ *     images  host, [n]: per image the geometry as in eg3d_jpegdec_params; data_offset (a multiple of 16; the bytes are readable up to the
+ *             next multiple of 16) and tables_offset (EG3D_JPEGDEC_TABLE_BYTES) from `upload`, both at or beyond plan_bytes and inside
+ *             upload_bytes; out: device uint8 [H][W][3], any address
+ *     result  device int32 [n][EG3D_JPEGDEC_RESULT_WORDS].  A non-zero status of one image touches no other image's pixels or result.
+ *     workspace  range after range (sums, offsets, unstuffed stream, ..., coefficients, planes), each range image after image: what a call
+ *             zeroes is two stretches whatever n is.  Batch totals are 64-bit; per image the limits of the one-image call hold.
+ *   Every entropy-pass store is guarded by that image's geometry, reads beyond a segment's end yield zero bits, integers only, the only
+ *   atomics are ORs into an image's own status word: pixels are a function of the bytes, identical between runs and between the builds.
+ *   Errors before any launch: EG3D_ERR_INVALID (n < 1, NULL or misaligned pointers, an offset outside the upload, a short workspace, or
+ *   what the one-image call rejects, for any image), EG3D_ERR_UNSUPPORTED (sampling factors), EG3D_ERR_TOO_LARGE (n > 65535: the image is a
+ *   grid dimension; or an image beyond the one-image limits).
+ *     eg3d_jpegdec_batch_query_workspace  host only: workspace bytes, and the bytes of the plan at the start of `upload`
+ *     eg3d_jpegdec_batch_plan             host only: fills `plan` (plan_bytes, 8-byte aligned)
+ *     eg3d_jpegdec_batch_decode           the launches of the one-image call (twelve), no host synchronise; `upload` holds the copied plan
+ */
+typedef struct eg3d_jpegdec_image {
+    int64_t data_offset;               /* from `upload`: the entropy-coded segment, 16-byte aligned */
+    int64_t data_bytes;
+    int64_t tables_offset;             /* from `upload`: EG3D_JPEGDEC_TABLE_BYTES */
+    uint8_t* out;                      /* device uint8 [H][W][3] */
+    int32_t H, W;
+    int32_t ncomp;                     /* 1 | 3 */
+    int32_t hsamp, vsamp;
+    int32_t tq[3], td[3], ta[3];
+    int32_t restart_interval;          /* MCUs; 0 = none */
+    int32_t reserved;
+} eg3d_jpegdec_image;
+typedef struct eg3d_jpegdec_batch_params {
+    const eg3d_jpegdec_image* images;  /* host, [n] */
+    void* plan;                        /* host, plan_bytes: written by eg3d_jpegdec_batch_plan, copied by the caller to upload[0 .. plan_bytes) */
+    const uint8_t* upload;             /* device, upload_bytes, 16-byte aligned: plan, tables, entropy-coded bytes */
+    int64_t upload_bytes;
+    void* workspace;                   /* eg3d_jpegdec_batch_query_workspace's bytes, 16-byte aligned */
+    int64_t workspace_bytes;
+    int32_t* result;                   /* device int32 [n][EG3D_JPEGDEC_RESULT_WORDS] */
+    int32_t n;                         /* 1..65535 */
+    int32_t subseq_bytes;              /* 16..1024, a power of two */
+    int32_t stages;                    /* as eg3d_jpegdec_params.stages */
+    int32_t reserved;
+} eg3d_jpegdec_batch_params;
+int eg3d_jpegdec_batch_query_workspace(const eg3d_jpegdec_batch_params* p, int64_t* workspace_bytes, int64_t* plan_bytes);
+int eg3d_jpegdec_batch_plan(const eg3d_jpegdec_batch_params* p);
+int eg3d_jpegdec_batch_decode(const eg3d_jpegdec_batch_params* p, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * PNG encoder (media export: every lossless image the package writes -- grids, aligned targets, paste-back outputs, mesh previews, the OBJ

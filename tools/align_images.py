@@ -26,11 +26,14 @@ def main(argv=None):
     ap.add_argument('--output-size', type=int, default=512)
     ap.add_argument('--png-gpu', action='store_true', help='filter and deflate the PNGs on the GPU, eight frames per encode')
     ap.add_argument('--jpeg-gpu', action='store_true', help='decode baseline JPEG inputs on the GPU (hipops.jpeg_decode: the same pixels as PIL; other files take the PIL path)')
+    ap.add_argument('--decode-batch', type=int, default=1, metavar='N', help='--jpeg-gpu: decode N files per device call (hipops.jpeg_decode_batch: the same pixels)')
     a = ap.parse_args(argv)
+    if a.decode_batch < 1:
+        raise SystemExit('--decode-batch >= 1')
     from inv3d_amd import images
     written = images.write_aligned(a.in_dir, a.landmarks, a.out_dir, a.output_size, device=torch.device('cuda'),
                                    png_encoder='gpu' if a.png_gpu else 'host', report=lambda path: print(f'{path}: no landmarks, skipped'),
-                                   decoder='gpu' if a.jpeg_gpu else 'pil', decode_report=lambda path, why: print(f'{path}: decoded by PIL ({why})'))
+                                   decoder='gpu' if a.jpeg_gpu else 'pil', decode_report=lambda path, why: print(f'{path}: decoded by PIL ({why})'), decode_batch=a.decode_batch)
     for out in written:
         print(out)
     print(f'{len(written)} aligned images of {a.output_size} x {a.output_size} in {a.out_dir}')

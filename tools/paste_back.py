@@ -32,6 +32,7 @@ def main(argv=None):
     ap.add_argument('--feather', type=float, default=0.08)
     ap.add_argument('--png-gpu', action='store_true', help='encode the PNGs on the GPU (hipops.png_encode: adaptive filters, run-length deflate)')
     ap.add_argument('--jpeg-gpu', action='store_true', help='decode baseline JPEG inputs on the GPU (hipops.jpeg_decode: the same pixels as PIL; other files take the PIL path)')
+    ap.add_argument('--decode-batch', type=int, default=1, metavar='N', help='--jpeg-gpu: decode N files per device call (hipops.jpeg_decode_batch: the same pixels)')
     ap.add_argument('--mask', default=None)
     ap.add_argument('--mask-binary', action='store_true', help='--mask is a raw binary mask (nonzero = head): clean and feather it first')
     ap.add_argument('--matte-feather', type=float, default=0.03, help="--mask-binary: the matte edge's ramp as a fraction of the side")
@@ -39,6 +40,8 @@ def main(argv=None):
     ap.add_argument('--bbox', action='store_true')
     ap.add_argument('--paste-bands', default='0', metavar='N|auto', help='multi-band blend of 1..6 levels, or auto (images.paste_bands); 0: one alpha')
     a = ap.parse_args(argv)
+    if a.decode_batch < 1:
+        raise SystemExit('--decode-batch >= 1')
     from inv3d_amd import images, video
     try:
         bands = images.bands_arg(a.paste_bands)
@@ -64,8 +67,11 @@ def main(argv=None):
         raise SystemExit('--mask-binary belongs to --mask')
     os.makedirs(a.out_dir, exist_ok=True)
     written = []
-    for path in a.edit:
-        edit = images.decode_rgb(path, dev, decoder)
+    edits = []
+    for k in range(0, len(a.edit), a.decode_batch):
+        block = a.edit[k:k + a.decode_batch]
+        edits += images.decode_rgb_batch(block, dev, decoder) if a.decode_batch > 1 else [images.decode_rgb(p, dev, decoder) for p in block]
+    for path, edit in zip(a.edit, edits):
         out = os.path.join(a.out_dir, os.path.basename(path).split('.')[0] + '.png')
         video.write_png(out, images.paste_back(photo, edit, lms[key], feather=a.feather, mask=mask, region='bbox' if a.bbox else 'photo', **bkw),
                         encoder='gpu' if a.png_gpu else 'host')

@@ -12,7 +12,9 @@ already.  --weights: a generator archive (inv3d_amd.weights, tools/convert_eg3d_
 {out-dir}/pasted/{name}.png for every image that had landmarks: the tuned reconstruction blended back into the photograph it was aligned
 from (images.paste_back); with --paste-matte [--matte-feather F] [--matte-shrink F] through the head's own matte (images.head_matte, from the
 depth of the same render), so the photograph's background stays around the head; with --paste-bands N|auto blended through a Laplacian
-pyramid of N levels (images.paste_back(bands=...)) instead of the one alpha."""
+pyramid of N levels (images.paste_back(bands=...)) instead of the one alpha.  --video PATH [--frames A:B:S] in place of --in-dir: the targets are
+the frames of a Motion-JPEG AVI (images.video_targets; names {stem}_{index:06d}), decoded on the GPU --decode-batch frames per call;
+--decode-batch N with --in-dir --jpeg-gpu decodes N files per call."""
 import argparse
 import os
 import sys
@@ -44,7 +46,9 @@ def _generator(a, dev):
 
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.splitlines()[0])
-    ap.add_argument('--in-dir', required=True)
+    ap.add_argument('--in-dir', default=None, help='a directory of target images (or --video)')
+    ap.add_argument('--video', default=None, metavar='PATH', help='a Motion-JPEG AVI whose frames are the targets (images.video_targets)')
+    ap.add_argument('--frames', default=None, metavar='A:B:S', help='--video: the frames start:stop:step (default: all)')
     ap.add_argument('--out-dir', required=True)
     ap.add_argument('--landmarks', default=None)
     ap.add_argument('--weights', default=None, help='generator archive; default: a synthetic generator')
@@ -61,6 +65,7 @@ def main(argv=None):
     ap.add_argument('--gen-video', action='store_true')
     ap.add_argument('--png-gpu', action='store_true', help='encode the PNGs on the GPU (hipops.png_encode: adaptive filters, run-length deflate)')
     ap.add_argument('--jpeg-gpu', action='store_true', help='decode baseline JPEG inputs on the GPU (hipops.jpeg_decode: the same pixels as PIL; other files take the PIL path)')
+    ap.add_argument('--decode-batch', type=int, default=1, metavar='N', help='--jpeg-gpu: decode N files, or --video: N frames, per device call (hipops.jpeg_decode_batch: the same pixels)')
     ap.add_argument('--gen-mesh', action='store_true')
     ap.add_argument('--mesh-format', choices=('.mrc', '.ply'), default='.mrc')
     ap.add_argument('--mesh-res', type=int, default=512)
@@ -73,6 +78,18 @@ def main(argv=None):
     ap.add_argument('--matte-shrink', type=float, default=0.0, help='--paste-matte: move the matte edge inwards by this fraction of the aligned side')
     ap.add_argument('--paste-bands', default='0', metavar='N|auto', help='--paste-back: multi-band blend of 1..6 levels, or auto (images.paste_bands); 0: one alpha')
     a = ap.parse_args(argv)
+    if (a.in_dir is None) == (a.video is None):
+        raise SystemExit('one of --in-dir and --video')
+    if a.frames is not None and a.video is None:
+        raise SystemExit('--frames belongs to --video')
+    if a.video is not None and a.paste_back:
+        raise SystemExit('--paste-back takes photographs (--in-dir), not --video')
+    if a.decode_batch < 1:
+        raise SystemExit('--decode-batch >= 1')
+    try:
+        frames = slice(*[int(t) if t else None for t in a.frames.split(':')]) if a.frames else slice(None)
+    except (ValueError, TypeError):
+        raise SystemExit(f'--frames: A:B:S, got {a.frames!r}')
     if a.paste_matte and not a.paste_back:
         raise SystemExit('--paste-matte belongs to --paste-back')
     from inv3d_amd import images
@@ -87,9 +104,12 @@ def main(argv=None):
     G = _generator(a, dev)
     size = a.output_size or int(G.img_resolution)
     decoder = 'gpu' if a.jpeg_gpu else 'pil'
-    targets = images.load_targets(a.in_dir, a.landmarks, output_size=size, device=dev, decoder=decoder)
+    if a.video is not None:                                                # the device decoder unless told otherwise: frames come 16 at a time
+        targets = images.video_targets(a.video, a.landmarks, frames, output_size=size, device=dev, batch=a.decode_batch if a.decode_batch > 1 else 16)
+    else:
+        targets = images.load_targets(a.in_dir, a.landmarks, output_size=size, device=dev, decoder=decoder, decode_batch=a.decode_batch)
     if not targets:
-        raise SystemExit(f'no image files in {a.in_dir}')
+        raise SystemExit(f'no image files in {a.in_dir}' if a.video is None else f'no frames {a.frames} in {a.video}')
     sub = lambda d: os.path.join(a.out_dir, d)
     on_tuned = None
     if a.paste_back:
